@@ -15,13 +15,18 @@ Workload: ONE circuit for every N (strong scaling) -- BASELINE.json configs[4], 
 2x7-grid MRF, 256 GiB of complex128 amplitudes: it fits the 288 GiB of a single MI355X, so
 value(8) / value(1) is the 1 -> 8 GPU speed-up "at 34 qubits" of the north star (shards of
 256 / 128 / 64 / 32 GiB at N = 1 / 2 / 4 / 8).  On a smaller card the widest grid MRF one device
-holds is used instead (same rule on every rank).  --config i / --qubits W override.  At N = 1 the
-line also carries ``other_configs``: configs[2] (28 qubits, the HBM-roofline config) and
-configs[1] (20 qubits), same step definition, not part of ``value``.
+holds is used instead (same rule on every rank).  --config i / --qubits W override.
 theta = -halfnorm.rvs(scale=0.5), seed 1984; 4096 shots; seed_simulator 1984.
 
-The JSON line carries ``roofline`` (dominant kernel, HIP-event timed on its launch stream over
-the timed steps, algorithmic bytes of SURVEY.md 8(d)) and, at N=1, ``roofline_gate_sweeps_28q``
+A plain run sets up, warms up, times exactly --steps steps and prints one JSON line: ``value``,
+``ms_per_step`` (one timed step), the per-step breakdown and ``roofline`` (dominant kernel,
+HIP-event timed on its launch stream over the timed steps, algorithmic bytes of SURVEY.md 8(d)).
+--dump-outputs DIR also writes what the last timed step computed (see dump_outputs).
+
+Everything else runs only with --full.  The line then also carries ``validation`` (exact device
+checks of the last timed step), ``variants`` and, at N = 1, ``other_configs``: configs[2] (28 qubits,
+the HBM-roofline config) and configs[1] (20 qubits), same step definition, not part of ``value``;
+``roofline_gate_sweeps_28q``
 (BASELINE configs[2], the 28-qubit roofline config, with every fused gate SWEPT over the vector:
 the read+write ``k_multi`` pass is the "gate-apply sweep" of the north star), ``gate_microbench_28q``
 (one kernel per gate kind on a 28-qubit state: min / median / worst fraction of peak) and
@@ -59,10 +64,15 @@ def parse():
     ap.add_argument("--shots", type=int, default=4096)
     ap.add_argument("--fusion", type=int, default=3)
     ap.add_argument("--layout", default="auto")
-    ap.add_argument("--no-cpu", action="store_true", help="skip the cpu_baseline leg")
-    ap.add_argument("--no-variants", action="store_true", help="skip the extra (untimed-for-value) legs")
-    ap.add_argument("--variants", action="store_true", help="N > 1: run every extra leg (default there: the measured leg + the full-width-sweep leg)")
-    ap.add_argument("--with-exchange", action="store_true", help="N > 1, with --variants: also the reference-layout leg, which needs shard-bit exchanges "
+    ap.add_argument("--full", action="store_true",
+                    help="besides the timed steps: validation of the last step, the variant legs, other configs, the 28-qubit "
+                         "roofline legs, the gate micro-benchmark, the CPU baseline and (N > 1) the exchange legs")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed (counts and a seeded sample of the amplitudes) as DIR/<name>.npy")
+    ap.add_argument("--no-cpu", action="store_true", help="with --full: skip the cpu_baseline leg")
+    ap.add_argument("--no-variants", action="store_true", help="with --full: skip the extra (untimed-for-value) legs")
+    ap.add_argument("--variants", action="store_true", help="N > 1, with --full: run every extra leg (default there: the measured leg + the full-width-sweep leg)")
+    ap.add_argument("--with-exchange", action="store_true", help="N > 1, with --full --variants: also the reference-layout leg, which needs shard-bit exchanges "
                                                             "(RCCL between GPUs, peer-mapped shards when ranks share one)")
     ap.add_argument("--virtual-shards", type=int, default=0,
                     help="1 GPU: split the vector into this many shards on device 0 (config-4 rehearsal: real "
@@ -73,7 +83,7 @@ def parse():
     ap.add_argument("--no-fold", action="store_true",
                     help="fold_fresh off: every fused gate is applied as a sweep of the full vector (k_multi passes)")
     ap.add_argument("--option", action="append", default=[], help="engine option name=int")
-    ap.add_argument("--no-exchange-leg", action="store_true", help="N > 1: skip the reference-layout legs (RCCL / peer-mapped shard-bit exchanges)")
+    ap.add_argument("--no-exchange-leg", action="store_true", help="N > 1, with --full: skip the reference-layout legs (RCCL / peer-mapped shard-bit exchanges)")
     ap.add_argument("--exchange-deadline", type=float, default=150.0, help="seconds one exchange leg may take before it is abandoned")
     ap.add_argument("--exchange-child", action="store_true", help=argparse.SUPPRESS)   # internal: run only the exchange legs, print their JSON
     return ap.parse_args()
@@ -286,6 +296,43 @@ def validate_last_step(backend, comm, qc, cliques, theta, counts, shots):
                     ">= 4 x support shots passed the post-selection"}
 
 
+DUMP_AMPLITUDES = 8192          # size of the seeded amplitude sample --dump-outputs writes
+
+
+def dump_outputs(out_dir, backend, comm, counts):
+    """What the last timed step handed its caller, as float64 .npy files in out_dir (rank 0 writes):
+    counts_outcomes / counts -- the counts dict, outcome bit strings as integers in ascending order;
+    amplitude_index / amplitudes -- the state that step left in HBM at a fixed, seeded sample of
+    logical basis indices (all of them when the state has no more than DUMP_AMPLITUDES), as
+    (real, imag) rows.  Every rank reads the sampled amplitudes its own shard holds."""
+    eng, pl = backend.last_engine, backend.last_plan
+    W = len(pl.layout)
+    if 2 ** W <= DUMP_AMPLITUDES:
+        idx = np.arange(2 ** W, dtype=np.int64)
+    else:
+        idx = np.unique(np.random.RandomState(1984).randint(0, 2 ** W, size=DUMP_AMPLITUDES, dtype=np.int64))
+    phys = np.zeros_like(idx)
+    for q, pos in enumerate(pl.layout):                       # logical bit q -> physical bit pos (backend.statevector's map)
+        phys |= ((idx >> q) & 1) << pos
+    mine = [i for i, p in enumerate(phys) if not eng.multiproc or (int(p) >> eng.local_qubits) == eng.rank]
+    part = np.zeros((len(mine), 3), dtype=np.float64)
+    for r, i in enumerate(mine):
+        a = eng.amplitudes(int(phys[i]), 1)[0]
+        part[r] = (i, a.real, a.imag)
+    parts = comm.allgather(part)
+    if comm.rank != 0:
+        return
+    amp = np.full((idx.size, 2), np.nan)
+    for p in parts:
+        amp[p[:, 0].astype(np.int64)] = p[:, 1:]
+    assert not np.isnan(amp).any(), "an amplitude of the sample was read by no rank"
+    outcomes = np.array(sorted((int(k.replace(" ", ""), 2), v) for k, v in counts.items()), dtype=np.float64).reshape(-1, 2)
+    os.makedirs(out_dir, exist_ok=True)
+    for name, arr in (("counts_outcomes", outcomes[:, 0]), ("counts", outcomes[:, 1]),
+                      ("amplitude_index", idx.astype(np.float64)), ("amplitudes", amp)):
+        np.save(os.path.join(out_dir, name + ".npy"), arr)
+
+
 PMC_FILE = "profiles/pmc_traffic.json"
 
 
@@ -439,7 +486,10 @@ def main():
 
     main_leg = timed_leg(backend, comm, qc, args.shots, args.steps, args.warmup, options=args.option)
     elapsed, meta, agg = main_leg["elapsed"], main_leg["meta"], main_leg["agg"]
-    validation = validate_last_step(backend, comm, qc, cliques, theta, main_leg["counts"], args.shots)
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, backend, comm, main_leg["counts"])
+    # everything below up to the JSON line runs only with --full: a plain run times the steps and reports them
+    validation = validate_last_step(backend, comm, qc, cliques, theta, main_leg["counts"], args.shots) if args.full else None
     # host time per rank (what does not shrink with the rank count): compile + sample/merge/format of the timed steps
     host_by_rank = comm.allgather({k: round(v, 4) for k, v in main_leg["breakdown_ms"].items()}) if world > 1 else None
 
@@ -472,13 +522,13 @@ def main():
     # N > 1: besides the measured leg only the full-width-sweep leg (how the sweep path scales),
     # unless --variants asks for more; a leg that fails is recorded, not fatal (the host collectives
     # time out after 10 minutes instead of leaving the other ranks in a barrier for good)
-    if not args.no_variants:
+    if args.full and not args.no_variants:
         n = max(2, args.steps // 2)
         try:
             leg("full-width gate sweeps (fold_fresh off: init-fused pass + read/write k_multi passes)", n, fold_fresh=False)
         except Exception as e:                       # noqa: BLE001
             variants["full-width gate sweeps (fold_fresh off)"] = {"error": repr(e)[:300]}
-    if not args.no_variants and (world == 1 or args.variants):
+    if args.full and not args.no_variants and (world == 1 or args.variants):
         leg("full-width gate sweeps + zero tracking (opt-in: skips the provably-zero part of the vector)", n,
             fold_fresh=False, engine_options={"zero_tracking": 1})
         if world > 1 and args.with_exchange:
@@ -506,7 +556,7 @@ def main():
     # the "next" rows of SURVEY.md 8(f), measured by this run (N = 1): the diagonal-observable read pass on the resident
     # 34-qubit state (f4: qsv_expect_diag) and trajectory mode beyond statevector reach (f3)
     expect_roof = None
-    if world == 1 and not args.no_variants:
+    if args.full and world == 1 and not args.no_variants:
         eng = backend.last_engine
         if backend.last_plan is None or len(backend.last_plan.layout) != W:
             backend.run(qc, shots=0)
@@ -550,7 +600,7 @@ def main():
 
     # N = 1: the other single-GPU configs of BASELINE.json, same step definition (not part of `value`)
     other = {}
-    if world == 1 and not args.no_variants and not (args.qubits or args.config or args.virtual_shards):
+    if args.full and world == 1 and not args.no_variants and not (args.qubits or args.config or args.virtual_shards):
         for ci in (2, 1):
             oname, oc = wl.baseline_config(ci)
             oq = QCMRF(oc, wl.theta_halfnorm(wl.dimension(oc)))
@@ -565,7 +615,7 @@ def main():
     # fused gate swept over the vector (fold_fresh off) -- the read+write k_multi pass is the
     # "gate-apply sweep"; and one kernel per gate kind on a 28-qubit state (--gates in brief)
     sweeps28, gates28 = None, None
-    if world == 1 and not args.no_variants and not (args.qubits or args.config or args.virtual_shards):
+    if args.full and world == 1 and not args.no_variants and not (args.qubits or args.config or args.virtual_shards):
         oname, oc = wl.baseline_config(2)
         oq = QCMRF(oc, wl.theta_halfnorm(wl.dimension(oc)))
         nst = max(args.steps, 20)
@@ -601,7 +651,7 @@ def main():
     # once over the peer-mapped transport.  Never part of `value`.  A watchdog keeps a transport
     # that hangs from taking the already measured line down with it.
     exchange_legs = None
-    if world > 1 and not args.no_exchange_leg:
+    if args.full and world > 1 and not args.no_exchange_leg:
         backend.close()                       # its numbers are in; the legs allocate their own shards
         if n_dev >= world:
             exchange_legs = exchange_legs_in_child_processes(args, rank)
@@ -637,9 +687,10 @@ def main():
             "breakdown_ms_by_rank": host_by_rank,
             "kernels": main_leg["kernels"],
             "roofline": roof,
-            "validation": validation,
         }
-        line["variants"] = variants
+        if args.full:
+            line["validation"] = validation
+            line["variants"] = variants
         # the same circuit with every fused gate swept over the full vector (fold_fresh off): the
         # read+write k_multi pass is the "gate-apply sweep" of BASELINE.json's metric
         for vname, v in variants.items():
@@ -662,7 +713,7 @@ def main():
             line["rccl_ranks"] = exchange_legs.get("rccl_ranks", 0)
         if other:
             line["other_configs"] = other
-        if args.gpus == 1 and not args.no_cpu:
+        if args.full and args.gpus == 1 and not args.no_cpu:
             backend.close()
             line["cpu_baseline"] = cpu_baseline(cliques, theta, args.shots, args.cpu_seconds)
             # the port executes the UNFUSED reference-order stream: the GPU number that does the same work is the
@@ -677,7 +728,7 @@ def main():
     if world > 1:
         comm.barrier()
         comm.close()
-    if rank == 0 and not validation["ok"]:
+    if rank == 0 and validation is not None and not validation["ok"]:
         sys.exit("bench.py: the state the timed steps left in HBM failed validation (see \"validation\" in the line above)")
 
 
