@@ -271,7 +271,9 @@ int qsv_timer_end(qsv_handle* h, double* ms);
  *   kernels     unroll [4], lowt_shuffle [1], pair_variant [0], kq_mfma [1], blocks_per_cu [65536]
  *               swizzle [1]        one-gate kernels: lane bit 5 of a wave access carries address bit 11 (two 512-byte runs 32 KiB apart);
  *                                  1 from 2^26 amplitudes per shard, 2 from 2^14, 0 never        lane_map_min_l [26]  same for k_multi tiles other than bits 6..10
- *   other       zero_tracking [0]  skip amplitudes known to be zero (opt-in)       exchange_chunk_log2 [24]  amplitudes per exchange chunk */
+ *   other       zero_tracking [0]  skip amplitudes known to be zero (opt-in)       exchange_chunk_log2 [24]  amplitudes per exchange chunk
+ *               implied_zeros [1]  the generator as a program's last pass (and qsv_exec's end) leaves the provably-zero part
+ *                                  of a shard unwritten; every reader honours that or writes the zeros first (0: write them always) */
 int qsv_set_option(qsv_handle* h, const char* name, int value);
 
 const char* qsv_last_error(void);

@@ -135,7 +135,7 @@ struct Shard {
   hipEvent_t ev_packed[2] = {nullptr, nullptr}, ev_sent[2] = {nullptr, nullptr}, ev_unpacked[2] = {nullptr, nullptr};
   hipEvent_t ev_start = nullptr;
   int n_cu = 256;
-  uint64_t zmask = 0;            // zero tracking: local bits known |0>; memory with such a bit set is unwritten
+  uint64_t zmask = 0;            // local bits known |0>: memory at an address with such a bit set is undefined (implied zeros, materialize)
   std::vector<double> h_sums;    // host copy of the block sums, valid until the state changes
   bool sums_valid = false;
   // sums left behind by the last k_multi pass of a program, one per workgroup tile (no read pass)
@@ -214,6 +214,7 @@ struct qsv_handle {
   int opt_fused_sums = 1;             // last k_multi pass of a program also leaves the per-tile |amp|^2 sums
   int opt_kq_mfma = 1;                // dense k >= 3 gates on the f64 matrix cores
   int opt_zero_tracking = 0;          // opt-in: skip the part of the shard that is provably still zero
+  int opt_implied_zeros = 1;          // the generator as a program's last pass leaves its zero half unwritten (zmask), and so does qsv_exec
   int opt_multi_nt = -1;              // k_multi with non-temporal loads + stores: -1 shards of >= 2^26 amplitudes, 0 never, 1 always
   int opt_init_prod_nt = -1;          // generator with non-temporal stores: -1 by shard size, 0 never, 1 always
   int opt_xframe = 1;                 // uncontrolled X gates inside a pass become an XOR on its store addresses
@@ -672,6 +673,31 @@ extern "C" int qsv_init_uniform(qsv_handle* h, uint64_t qubit_mask) {
   return QSV_OK;
 }
 extern "C" int qsv_init_zero(qsv_handle* h) { return qsv_init_uniform(h, 0ull); }
+
+// Implied zeros: while s.zmask != 0 the memory at every local address with a zmask bit set is undefined and the state is
+// zero there (zero tracking; the generator as a program's last pass, option implied_zeros).  Every entry point that reads
+// the shard, or writes part of it, either honours zmask or calls this first: it writes those zeros (k_fill_zero).  The
+// state does not change, so the cached block / tile sums stay valid.
+static int materialize(qsv_handle* h, Shard& s) {
+  if (!s.zmask) return QSV_OK;
+  const uint64_t n = amps_local(h);
+  const uint64_t zm = s.zmask;
+  s.zmask = 0;
+  CHK(shard_set(s));
+  const bool sv = s.sums_valid, tv = s.tile_valid, hv = s.h_tsums_valid;
+  const int nz = __builtin_popcountll(zm);
+  CHK(launch(h, s, QSV_K_INIT, 16.0 * ((double)n - (double)(n >> nz)), [&] {
+    hipLaunchKernelGGL(k_fill_zero, dim3(grid_for(h, s, n, QSV_TPB * 4)), dim3(QSV_TPB), 0, s.stream, s.amp, n, zm);
+  }));
+  s.sums_valid = sv;
+  s.tile_valid = tv;
+  s.h_tsums_valid = hv;
+  return QSV_OK;
+}
+static int materialize_all(qsv_handle* h) {
+  for (Shard& s : h->shards) CHK(materialize(h, s));
+  return QSV_OK;
+}
 
 // The rest of the host side, in dependency order (one translation unit):
 #include "qsv_gates.inc"     // LocalOp, validation, per-shard resolution, single-gate launchers, qsv_apply_*

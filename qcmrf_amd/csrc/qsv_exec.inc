@@ -11,6 +11,17 @@ extern "C" int qsv_exec(qsv_handle* h, const qsv_op* ops, int n_ops, const doubl
     return QSV_OK;
   };
   for (Shard& s : h->shards) s.tile_fresh = false;
+  // An init sets a shard's zmask when it is parsed, before anything is written.  If the program fails before that write
+  // (a bad op later on), the shard still holds the previous state: its zmask goes back to the one that describes it.
+  std::vector<uint64_t> zheld(ns);
+  struct InitGuard {
+    qsv_handle* h;
+    const std::vector<PendingGroup>& pend;
+    const std::vector<uint64_t>& zheld;
+    ~InitGuard() { for (size_t k = 0; k < pend.size(); ++k) if (pend[k].init) h->shards[k].zmask = zheld[k]; }
+  } init_guard{h, pend, zheld};
+  // implied zeros left by the previous program: an init supersedes them, anything else sees the zeros written first
+  if (n_ops > 0 && ops[0].kind != QSV_OP_INIT_ZERO && ops[0].kind != QSV_OP_INIT_UNIFORM) CHK(materialize_all(h));
   // An init write is pending and nothing has been applied since: an uncontrolled Hadamard on a qubit that is still |0> is
   // part of that write (|0> -> |+>: the qubit joins the uniform mask) -- the same merge the INIT-fused pass is, one step
   // earlier.  The reference's stream opens with H on every variable qubit (QCMRF.py:204-205): gate by gate they cost a
@@ -44,6 +55,7 @@ extern "C" int qsv_exec(qsv_handle* h, const qsv_op* ops, int n_ops, const doubl
           pend[k].init = true;
           pend[k].initval = (hi & ~mask) ? 0.0 : val;
           pend[k].nonmask = ~mask & (amps_local(h) - 1);
+          zheld[k] = h->shards[k].zmask;
           h->shards[k].zmask = h->opt_zero_tracking ? pend[k].nonmask : 0ull;
         }
         init_streak = h->opt_fold_init_h != 0;
@@ -127,7 +139,7 @@ extern "C" int qsv_exec(qsv_handle* h, const qsv_op* ops, int n_ops, const doubl
   h->exec_ops_left = 1 << 30;
   CHK(flush_all(true));
   for (Shard& s : h->shards) {
-    CHK(materialize(h, s));                  // writes zeros only: the tile sums stay right
+    if (!h->opt_implied_zeros) CHK(materialize(h, s));   // else the zero region stays implied (s.zmask, materialize)
     s.tile_valid = s.tile_fresh;
     s.tile_fresh = false;
   }
@@ -187,6 +199,7 @@ extern "C" int qsv_set_option(qsv_handle* h, const char* name, int value) {
   else if (!strcmp(name, "pair_variant")) h->opt_pair_variant = value;
   else if (!strcmp(name, "kq_mfma")) h->opt_kq_mfma = value != 0;
   else if (!strcmp(name, "zero_tracking")) h->opt_zero_tracking = value != 0;
+  else if (!strcmp(name, "implied_zeros")) h->opt_implied_zeros = value != 0;
   else if (!strcmp(name, "lane_map")) h->opt_lane_map = value;
   else if (!strcmp(name, "lane_map_min_l")) h->opt_lane_map_min_l = value;
   else if (!strcmp(name, "init_prod_bit0")) h->opt_init_prod_bit0 = value;

@@ -289,6 +289,7 @@ static int apply_gate(qsv_handle* h, int kind, int n, const int* q, const int* v
                       const double* data, double angle) {
   if (!h) return fail(QSV_E_BADARG, "NULL handle");
   CHK(validate_gate(h, kind, n, q, target, kind == QSV_OP_MCX || kind == QSV_OP_MCPHASE ? (const void*)h : (const void*)data));
+  CHK(materialize_all(h));                         // the one-gate kernels read every amplitude
   LocalOp lo;
   for (Shard& s : h->shards)
     if (resolve_gate(h, s, kind, n, q, vals, target, data, angle, lo)) CHK(run_single(h, s, lo));

@@ -661,6 +661,13 @@ __global__ __launch_bounds__(QSV_TPB) void k_reduce_pairs(const double* __restri
 // touch exactly one register bit are expanded bit by bit (1 -> 2 -> 4 ... 2^R values: 2^(R+1) - 2
 // complex multiplies for the whole tile instead of 2^R per factor); only factors on two or more
 // register bits cost one multiply per amplitude.  Roofline: HBM write, 16 B / amplitude.
+// zskip != 0 (the generator is its program's last pass, implied zeros): amplitudes with a zskip bit set -- a subset of
+// the ones nonmask makes zero -- are not stored; the shard's zmask says so.  Such a register bit drops its half of
+// every thread's stores (a uniform branch), a zskip thread bit its threads' stores; a tile whose block bits hit zskip
+// only gets its sum, 0.  Tiles keep their index and their sums stay bit-identical: what is skipped adds exactly +-0.
+// At 34 qubits (zero bit = register bit 3) the half write takes 32.5 ms against 38.5 ms: the per-thread factor
+// arithmetic, no longer hidden behind 16 stores, bounds it.  Two tiles per workgroup (16 stores per thread) measured
+// the same, so they were not kept.
 // ---------------------------------------------------------------------------------------
 struct ProdFactor {
   int nlist;                      // table index bit e <- address bit pos[e] (pos[e] < 0: a register bit)
@@ -675,20 +682,26 @@ template <int R, bool NT>
 __global__ __launch_bounds__(QSV_TPB) void k_init_prod(cplx* __restrict__ amp, uint64_t nthreads, BitIns ins, RegPos rp,
                                                        LanePos lp, const ProdFactor* __restrict__ fac, ProdCounts cnt,
                                                        const cplx* __restrict__ tables, int ntab, uint64_t nonmask,
-                                                       double initval, double* __restrict__ tile_sums) {
+                                                       double initval, double* __restrict__ tile_sums,
+                                                       uint64_t zskip, unsigned zreg) {
   extern __shared__ double4 lds_raw[];
   cplx* lt = reinterpret_cast<cplx*>(lds_raw);
+  const uint64_t base_blk = tile_base_blk(blockIdx.x, ins, lp);
+  if (base_blk & zskip) {                          // the whole tile is implied zero (uniform: no barrier crossed)
+    if (tile_sums && threadIdx.x == 0) tile_sums[blockIdx.x] = 0.0;
+    return;
+  }
   for (int i = threadIdx.x; i < ntab; i += QSV_TPB) lt[i] = tables[i];
   __syncthreads();
   const uint64_t gb = (uint64_t)blockIdx.x * QSV_TPB;
   if (gb + threadIdx.x >= nthreads) return;
-  const uint64_t base_blk = tile_base_blk(blockIdx.x, ins, lp);
   const uint32_t base_thr = tile_base_thr(threadIdx.x, ins, lp);
-  const uint64_t base = base_blk | base_thr;
-  cplx* __restrict__ pblk = amp + base_blk;
+  const bool store = (base_thr & zskip) == 0;
   uint64_t ob[R > 0 ? R : 1];
 #pragma unroll
   for (int c = 0; c < R; ++c) ob[c] = 1ull << rp.pos[c];
+  const uint64_t base = base_blk | base_thr;
+  cplx* __restrict__ pblk = amp + base_blk;
   // factors without a register bit: one scalar per thread
   cplx f = make_double2(((base & nonmask) == 0) ? initval : 0.0, 0.0);
   int k0 = 0;
@@ -703,20 +716,23 @@ __global__ __launch_bounds__(QSV_TPB) void k_init_prod(cplx* __restrict__ amp, u
   a[0] = f;
 #pragma unroll
   for (int c = 0; c < R; ++c) {
-    // both values of register bit c: product of the factors that see this bit and no other
+    // both values of register bit c: product of the factors that see this bit and no other.  Register combinations with
+    // a zreg bit are implied zeros: they are set to 0 and cost no arithmetic (uniform branches)
+    const bool zc = (zreg >> c) & 1u;
     cplx t0 = make_double2(1.0, 0.0), t1 = make_double2((ob[c] & nonmask) ? 0.0 : 1.0, 0.0);
     for (int k = k0; k < k0 + cnt.nsingle[c]; ++k) {
       const ProdFactor& pf = fac[k];
       uint32_t jt = 0;
       for (int e = 0; e < pf.nlist; ++e) if (pf.pos[e] >= 0) jt |= (uint32_t)((base >> pf.pos[e]) & 1ull) << e;
       t0 = cmul(t0, lt[pf.tab + jt]);
-      t1 = cmul(t1, lt[pf.tab + jt + pf.regw[c]]);
+      if (!zc) t1 = cmul(t1, lt[pf.tab + jt + pf.regw[c]]);
     }
     k0 += cnt.nsingle[c];
 #pragma unroll
     for (int j = 0; j < (1 << c); ++j) {
-      a[j | (1 << c)] = cmul(a[j], t1);
-      a[j] = cmul(a[j], t0);
+      if (((unsigned)j & zreg) || zc) a[j | (1 << c)] = make_double2(0.0, 0.0);
+      else a[j | (1 << c)] = cmul(a[j], t1);
+      if (!((unsigned)j & zreg)) a[j] = cmul(a[j], t0);
     }
   }
   for (int k = k0; k < k0 + cnt.nmulti; ++k) {
@@ -726,6 +742,7 @@ __global__ __launch_bounds__(QSV_TPB) void k_init_prod(cplx* __restrict__ amp, u
     const cplx* tp = lt + pf.tab + jt;
 #pragma unroll
     for (int j = 0; j < (1 << R); ++j) {
+      if ((unsigned)j & zreg) continue;
       int jr = 0;
 #pragma unroll
       for (int c = 0; c < R; ++c) if ((j >> c) & 1) jr += pf.regw[c];
@@ -735,10 +752,11 @@ __global__ __launch_bounds__(QSV_TPB) void k_init_prod(cplx* __restrict__ amp, u
   double psum = 0.0;
 #pragma unroll
   for (int j = 0; j < (1 << R); ++j) {
+    if ((unsigned)j & zreg) continue;              // implied zero: a[j] is 0, not stored, adds 0 to the sum
     uint64_t off = 0;
 #pragma unroll
     for (int c = 0; c < R; ++c) if ((j >> c) & 1) off |= ob[c];
-    if (NT) st_nt((pblk + off) + base_thr, a[j]); else (pblk + off)[base_thr] = a[j];
+    if (store) { if (NT) st_nt((pblk + off) + base_thr, a[j]); else (pblk + off)[base_thr] = a[j]; }
     psum = fma(a[j].x, a[j].x, fma(a[j].y, a[j].y, psum));
   }
   if (tile_sums) {
@@ -1276,12 +1294,14 @@ __global__ __launch_bounds__(QSV_TPB) void k_pair_x(cplx* __restrict__ amp, uint
 }
 
 // one workgroup per shot, tiles in the order the last k_multi pass left them: thread t owns the
-// 2^R amplitudes base(t) | off(j); find the first (t, j) whose running |amp|^2 exceeds resid[s]
+// 2^R amplitudes base(t) | off(j); find the first (t, j) whose running |amp|^2 exceeds resid[s].
+// Addresses with a zmask bit set are implied zeros (undefined memory): p = 0 there, nothing is loaded.
 template <int R>
 __global__ __launch_bounds__(QSV_TPB) void k_locate_tile(const cplx* __restrict__ amp, BitIns ins, RegPos rp, LanePos lp,
                                                          const uint64_t* __restrict__ blk,
                                                          const double* __restrict__ resid,
-                                                         uint64_t* __restrict__ out, uint64_t shots, uint64_t xmask) {
+                                                         uint64_t* __restrict__ out, uint64_t shots, uint64_t xmask,
+                                                         uint64_t zmask) {
   __shared__ double wtot[QSV_TPB / 64];
   __shared__ unsigned long long found;
   __shared__ unsigned long long lastnz;
@@ -1297,7 +1317,8 @@ __global__ __launch_bounds__(QSV_TPB) void k_locate_tile(const cplx* __restrict_
       uint64_t off = 0;
 #pragma unroll
       for (int c = 0; c < R; ++c) if ((j >> c) & 1) off |= 1ull << rp.pos[c];
-      const cplx a = amp[base ^ off];                     // (tile address | off) ^ xmask
+      const uint64_t i = base ^ off;                      // (tile address | off) ^ xmask
+      const cplx a = (i & zmask) ? make_double2(0.0, 0.0) : amp[i];
       p[j] = fma(a.x, a.x, a.y * a.y);
       mine += p[j];
     }

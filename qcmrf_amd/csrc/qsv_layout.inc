@@ -125,6 +125,7 @@ extern "C" int qsv_apply_kq(qsv_handle* h, int k, const int* qubits, const doubl
     if (qubits[b] >= h->L)
       return fail(QSV_E_UNSUPPORTED, "qubit %d of a dense gate is a shard bit (local qubits: %d); qsv_swap_layout it first", qubits[b], h->L);
   if (h->L < k) return fail(QSV_E_BADARG, "dense %d-qubit gate on %d local qubits", k, h->L);
+  CHK(materialize_all(h));
   const uint64_t n = amps_local(h);
 
   // matrix-core path: K = 4, 5 natively; K = 3 embedded as I (x) U on one extra (free) qubit
@@ -499,6 +500,8 @@ extern "C" int qsv_swap_layout(qsv_handle* h, int npairs, const int* a, const in
     if (std::min(a[i], b[i]) >= h->L)
       return fail(QSV_E_UNSUPPORTED, "swap of two shard bits (%d,%d) is not implemented; route through a local bit", a[i], b[i]);
   }
+  // a local swap reads every amplitude, and an exchange partner must never read undefined memory
+  CHK(materialize_all(h));
   // pairs that touch distinct qubits commute: the local ones run as permutation sweeps, ALL the
   // shard-bit ones as ONE batched exchange (an all-to-all inside each group of 2^k shards)
   std::vector<int> G, J;

@@ -43,6 +43,7 @@ static int block_sums(qsv_handle* h, Shard& s, SumView& sums) {
   if (s.sums_valid && h->opt_cache_sums) { sums.p = s.h_sums.data(); sums.n = s.h_sums.size(); return QSV_OK; }
   const uint64_t n = amps_local(h);
   const uint64_t nblk = (n + QSV_SBLOCK - 1) / QSV_SBLOCK;
+  CHK(materialize(h, s));                   // the block-sum pass (and k_locate after it) read every amplitude
   CHK(shard_set(s));
   CHK(launch(h, s, QSV_K_PROB, 16.0 * (double)n, [&] {
     const bool nt = h->opt_multi_nt > 0 || (h->opt_multi_nt < 0 && h->L >= 26);       // a read stream beyond the caches
@@ -158,13 +159,14 @@ extern "C" int qsv_sample(qsv_handle* h, uint64_t shots, uint64_t seed, const in
       }
       if (bs.super) {                     // tile order of the program's last pass
         const dim3 g((unsigned)std::min<uint64_t>(cnt, 65535));
-#define LT(RR) hipLaunchKernelGGL((k_locate_tile<RR>), g, dim3(QSV_TPB), 0, sh.stream, sh.amp, sh.tile_ins, sh.tile_rp, sh.tile_lp, sh.d_sblk, sh.d_sres, sh.d_sout, cnt, sh.tile_xor)
+#define LT(RR) hipLaunchKernelGGL((k_locate_tile<RR>), g, dim3(QSV_TPB), 0, sh.stream, sh.amp, sh.tile_ins, sh.tile_rp, sh.tile_lp, sh.d_sblk, sh.d_sres, sh.d_sout, cnt, sh.tile_xor, sh.zmask)
         switch (sh.tile_R) {
           case 0: LT(0); break; case 1: LT(1); break; case 2: LT(2); break; case 3: LT(3); break;
           case 4: LT(4); break; case 5: LT(5); break; default: LT(6); break;
         }
 #undef LT
       } else {
+        CHK(materialize(h, sh));          // (done by block_sums already; k_locate reads amplitudes, not tile sums)
         hipLaunchKernelGGL(k_locate, dim3((unsigned)std::min<uint64_t>(cnt, 65535)), dim3(64), 0, sh.stream,
                            sh.amp, amps_local(h), sh.d_sblk, sh.d_sres, sh.d_sout, cnt);
       }
@@ -217,6 +219,7 @@ extern "C" int qsv_probabilities_cond(qsv_handle* h, const int* qubits, int k, u
   std::vector<double> part(ntab);
   for (int i = 0; i < ntab; ++i) out[i] = 0.0;
   const uint64_t n = amps_local(h);
+  CHK(materialize_all(h));
   for (Shard& s : h->shards) {
     CHK(shard_set(s));
     double* d_out = nullptr;
@@ -255,6 +258,7 @@ extern "C" int qsv_expect_diag(qsv_handle* h, const int* qubits, int k, const do
   const size_t tbytes = (size_t)ntab * sizeof(double);
   const bool lds = k <= 12;                                  // 32 KiB of table in LDS; wider ones through L2
   out[0] = out[1] = 0.0;
+  CHK(materialize_all(h));
   for (Shard& s : h->shards) {
     CHK(shard_set(s));
     double* d_tab = nullptr;
@@ -313,8 +317,27 @@ static int amp_copy(qsv_handle* h, uint64_t start, uint64_t count, double* out, 
     const uint64_t m = std::min(count - done, n - off);
     CHK(shard_set(*sh));
     HIPCHK(hipStreamSynchronize(sh->stream));
-    if (out) HIPCHK(hipMemcpy(out + 2 * done, sh->amp + off, m * sizeof(cplx), hipMemcpyDeviceToHost));
-    else   { HIPCHK(hipMemcpy(sh->amp + off, in + 2 * done, m * sizeof(cplx), hipMemcpyHostToDevice)); sh->sums_valid = false; sh->tile_valid = false; sh->h_tsums_valid = false; }
+    if (out) {
+      HIPCHK(hipMemcpy(out + 2 * done, sh->amp + off, m * sizeof(cplx), hipMemcpyDeviceToHost));
+      // implied zeros: the copy of undefined memory is overwritten by the zeros it stands for.  zmask is constant on
+      // every aligned run of 2^(lowest zmask bit) amplitudes: one memset per run.  A zero qubit on bit 0 makes that one
+      // per amplitude -- a few ns each, the order of the PCIe copy of its 16 bytes, on this debugging read path; cheaper
+      // than writing the zero half of a large shard on the device for a read of a few amplitudes.
+      if (sh->zmask) {
+        const uint64_t run = sh->zmask & (0 - sh->zmask);
+        for (uint64_t a = off; a < off + m;) {
+          const uint64_t e = std::min(off + m, (a | (run - 1)) + 1);
+          if (a & sh->zmask) memset(out + 2 * (done + (a - off)), 0, (e - a) * sizeof(cplx));
+          a = e;
+        }
+      }
+    } else {
+      CHK(materialize(h, *sh));           // a partial write into the zero region must not be lost
+      CHK(shard_set(*sh));
+      HIPCHK(hipStreamSynchronize(sh->stream));
+      HIPCHK(hipMemcpy(sh->amp + off, in + 2 * done, m * sizeof(cplx), hipMemcpyHostToDevice));
+      sh->sums_valid = false; sh->tile_valid = false; sh->h_tsums_valid = false;
+    }
     done += m;
   }
   return QSV_OK;

@@ -192,19 +192,6 @@ static void launch_multi(const qsv_handle* h, const Shard& s, bool init, int mod
 #undef QSV_LM
 }
 
-// zero tracking: write the zeros that were only implied so far
-static int materialize(qsv_handle* h, Shard& s) {
-  if (!s.zmask) return QSV_OK;
-  const uint64_t n = amps_local(h);
-  const uint64_t zm = s.zmask;
-  s.zmask = 0;
-  CHK(shard_set(s));
-  const int nz = __builtin_popcountll(zm);
-  return launch(h, s, QSV_K_INIT, 16.0 * ((double)n - (double)(n >> nz)), [&] {
-    hipLaunchKernelGGL(k_fill_zero, dim3(grid_for(h, s, n, QSV_TPB * 4)), dim3(QSV_TPB), 0, s.stream, s.amp, n, zm);
-  });
-}
-
 // ------------------------------------------------------------------------------------------
 // init + diagonal factors only: k_init_prod (write-only generator, no k_multi machinery)
 // ------------------------------------------------------------------------------------------
@@ -218,14 +205,14 @@ static bool group_is_init_product(const qsv_handle* h, const PendingGroup& g) {
 template <int R>
 static void launch_init_prod(const qsv_handle* h, const Shard& s, uint64_t nthreads, const BitIns& ins, const RegPos& rp, const LanePos& lp,
                              const ProdFactor* f, const ProdCounts& cnt, const cplx* tab, int ntab, uint64_t nonmask,
-                             double initval, double* tsums) {
+                             double initval, double* tsums, uint64_t zskip, unsigned zreg) {
   // non-temporal stores pay on big shards (34 qubits: 6.86 -> 7.11 TB/s; 28 qubits: -1 %; profiles/r02_nt_variants.log)
   if (h->opt_nt > 0 || (h->opt_init_prod_nt < 0 && h->L >= QSV_GEN_NT_MIN_L) || h->opt_init_prod_nt > 0)
     hipLaunchKernelGGL((k_init_prod<R, true>), dim3((unsigned)(nthreads / QSV_TPB)), dim3(QSV_TPB), (size_t)std::max(ntab, 1) * sizeof(cplx),
-                       s.stream, s.amp, nthreads, ins, rp, lp, f, cnt, tab, ntab, nonmask, initval, tsums);
+                       s.stream, s.amp, nthreads, ins, rp, lp, f, cnt, tab, ntab, nonmask, initval, tsums, zskip, zreg);
   else
     hipLaunchKernelGGL((k_init_prod<R, false>), dim3((unsigned)(nthreads / QSV_TPB)), dim3(QSV_TPB), (size_t)std::max(ntab, 1) * sizeof(cplx),
-                       s.stream, s.amp, nthreads, ins, rp, lp, f, cnt, tab, ntab, nonmask, initval, tsums);
+                       s.stream, s.amp, nthreads, ins, rp, lp, f, cnt, tab, ntab, nonmask, initval, tsums, zskip, zreg);
 }
 
 template <int R>
@@ -301,13 +288,19 @@ static int flush_init_product_r(qsv_handle* h, Shard& s, PendingGroup& g, bool f
     s.tile_nblocks = nb;
     s.tile_xor = 0;
   }
-  s.zmask = 0;                                  // every amplitude is written, zeros included
-  h->stats.fused_gates += g.ops.size();
+  // implied zeros: as the program's last pass the generator stores only the amplitudes outside the provably-zero
+  // region (planner.choose_layout puts such a qubit on the top bit: half the shard); otherwise every amplitude is
+  // written, zeros included, so that the passes after it need not know
   const uint64_t nonmask = g.nonmask;
+  const uint64_t zskip = final_pass && h->opt_implied_zeros ? nonmask : 0ull;
+  unsigned zreg = 0;
+  for (int c = 0; c < R; ++c) if ((zskip >> rp.pos[c]) & 1ull) zreg |= 1u << c;
+  s.zmask = zskip;
+  h->stats.fused_gates += g.ops.size();
   const double initval = g.initval;
-  const int r = launch(h, s, QSV_K_INIT_PROD, 16.0 * (double)n, [&] {
+  const int r = launch(h, s, QSV_K_INIT_PROD, 16.0 * (double)(n >> __builtin_popcountll(zskip)), [&] {
     launch_init_prod<R>(h, s, nthreads, ins, rp, lp, reinterpret_cast<const ProdFactor*>(dfac), cnt,
-                        reinterpret_cast<const cplx*>(dtab), ntab, nonmask, initval, tsums);
+                        reinterpret_cast<const cplx*>(dtab), ntab, nonmask, initval, tsums, zskip, zreg);
   });
   s.tile_fresh = tsums != nullptr;
   g = PendingGroup();
