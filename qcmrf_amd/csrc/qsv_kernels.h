@@ -665,106 +665,174 @@ __global__ __launch_bounds__(QSV_TPB) void k_reduce_pairs(const double* __restri
 // the ones nonmask makes zero -- are not stored; the shard's zmask says so.  Such a register bit drops its half of
 // every thread's stores (a uniform branch), a zskip thread bit its threads' stores; a tile whose block bits hit zskip
 // only gets its sum, 0.  Tiles keep their index and their sums stay bit-identical: what is skipped adds exactly +-0.
-// At 34 qubits (zero bit = register bit 3) the half write takes 32.5 ms against 38.5 ms: the per-thread factor
-// arithmetic, no longer hidden behind 16 stores, bounds it.  Two tiles per workgroup (16 stores per thread) measured
-// the same, so they were not kept.
+// Work per tile scales with what changes from tile to tile.  The host splits every table index bit by
+// class for the tile geometry: register bit, lane bit (address bits the 64 lanes of a wave vary in: fixed per lane
+// for the whole kernel) or wave-uniform bit (a bit of the wave index tile * 4 + wave: the wave bits of the tile and
+// every block bit).  The grid is persistent: the workgroups the chip holds at once, each walking the tiles with the
+// grid as its stride, so the tiles in flight stay the contiguous window a one-tile-per-workgroup launch had.  Once
+// per workgroup the tables go to LDS together with every factor's lane part (64 byte offsets per factor); per tile
+// lane k of every
+// wave gathers the wave-uniform part of factor k's index (and of factor k + 64) from the wave index, and a factor
+// then costs one v_readlane, one add, one ds_read_b128 and one complex multiply per thread.  Products are formed
+// in the same order as ever (init value, the nuni factors in list order, register expansion c = 0..R-1, multi
+// factors), so amplitudes and tile sums are bit-identical to the one-tile-per-workgroup generator.
+// ZR >= 0: the implied-zero register bits zreg as a compile-time constant (the top register bit as at 34 qubits: the
+// zero half of the register tile costs nothing); ZR < 0: zreg at run time.
 // ---------------------------------------------------------------------------------------
+#define QSV_PROD_MAXF 128           // factors per launch: >= the ops of one group (group_fits: 64 * QSV_COMBO_WORDS)
+#define QSV_PROD_NOBIT 31           // wave-index bit of an element that is not wave-uniform (the wave index is < 2^31)
 struct ProdFactor {
-  int nlist;                      // table index bit e <- address bit pos[e] (pos[e] < 0: a register bit)
-  int tab;                        // table offset in LDS, complex128 units
-  int pos[QSV_MULTI_MAXLIST];
-  int regw[QSV_MULTI_MAXR];       // table-index weight of register bit c
+  int nlist;                        // table index bit e <- address bit of element e
+  int tab;                          // table offset in LDS, complex128 units
+  int pos[QSV_MULTI_MAXLIST];       // lane element: its address bit; else -1
+  int regw[QSV_MULTI_MAXR];         // table-index weight of register bit c
+  uint32_t wbit[(QSV_MULTI_MAXLIST + 3) / 4];   // byte e: wave-index bit of element e (QSV_PROD_NOBIT: none)
 };
 // factor list order: nuni thread-uniform ones, then nsingle[c] factors on register bit c only
-// (c = 0..R-1), then nmulti factors on several register bits
-struct ProdCounts { int nuni; int nsingle[QSV_MULTI_MAXR]; int nmulti; };
-template <int R, bool NT>
-__global__ __launch_bounds__(QSV_TPB) void k_init_prod(cplx* __restrict__ amp, uint64_t nthreads, BitIns ins, RegPos rp,
+// (c = 0..R-1), then nmulti factors on several register bits; nlmax = the longest list
+struct ProdCounts { int nuni; int nsingle[QSV_MULTI_MAXR]; int nmulti; int nfac; int nlmax; };
+
+// wave-uniform part of one factor's table index: bit e <- bit wbit[e] of the wave index (NE >= the longest list)
+template <int NE>
+__device__ __forceinline__ uint32_t prod_gather_wave(uint32_t wi, const uint32_t (&wb)[(QSV_MULTI_MAXLIST + 3) / 4]) {
+  uint32_t j = 0;
+#pragma unroll
+  for (int e = 0; e < NE; ++e) j |= ((wi >> ((wb[e >> 2] >> (8 * (e & 3))) & 31u)) & 1u) << e;
+  return j;
+}
+__device__ __forceinline__ uint32_t prod_gather_wave(uint32_t wi, const uint32_t (&wb)[(QSV_MULTI_MAXLIST + 3) / 4], int nl) {
+  return nl <= 4 ? prod_gather_wave<4>(wi, wb) : prod_gather_wave<QSV_MULTI_MAXLIST>(wi, wb);   // uniform branch
+}
+
+template <int R, bool NT, int ZR>
+__global__ __launch_bounds__(QSV_TPB) void k_init_prod(cplx* __restrict__ amp, uint64_t ntiles, BitIns ins, RegPos rp,
                                                        LanePos lp, const ProdFactor* __restrict__ fac, ProdCounts cnt,
                                                        const cplx* __restrict__ tables, int ntab, uint64_t nonmask,
                                                        double initval, double* __restrict__ tile_sums,
-                                                       uint64_t zskip, unsigned zreg) {
+                                                       uint64_t zskip, unsigned zreg_arg) {
+  constexpr int NWB = (QSV_MULTI_MAXLIST + 3) / 4;
+  static_assert(NWB == 3, "a factor descriptor holds 12 wave-index bit bytes");
+  const unsigned zreg = ZR >= 0 ? (unsigned)ZR : zreg_arg;
   extern __shared__ double4 lds_raw[];
   cplx* lt = reinterpret_cast<cplx*>(lds_raw);
-  const uint64_t base_blk = tile_base_blk(blockIdx.x, ins, lp);
-  if (base_blk & zskip) {                          // the whole tile is implied zero (uniform: no barrier crossed)
-    if (tile_sums && threadIdx.x == 0) tile_sums[blockIdx.x] = 0.0;
-    return;
-  }
+  const char* ltb = reinterpret_cast<const char*>(lds_raw);
+  // LDS: tables | per factor {wave-index bit of element e (bytes 0..11), table offset | single-register weight << 16}
+  // (bytes) | per factor and lane the lane part of the table index (bytes)
+  uint4* desc = reinterpret_cast<uint4*>(lt + ntab);
+  uint16_t* lane_off = reinterpret_cast<uint16_t*>(desc + cnt.nfac);
+  const int lane = threadIdx.x & 63;
+  const uint32_t wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  // once per workgroup
   for (int i = threadIdx.x; i < ntab; i += QSV_TPB) lt[i] = tables[i];
+  for (int i = threadIdx.x; i < cnt.nfac; i += QSV_TPB) {
+    uint32_t rw = 0;
+    for (int c = 0; c < R; ++c) rw += (uint32_t)fac[i].regw[c];
+    desc[i] = make_uint4(fac[i].wbit[0], fac[i].wbit[1], fac[i].wbit[2], (uint32_t)(fac[i].tab * sizeof(cplx)) | (uint32_t)(rw * sizeof(cplx)) << 16);
+  }
+  for (int i = threadIdx.x; i < cnt.nfac * 64; i += QSV_TPB) {
+    const ProdFactor& pf = fac[i >> 6];
+    const uint32_t lb = tile_base_thr((uint32_t)(i & 63), ins, lp);
+    uint32_t j = 0;
+    for (int e = 0; e < pf.nlist; ++e) if (pf.pos[e] >= 0) j |= ((lb >> pf.pos[e]) & 1u) << e;
+    lane_off[i] = (uint16_t)(j * sizeof(cplx));
+  }
+  const bool two = cnt.nfac > 64;
+  const int d0 = cnt.nfac ? (lane < cnt.nfac ? lane : 0) : -1;          // this lane's factors: lane and lane + 64
+  const int d1 = two ? (lane + 64 < cnt.nfac ? lane + 64 : 0) : -1;
   __syncthreads();
-  const uint64_t gb = (uint64_t)blockIdx.x * QSV_TPB;
-  if (gb + threadIdx.x >= nthreads) return;
   const uint32_t base_thr = tile_base_thr(threadIdx.x, ins, lp);
   const bool store = (base_thr & zskip) == 0;
+  const bool thr_live = (base_thr & nonmask) == 0;
   uint64_t ob[R > 0 ? R : 1];
 #pragma unroll
   for (int c = 0; c < R; ++c) ob[c] = 1ull << rp.pos[c];
-  const uint64_t base = base_blk | base_thr;
-  cplx* __restrict__ pblk = amp + base_blk;
-  // factors without a register bit: one scalar per thread
-  cplx f = make_double2(((base & nonmask) == 0) ? initval : 0.0, 0.0);
-  int k0 = 0;
-  for (int k = 0; k < cnt.nuni; ++k) {
-    const ProdFactor& pf = fac[k];
-    uint32_t jt = 0;
-    for (int e = 0; e < pf.nlist; ++e) jt |= (uint32_t)((base >> pf.pos[e]) & 1ull) << e;
-    f = cmul(f, lt[pf.tab + jt]);
-  }
-  k0 = cnt.nuni;
-  cplx a[1 << R];
-  a[0] = f;
+  // the walk in address space: adding tile_base_blk(gridDim.x) with every inserted bit set to 1 carries across them
+  uint64_t holes = 0;
+  for (int j = 0; j < ins.n; ++j) holes |= 1ull << ins.pos[j];
+  const uint64_t dblk = tile_base_blk(gridDim.x, ins, lp);
+  uint64_t base_blk = tile_base_blk(blockIdx.x, ins, lp);
+  __shared__ double wpart[2][QSV_TPB / 64];
+  int par = 0;
+  for (uint64_t tile = blockIdx.x; tile < ntiles; tile += gridDim.x, base_blk = ((base_blk | holes) + dblk) & ~holes) {
+    if (base_blk & zskip) {                        // the whole tile is implied zero (uniform: no barrier crossed)
+      if (tile_sums && threadIdx.x == 0) tile_sums[tile] = 0.0;
+      continue;
+    }
+    // wave-uniform parts of this tile: lane k holds factor k's (and k + 64's) table offset, in bytes
+    uint32_t jb0 = 0, jb1 = 0, rw0 = 0, rw1 = 0;
+    const uint32_t wi = (uint32_t)tile * (QSV_TPB / 64) + wave;
+    if (d0 >= 0) {
+      const uint4 d = desc[d0];
+      const uint32_t wb[NWB] = {d.x, d.y, d.z};
+      jb0 = (d.w & 0xffffu) + (prod_gather_wave(wi, wb, cnt.nlmax) << 4);
+      rw0 = d.w >> 16;
+    }
+    if (d1 >= 0) {
+      const uint4 d = desc[d1];
+      const uint32_t wb[NWB] = {d.x, d.y, d.z};
+      jb1 = (d.w & 0xffffu) + (prod_gather_wave(wi, wb, cnt.nlmax) << 4);
+      rw1 = d.w >> 16;
+    }
+    auto entry = [&](int k) -> uint32_t {         // byte offset in LDS of this thread's entry of factor k
+      const uint32_t u = (uint32_t)__builtin_amdgcn_readlane((int)(k < 64 ? jb0 : jb1), k & 63);
+      return u + lane_off[k * 64 + lane];
+    };
+    auto ldt = [&](uint32_t o) -> cplx { return *reinterpret_cast<const cplx*>(ltb + o); };
+    cplx* __restrict__ pblk = amp + base_blk;
+    // factors without a register bit: one scalar per thread
+    cplx f = make_double2(((base_blk & nonmask) == 0 && thr_live) ? initval : 0.0, 0.0);
+    for (int k = 0; k < cnt.nuni; ++k) f = cmul(f, ldt(entry(k)));
+    int k0 = cnt.nuni;
+    cplx a[1 << R];
+    a[0] = f;
 #pragma unroll
-  for (int c = 0; c < R; ++c) {
-    // both values of register bit c: product of the factors that see this bit and no other.  Register combinations with
-    // a zreg bit are implied zeros: they are set to 0 and cost no arithmetic (uniform branches)
-    const bool zc = (zreg >> c) & 1u;
-    cplx t0 = make_double2(1.0, 0.0), t1 = make_double2((ob[c] & nonmask) ? 0.0 : 1.0, 0.0);
-    for (int k = k0; k < k0 + cnt.nsingle[c]; ++k) {
+    for (int c = 0; c < R; ++c) {
+      // both values of register bit c: product of the factors that see this bit and no other.  Register combinations
+      // with a zreg bit are implied zeros: they are set to 0 and cost no arithmetic (uniform branches)
+      const bool zc = (zreg >> c) & 1u;
+      cplx t0 = make_double2(1.0, 0.0), t1 = make_double2((ob[c] & nonmask) ? 0.0 : 1.0, 0.0);
+      for (int k = k0; k < k0 + cnt.nsingle[c]; ++k) {
+        const uint32_t o = entry(k);
+        t0 = cmul(t0, ldt(o));
+        if (!zc) t1 = cmul(t1, ldt(o + (uint32_t)__builtin_amdgcn_readlane((int)(k < 64 ? rw0 : rw1), k & 63)));
+      }
+      k0 += cnt.nsingle[c];
+#pragma unroll
+      for (int j = 0; j < (1 << c); ++j) {
+        if (((unsigned)j & zreg) || zc) a[j | (1 << c)] = make_double2(0.0, 0.0);
+        else a[j | (1 << c)] = cmul(a[j], t1);
+        if (!((unsigned)j & zreg)) a[j] = cmul(a[j], t0);
+      }
+    }
+    for (int k = k0; k < k0 + cnt.nmulti; ++k) {
+      const uint32_t o = entry(k);
       const ProdFactor& pf = fac[k];
-      uint32_t jt = 0;
-      for (int e = 0; e < pf.nlist; ++e) if (pf.pos[e] >= 0) jt |= (uint32_t)((base >> pf.pos[e]) & 1ull) << e;
-      t0 = cmul(t0, lt[pf.tab + jt]);
-      if (!zc) t1 = cmul(t1, lt[pf.tab + jt + pf.regw[c]]);
-    }
-    k0 += cnt.nsingle[c];
 #pragma unroll
-    for (int j = 0; j < (1 << c); ++j) {
-      if (((unsigned)j & zreg) || zc) a[j | (1 << c)] = make_double2(0.0, 0.0);
-      else a[j | (1 << c)] = cmul(a[j], t1);
-      if (!((unsigned)j & zreg)) a[j] = cmul(a[j], t0);
+      for (int j = 0; j < (1 << R); ++j) {
+        if ((unsigned)j & zreg) continue;
+        int jr = 0;
+#pragma unroll
+        for (int c = 0; c < R; ++c) if ((j >> c) & 1) jr += pf.regw[c];
+        a[j] = cmul(a[j], ldt(o + (uint32_t)jr * sizeof(cplx)));
+      }
     }
-  }
-  for (int k = k0; k < k0 + cnt.nmulti; ++k) {
-    const ProdFactor& pf = fac[k];
-    uint32_t jt = 0;
-    for (int e = 0; e < pf.nlist; ++e) if (pf.pos[e] >= 0) jt |= (uint32_t)((base >> pf.pos[e]) & 1ull) << e;
-    const cplx* tp = lt + pf.tab + jt;
+    double psum = 0.0;
 #pragma unroll
     for (int j = 0; j < (1 << R); ++j) {
-      if ((unsigned)j & zreg) continue;
-      int jr = 0;
+      if ((unsigned)j & zreg) continue;            // implied zero: a[j] is 0, not stored, adds 0 to the sum
+      uint64_t off = 0;
 #pragma unroll
-      for (int c = 0; c < R; ++c) if ((j >> c) & 1) jr += pf.regw[c];
-      a[j] = cmul(a[j], tp[jr]);
+      for (int c = 0; c < R; ++c) if ((j >> c) & 1) off |= ob[c];
+      if (store) { if (NT) st_nt((pblk + off) + base_thr, a[j]); else (pblk + off)[base_thr] = a[j]; }
+      psum = fma(a[j].x, a[j].x, fma(a[j].y, a[j].y, psum));
     }
-  }
-  double psum = 0.0;
-#pragma unroll
-  for (int j = 0; j < (1 << R); ++j) {
-    if ((unsigned)j & zreg) continue;              // implied zero: a[j] is 0, not stored, adds 0 to the sum
-    uint64_t off = 0;
-#pragma unroll
-    for (int c = 0; c < R; ++c) if ((j >> c) & 1) off |= ob[c];
-    if (store) { if (NT) st_nt((pblk + off) + base_thr, a[j]); else (pblk + off)[base_thr] = a[j]; }
-    psum = fma(a[j].x, a[j].x, fma(a[j].y, a[j].y, psum));
-  }
-  if (tile_sums) {
-    __shared__ double wpart[QSV_TPB / 64];
-    psum = wave_sum(psum);
-    if ((threadIdx.x & 63) == 0) wpart[threadIdx.x >> 6] = psum;
-    __syncthreads();
-    if (threadIdx.x == 0) tile_sums[blockIdx.x] = (wpart[0] + wpart[1]) + (wpart[2] + wpart[3]);
+    if (tile_sums) {                               // two buffers: one barrier per tile orders both uses of one
+      psum = wave_sum(psum);
+      if (lane == 0) wpart[par][wave] = psum;
+      __syncthreads();
+      if (threadIdx.x == 0) tile_sums[tile] = (wpart[par][0] + wpart[par][1]) + (wpart[par][2] + wpart[par][3]);
+      par ^= 1;
+    }
   }
 }
 

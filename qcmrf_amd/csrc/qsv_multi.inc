@@ -202,17 +202,45 @@ static bool group_is_init_product(const qsv_handle* h, const PendingGroup& g) {
 }
 
 #define QSV_GEN_NT_MIN_L 30
+template <int R, bool NT, int ZR>
+static int launch_init_prod_k(const qsv_handle* h, const Shard& s, uint64_t ntiles, const BitIns& ins, const RegPos& rp,
+                              const LanePos& lp, const ProdFactor* f, const ProdCounts& cnt, const cplx* tab, int ntab,
+                              uint64_t nonmask, double initval, double* tsums, uint64_t zskip, unsigned zreg) {
+  // persistent grid: every workgroup the chip holds at once at this kernel's occupancy (option init_prod_grid: fewer)
+  const size_t lds = (size_t)ntab * sizeof(cplx) + (size_t)cnt.nfac * (16 + 64 * sizeof(uint16_t));
+  // (asked once per LDS size: the answer depends on nothing else, and the query is host time on every step)
+  static thread_local std::unordered_map<size_t, int> occupancy;
+  auto it = occupancy.find(lds);
+  if (it == occupancy.end()) {
+    int per_cu = 0;
+    HIPCHK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, reinterpret_cast<const void*>(&k_init_prod<R, NT, ZR>),
+                                                        QSV_TPB, std::max<size_t>(lds, 16)));
+    it = occupancy.emplace(lds, per_cu).first;
+  }
+  const int per_cu = it->second;
+  if (per_cu < 1) return fail(QSV_E_UNSUPPORTED, "k_init_prod does not fit a CU (%zu B of LDS)", lds);
+  uint64_t grid = (uint64_t)per_cu * (uint64_t)s.n_cu;
+  if (h->opt_init_prod_grid > 0) grid = std::min<uint64_t>(grid, (uint64_t)h->opt_init_prod_grid);
+  grid = std::min(grid, ntiles);
+  hipLaunchKernelGGL((k_init_prod<R, NT, ZR>), dim3((unsigned)grid), dim3(QSV_TPB), std::max<size_t>(lds, 16), s.stream,
+                     s.amp, ntiles, ins, rp, lp, f, cnt, tab, ntab, nonmask, initval, tsums, zskip, zreg);
+  return QSV_OK;
+}
 template <int R>
-static void launch_init_prod(const qsv_handle* h, const Shard& s, uint64_t nthreads, const BitIns& ins, const RegPos& rp, const LanePos& lp,
-                             const ProdFactor* f, const ProdCounts& cnt, const cplx* tab, int ntab, uint64_t nonmask,
-                             double initval, double* tsums, uint64_t zskip, unsigned zreg) {
+static int launch_init_prod(const qsv_handle* h, const Shard& s, uint64_t ntiles, const BitIns& ins, const RegPos& rp, const LanePos& lp,
+                            const ProdFactor* f, const ProdCounts& cnt, const cplx* tab, int ntab, uint64_t nonmask,
+                            double initval, double* tsums, uint64_t zskip, unsigned zreg) {
   // non-temporal stores pay on big shards (34 qubits: 6.86 -> 7.11 TB/s; 28 qubits: -1 %; profiles/r02_nt_variants.log)
-  if (h->opt_nt > 0 || (h->opt_init_prod_nt < 0 && h->L >= QSV_GEN_NT_MIN_L) || h->opt_init_prod_nt > 0)
-    hipLaunchKernelGGL((k_init_prod<R, true>), dim3((unsigned)(nthreads / QSV_TPB)), dim3(QSV_TPB), (size_t)std::max(ntab, 1) * sizeof(cplx),
-                       s.stream, s.amp, nthreads, ins, rp, lp, f, cnt, tab, ntab, nonmask, initval, tsums, zskip, zreg);
-  else
-    hipLaunchKernelGGL((k_init_prod<R, false>), dim3((unsigned)(nthreads / QSV_TPB)), dim3(QSV_TPB), (size_t)std::max(ntab, 1) * sizeof(cplx),
-                       s.stream, s.amp, nthreads, ins, rp, lp, f, cnt, tab, ntab, nonmask, initval, tsums, zskip, zreg);
+  const bool nt = h->opt_nt > 0 || (h->opt_init_prod_nt < 0 && h->L >= QSV_GEN_NT_MIN_L) || h->opt_init_prod_nt > 0;
+  // the top register bit as the only implied-zero register bit (the layout at 34 qubits) is a compile-time case; any
+  // other zreg, none included, is read at run time (a compile-time zreg = 0 took 127 registers at R = 4 against 109
+  // and wrote the full state 8 % slower)
+  constexpr int ZTOP = 1 << (R - 1);
+#define QSV_LIP(NT, ZR) return launch_init_prod_k<R, NT, ZR>(h, s, ntiles, ins, rp, lp, f, cnt, tab, ntab, nonmask, initval, tsums, zskip, zreg)
+  if (nt) { if (zreg == ZTOP) QSV_LIP(true, ZTOP); QSV_LIP(true, -1); }
+  if (zreg == ZTOP) QSV_LIP(false, ZTOP);
+  QSV_LIP(false, -1);
+#undef QSV_LIP
 }
 
 template <int R>
@@ -243,29 +271,53 @@ static int flush_init_product_r(qsv_handle* h, Shard& s, PendingGroup& g, bool f
     lp.pos[0] = lp.pos[1] = lp.pos[2] = -1;
   }
   const BitIns ins = make_ins(inspos);
+  // the class of every address bit for this tile geometry (k_init_prod): register bit, lane bit (varies within a
+  // wave), or wave-uniform -- then it is bit t of the wave index tile * 4 + wave, whose bits the tile map places
+  // (tile_base_thr / tile_base_blk) like those of the value (wave index << wsh)
+  uint32_t lanemask = 0;
+  for (uint32_t l = 0; l < 64; ++l) lanemask |= tile_base_thr(l, ins, lp);
+  const int wsh = lp.pos[0] < 0 ? 6 : 3;
+  int wbit_of[64];
+  for (int q = 0; q < 64; ++q) wbit_of[q] = -1;
+  for (int t = 0; t < QSV_PROD_NOBIT && t + wsh < 64; ++t) {
+    const uint64_t a = ins_bits(1ull << (t + wsh), ins);
+    if (a && a < (1ull << h->L)) wbit_of[__builtin_ctzll(a)] = t;
+  }
+  if ((n >> R) / 64 > (1ull << QSV_PROD_NOBIT)) return fail(QSV_E_UNSUPPORTED, "init product: shard too large for 31-bit wave indices");
   std::vector<ProdFactor> uni, multi, single[R];
   std::vector<double> tables;
+  int nlmax = 0;
   for (const LocalOp& lo : g.ops) {
     ProdFactor pf;
     memset(&pf, 0, sizeof pf);
     pf.nlist = (int)lo.list.size();
     pf.tab = (int)(tables.size() / 2);
+    nlmax = std::max(nlmax, pf.nlist);
     int nreg = 0, creg = 0;
+    for (int e = 0; e < QSV_MULTI_MAXLIST; ++e) pf.wbit[e >> 2] |= (uint32_t)QSV_PROD_NOBIT << (8 * (e & 3));
     for (int e = 0; e < pf.nlist; ++e) {
       const int q = lo.list[e];
-      if (q >= b0 && q < b0 + R) { pf.pos[e] = -1; pf.regw[q - b0] = 1 << e; ++nreg; creg = q - b0; }
-      else pf.pos[e] = q;
+      pf.pos[e] = -1;
+      if (q >= b0 && q < b0 + R) { pf.regw[q - b0] = 1 << e; ++nreg; creg = q - b0; }
+      else if (q < 32 && ((lanemask >> q) & 1u)) pf.pos[e] = q;
+      else {
+        if (wbit_of[q] < 0) return fail(QSV_E_UNSUPPORTED, "init product: address bit %d has no class", q);
+        pf.wbit[e >> 2] = (pf.wbit[e >> 2] & ~(0xffu << (8 * (e & 3)))) | ((uint32_t)wbit_of[q] << (8 * (e & 3)));
+      }
     }
     tables.insert(tables.end(), lo.table.begin(), lo.table.end());
     (nreg == 0 ? uni : nreg == 1 ? single[creg] : multi).push_back(pf);
   }
   if (tables.size() / 2 > 2560) return fail(QSV_E_UNSUPPORTED, "init product tables exceed LDS");
+  if (g.ops.size() > QSV_PROD_MAXF) return fail(QSV_E_UNSUPPORTED, "init product of %zu factors (limit %d)", g.ops.size(), QSV_PROD_MAXF);
   ProdCounts cnt;
   memset(&cnt, 0, sizeof cnt);
   cnt.nuni = (int)uni.size();
   for (int c = 0; c < R; ++c) { cnt.nsingle[c] = (int)single[c].size(); uni.insert(uni.end(), single[c].begin(), single[c].end()); }
   cnt.nmulti = (int)multi.size();
   uni.insert(uni.end(), multi.begin(), multi.end());
+  cnt.nfac = (int)uni.size();
+  cnt.nlmax = nlmax;
   void* dfac = nullptr;
   void* dtab = nullptr;
   CHK(arena_put(s, uni.data(), uni.size() * sizeof(ProdFactor), &dfac));
@@ -298,10 +350,12 @@ static int flush_init_product_r(qsv_handle* h, Shard& s, PendingGroup& g, bool f
   s.zmask = zskip;
   h->stats.fused_gates += g.ops.size();
   const double initval = g.initval;
+  int lr = QSV_OK;
   const int r = launch(h, s, QSV_K_INIT_PROD, 16.0 * (double)(n >> __builtin_popcountll(zskip)), [&] {
-    launch_init_prod<R>(h, s, nthreads, ins, rp, lp, reinterpret_cast<const ProdFactor*>(dfac), cnt,
-                        reinterpret_cast<const cplx*>(dtab), ntab, nonmask, initval, tsums, zskip, zreg);
+    lr = launch_init_prod<R>(h, s, nthreads / QSV_TPB, ins, rp, lp, reinterpret_cast<const ProdFactor*>(dfac), cnt,
+                             reinterpret_cast<const cplx*>(dtab), ntab, nonmask, initval, tsums, zskip, zreg);
   });
+  CHK(lr);
   s.tile_fresh = tsums != nullptr;
   g = PendingGroup();
   return r;
