@@ -267,6 +267,7 @@ int qsv_timer_end(qsv_handle* h, double* ms);
  *               single_shortcut [1] a one-op pass runs as its dedicated kernel     trace_passes [0]  one stderr line per pass
  *   generator   init_prod [1]      init x diagonal factors in one write-only pass   init_prod_r [0 = by shard size], init_prod_bit0 [0 = by size]
  *                                  init_prod_grid [0 = every workgroup the chip holds at once; else at most this many]
+ *                                  init_prod_group [-1 = up to 3 group bits; 0 = one tile per group; 1..4 = that many]
  *   memory      nontemporal [-1], multi_nt [-1], init_prod_nt [-1]   non-temporal loads/stores: -1 by shard size, 0 never, 1 always
  *   measurement cache_sums [1], fused_sums [1]   keep / produce per-tile |amp|^2 sums in the last pass of a program
  *   kernels     unroll [4], lowt_shuffle [1], pair_variant [0], kq_mfma [1], blocks_per_cu [65536]

@@ -211,6 +211,7 @@ extern "C" int qsv_set_option(qsv_handle* h, const char* name, int value) {
   else if (!strcmp(name, "multi_nt")) h->opt_multi_nt = value;
   else if (!strcmp(name, "init_prod_nt")) h->opt_init_prod_nt = value;
   else if (!strcmp(name, "init_prod_grid")) { if (value < 0) return fail(QSV_E_BADARG, "init_prod_grid < 0"); h->opt_init_prod_grid = value; }
+  else if (!strcmp(name, "init_prod_group")) { if (value < -1 || value > QSV_PROD_MAXG) return fail(QSV_E_BADARG, "init_prod_group must be -1 (auto) or 0..4"); h->opt_init_prod_group = value; }
   else if (!strcmp(name, "pass_max_ops")) { if (value < 1 || value > 512) return fail(QSV_E_BADARG, "pass_max_ops out of range"); h->opt_pass_max_ops = value; }
   else if (!strcmp(name, "single_shortcut")) h->opt_single_shortcut = value != 0;
   else if (!strcmp(name, "trace_passes")) h->opt_trace_passes = value != 0;

@@ -668,29 +668,40 @@ __global__ __launch_bounds__(QSV_TPB) void k_reduce_pairs(const double* __restri
 // Work per tile scales with what changes from tile to tile.  The host splits every table index bit by
 // class for the tile geometry: register bit, lane bit (address bits the 64 lanes of a wave vary in: fixed per lane
 // for the whole kernel) or wave-uniform bit (a bit of the wave index tile * 4 + wave: the wave bits of the tile and
-// every block bit).  The grid is persistent: the workgroups the chip holds at once, each walking the tiles with the
-// grid as its stride, so the tiles in flight stay the contiguous window a one-tile-per-workgroup launch had.  Once
-// per workgroup the tables go to LDS together with every factor's lane part (64 byte offsets per factor); per tile
-// lane k of every
-// wave gathers the wave-uniform part of factor k's index (and of factor k + 64) from the wave index, and a factor
-// then costs one v_readlane, one add, one ds_read_b128 and one complex multiply per thread.  Products are formed
-// in the same order as ever (init value, the nuni factors in list order, register expansion c = 0..R-1, multi
-// factors), so amplitudes and tile sums are bit-identical to the one-tile-per-workgroup generator.
+// every block bit).  The grid is persistent: the workgroups the chip holds at once, each walking the work with the
+// grid as its stride.  Once per workgroup the tables go to LDS together with every factor's lane part (64 byte
+// offsets per factor) and its group part (below); lane k of every wave gathers the wave-uniform part of factor k's
+// index (and of factor k + 64) from the wave index, and a factor then costs one v_readlane, one add, one
+// ds_read_b128 and one complex multiply per thread.
+// Tile groups: a workgroup takes 2^B tiles at once that differ only in B block bits of the tile index, the group bits
+// (grp, chosen by the host: never a nonmask bit, so a group is all implied zero or none of it).  The host sorts the
+// factors into four classes: outer (no register bit, no group bit), group (group bits, no register bit), register
+// (single: one register bit, or multi: several; no group bit) and mixed (register and group bits).  Once per group
+// each thread forms P0 = init value x the outer factors in list order, and A[j] for the live register combinations:
+// the register expansion c = 0..R-1 from 1, then the multi factors.  Per tile b of the group, s_b = P0 x the group
+// factors at b in list order, and a[j] = s_b x A[j] x the mixed factors in list order.  B = 0 is the one-tile form:
+// A[0] starts from P0 and a[j] = A[j], the product order of the one-tile-per-workgroup generator.  So the order of an
+// amplitude's products depends on its position and the group bits only, never on the grid or the walk; tiles keep
+// their index and their sums their reduction order.  Tile sums: two LDS buffers, one barrier per group.
 // ZR >= 0: the implied-zero register bits zreg as a compile-time constant (the top register bit as at 34 qubits: the
 // zero half of the register tile costs nothing); ZR < 0: zreg at run time.
 // ---------------------------------------------------------------------------------------
 #define QSV_PROD_MAXF 128           // factors per launch: >= the ops of one group (group_fits: 64 * QSV_COMBO_WORDS)
 #define QSV_PROD_NOBIT 31           // wave-index bit of an element that is not wave-uniform (the wave index is < 2^31)
+#define QSV_PROD_MAXG 4             // group bits at most: 16 tiles per group
 struct ProdFactor {
   int nlist;                        // table index bit e <- address bit of element e
   int tab;                          // table offset in LDS, complex128 units
   int pos[QSV_MULTI_MAXLIST];       // lane element: its address bit; else -1
   int regw[QSV_MULTI_MAXR];         // table-index weight of register bit c
+  int grpw[QSV_PROD_MAXG];          // table-index weight of group bit i
   uint32_t wbit[(QSV_MULTI_MAXLIST + 3) / 4];   // byte e: wave-index bit of element e (QSV_PROD_NOBIT: none)
 };
-// factor list order: nuni thread-uniform ones, then nsingle[c] factors on register bit c only
-// (c = 0..R-1), then nmulti factors on several register bits; nlmax = the longest list
-struct ProdCounts { int nuni; int nsingle[QSV_MULTI_MAXR]; int nmulti; int nfac; int nlmax; };
+// factor list order: nouter outer ones, ngrp group ones, then nsingle[c] factors on register bit c only
+// (c = 0..R-1), nmulti on several register bits, nmixed on register and group bits; nlmax = the longest list
+struct ProdCounts { int nouter; int ngrp; int nsingle[QSV_MULTI_MAXR]; int nmulti; int nmixed; int nfac; int nlmax; };
+// the group bits: nb tile-index bits, positions ascending (nb = 0: one tile per group)
+struct ProdGroup { int nb; int tpos[QSV_PROD_MAXG]; };
 
 // wave-uniform part of one factor's table index: bit e <- bit wbit[e] of the wave index (NE >= the longest list)
 template <int NE>
@@ -707,19 +718,22 @@ __device__ __forceinline__ uint32_t prod_gather_wave(uint32_t wi, const uint32_t
 template <int R, bool NT, int ZR>
 __global__ __launch_bounds__(QSV_TPB) void k_init_prod(cplx* __restrict__ amp, uint64_t ntiles, BitIns ins, RegPos rp,
                                                        LanePos lp, const ProdFactor* __restrict__ fac, ProdCounts cnt,
-                                                       const cplx* __restrict__ tables, int ntab, uint64_t nonmask,
-                                                       double initval, double* __restrict__ tile_sums,
+                                                       ProdGroup grp, const cplx* __restrict__ tables, int ntab,
+                                                       uint64_t nonmask, double initval, double* __restrict__ tile_sums,
                                                        uint64_t zskip, unsigned zreg_arg) {
   constexpr int NWB = (QSV_MULTI_MAXLIST + 3) / 4;
   static_assert(NWB == 3, "a factor descriptor holds 12 wave-index bit bytes");
   const unsigned zreg = ZR >= 0 ? (unsigned)ZR : zreg_arg;
+  const int nsub = 1 << grp.nb;                   // tiles per group
   extern __shared__ double4 lds_raw[];
   cplx* lt = reinterpret_cast<cplx*>(lds_raw);
   const char* ltb = reinterpret_cast<const char*>(lds_raw);
   // LDS: tables | per factor {wave-index bit of element e (bytes 0..11), table offset | single-register weight << 16}
-  // (bytes) | per factor and lane the lane part of the table index (bytes)
+  // (bytes) | per factor and lane the lane part of the table index (bytes) | group bits only: per factor and tile of
+  // a group the group part of the table index (bytes)
   uint4* desc = reinterpret_cast<uint4*>(lt + ntab);
   uint16_t* lane_off = reinterpret_cast<uint16_t*>(desc + cnt.nfac);
+  uint16_t* grp_off = lane_off + cnt.nfac * 64;
   const int lane = threadIdx.x & 63;
   const uint32_t wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   // once per workgroup
@@ -736,6 +750,13 @@ __global__ __launch_bounds__(QSV_TPB) void k_init_prod(cplx* __restrict__ amp, u
     for (int e = 0; e < pf.nlist; ++e) if (pf.pos[e] >= 0) j |= ((lb >> pf.pos[e]) & 1u) << e;
     lane_off[i] = (uint16_t)(j * sizeof(cplx));
   }
+  if (grp.nb)
+    for (int i = threadIdx.x; i < cnt.nfac << grp.nb; i += QSV_TPB) {
+      const ProdFactor& pf = fac[i >> grp.nb];
+      uint32_t j = 0;
+      for (int g = 0; g < grp.nb; ++g) if ((i >> g) & 1) j += (uint32_t)pf.grpw[g];
+      grp_off[i] = (uint16_t)(j * sizeof(cplx));
+    }
   const bool two = cnt.nfac > 64;
   const int d0 = cnt.nfac ? (lane < cnt.nfac ? lane : 0) : -1;          // this lane's factors: lane and lane + 64
   const int d1 = two ? (lane + 64 < cnt.nfac ? lane + 64 : 0) : -1;
@@ -746,21 +767,47 @@ __global__ __launch_bounds__(QSV_TPB) void k_init_prod(cplx* __restrict__ amp, u
   uint64_t ob[R > 0 ? R : 1];
 #pragma unroll
   for (int c = 0; c < R; ++c) ob[c] = 1ull << rp.pos[c];
-  // the walk in address space: adding tile_base_blk(gridDim.x) with every inserted bit set to 1 carries across them
-  uint64_t holes = 0;
+  // The walk over groups, in tile index and in address space.  A group's first tile has its group bits 0; adding the
+  // step with every skipped bit set to 1 (inserted address bits, group bits) carries across them.
+  uint64_t gt[QSV_PROD_MAXG], ga[QSV_PROD_MAXG];  // group bit i: its tile-index bit, its block address bit
+  uint64_t tholes = 0, holes = 0;
   for (int j = 0; j < ins.n; ++j) holes |= 1ull << ins.pos[j];
-  const uint64_t dblk = tile_base_blk(gridDim.x, ins, lp);
-  uint64_t base_blk = tile_base_blk(blockIdx.x, ins, lp);
-  __shared__ double wpart[2][QSV_TPB / 64];
+#pragma unroll
+  for (int i = 0; i < QSV_PROD_MAXG; ++i) {
+    gt[i] = i < grp.nb ? 1ull << grp.tpos[i] : 0ull;
+    ga[i] = tile_base_blk(gt[i], ins, lp);
+    tholes |= gt[i];
+    holes |= ga[i];
+  }
+  auto spread = [&](uint64_t x) -> uint64_t {     // group index -> tile index of its first tile
+    for (int i = 0; i < grp.nb; ++i) {
+      const int p = grp.tpos[i];
+      x = ((x >> p) << (p + 1)) | (x & ((1ull << p) - 1ull));
+    }
+    return x;
+  };
+  auto sub = [](const uint64_t (&v)[QSV_PROD_MAXG], uint32_t b) -> uint64_t {   // tile b of a group: its group bits
+    uint64_t o = 0;
+#pragma unroll
+    for (int i = 0; i < QSV_PROD_MAXG; ++i) if ((b >> i) & 1u) o |= v[i];
+    return o;
+  };
+  const uint64_t ngroups = ntiles >> grp.nb;
+  const uint64_t dtile = spread(gridDim.x);
+  const uint64_t dblk = tile_base_blk(dtile, ins, lp);
+  uint64_t tile0 = spread(blockIdx.x);
+  uint64_t base_blk = tile_base_blk(tile0, ins, lp);
+  __shared__ double wpart[2][1 << QSV_PROD_MAXG][QSV_TPB / 64];
   int par = 0;
-  for (uint64_t tile = blockIdx.x; tile < ntiles; tile += gridDim.x, base_blk = ((base_blk | holes) + dblk) & ~holes) {
-    if (base_blk & zskip) {                        // the whole tile is implied zero (uniform: no barrier crossed)
-      if (tile_sums && threadIdx.x == 0) tile_sums[tile] = 0.0;
+  for (uint64_t gi = blockIdx.x; gi < ngroups; gi += gridDim.x, tile0 = ((tile0 | tholes) + dtile) & ~tholes,
+                                                                base_blk = ((base_blk | holes) + dblk) & ~holes) {
+    if (base_blk & zskip) {                        // the whole group is implied zero (uniform: no barrier crossed)
+      if (tile_sums && (int)threadIdx.x < nsub) tile_sums[tile0 | sub(gt, threadIdx.x)] = 0.0;
       continue;
     }
-    // wave-uniform parts of this tile: lane k holds factor k's (and k + 64's) table offset, in bytes
+    // wave-uniform parts of the group's first tile: lane k holds factor k's (and k + 64's) table offset, in bytes
     uint32_t jb0 = 0, jb1 = 0, rw0 = 0, rw1 = 0;
-    const uint32_t wi = (uint32_t)tile * (QSV_TPB / 64) + wave;
+    const uint32_t wi = (uint32_t)tile0 * (QSV_TPB / 64) + wave;
     if (d0 >= 0) {
       const uint4 d = desc[d0];
       const uint32_t wb[NWB] = {d.x, d.y, d.z};
@@ -773,18 +820,19 @@ __global__ __launch_bounds__(QSV_TPB) void k_init_prod(cplx* __restrict__ amp, u
       jb1 = (d.w & 0xffffu) + (prod_gather_wave(wi, wb, cnt.nlmax) << 4);
       rw1 = d.w >> 16;
     }
-    auto entry = [&](int k) -> uint32_t {         // byte offset in LDS of this thread's entry of factor k
-      const uint32_t u = (uint32_t)__builtin_amdgcn_readlane((int)(k < 64 ? jb0 : jb1), k & 63);
+    // byte offset in LDS of this thread's entry of factor k, lane k of j0 (k - 64 of j1) holding its wave-uniform part
+    auto entry = [&](uint32_t j0, uint32_t j1, int k) -> uint32_t {
+      const uint32_t u = (uint32_t)__builtin_amdgcn_readlane((int)(k < 64 ? j0 : j1), k & 63);
       return u + lane_off[k * 64 + lane];
     };
     auto ldt = [&](uint32_t o) -> cplx { return *reinterpret_cast<const cplx*>(ltb + o); };
-    cplx* __restrict__ pblk = amp + base_blk;
-    // factors without a register bit: one scalar per thread
-    cplx f = make_double2(((base_blk & nonmask) == 0 && thr_live) ? initval : 0.0, 0.0);
-    for (int k = 0; k < cnt.nuni; ++k) f = cmul(f, ldt(entry(k)));
-    int k0 = cnt.nuni;
-    cplx a[1 << R];
-    a[0] = f;
+    // once per group: the outer factors, one scalar per thread
+    cplx p0 = make_double2(((base_blk & nonmask) == 0 && thr_live) ? initval : 0.0, 0.0);
+    for (int k = 0; k < cnt.nouter; ++k) p0 = cmul(p0, ldt(entry(jb0, jb1, k)));
+    const int kg = cnt.nouter;                     // the group factors
+    int k0 = kg + cnt.ngrp;
+    cplx A[1 << R];
+    A[0] = grp.nb ? make_double2(1.0, 0.0) : p0;
 #pragma unroll
     for (int c = 0; c < R; ++c) {
       // both values of register bit c: product of the factors that see this bit and no other.  Register combinations
@@ -792,20 +840,20 @@ __global__ __launch_bounds__(QSV_TPB) void k_init_prod(cplx* __restrict__ amp, u
       const bool zc = (zreg >> c) & 1u;
       cplx t0 = make_double2(1.0, 0.0), t1 = make_double2((ob[c] & nonmask) ? 0.0 : 1.0, 0.0);
       for (int k = k0; k < k0 + cnt.nsingle[c]; ++k) {
-        const uint32_t o = entry(k);
+        const uint32_t o = entry(jb0, jb1, k);
         t0 = cmul(t0, ldt(o));
         if (!zc) t1 = cmul(t1, ldt(o + (uint32_t)__builtin_amdgcn_readlane((int)(k < 64 ? rw0 : rw1), k & 63)));
       }
       k0 += cnt.nsingle[c];
 #pragma unroll
       for (int j = 0; j < (1 << c); ++j) {
-        if (((unsigned)j & zreg) || zc) a[j | (1 << c)] = make_double2(0.0, 0.0);
-        else a[j | (1 << c)] = cmul(a[j], t1);
-        if (!((unsigned)j & zreg)) a[j] = cmul(a[j], t0);
+        if (((unsigned)j & zreg) || zc) A[j | (1 << c)] = make_double2(0.0, 0.0);
+        else A[j | (1 << c)] = cmul(A[j], t1);
+        if (!((unsigned)j & zreg)) A[j] = cmul(A[j], t0);
       }
     }
     for (int k = k0; k < k0 + cnt.nmulti; ++k) {
-      const uint32_t o = entry(k);
+      const uint32_t o = entry(jb0, jb1, k);
       const ProdFactor& pf = fac[k];
 #pragma unroll
       for (int j = 0; j < (1 << R); ++j) {
@@ -813,24 +861,56 @@ __global__ __launch_bounds__(QSV_TPB) void k_init_prod(cplx* __restrict__ amp, u
         int jr = 0;
 #pragma unroll
         for (int c = 0; c < R; ++c) if ((j >> c) & 1) jr += pf.regw[c];
-        a[j] = cmul(a[j], ldt(o + (uint32_t)jr * sizeof(cplx)));
+        A[j] = cmul(A[j], ldt(o + (uint32_t)jr * sizeof(cplx)));
       }
     }
-    double psum = 0.0;
+    const int km = k0 + cnt.nmulti;                // the mixed factors
+    for (int b = 0; b < nsub; ++b) {
+      // tile b: the group part of the table offsets of the group and mixed factors
+      uint32_t gb0 = jb0, gb1 = jb1;
+      if (grp.nb) {
+        if (d0 >= 0) gb0 += grp_off[(d0 << grp.nb) + b];
+        if (d1 >= 0) gb1 += grp_off[(d1 << grp.nb) + b];
+      }
+      cplx s = p0;                                 // s_b
+      for (int k = kg; k < kg + cnt.ngrp; ++k) s = cmul(s, ldt(entry(gb0, gb1, k)));
+      cplx* __restrict__ pblk = amp + (base_blk | sub(ga, (uint32_t)b));
+      double psum = 0.0;
+      // the tile's stores; the multiply by s_b only with group bits, the loop over the mixed factors only where there
+      // are any (uniform branches around the whole tile)
+      auto stores = [&](auto grouped, auto mixed) {
 #pragma unroll
-    for (int j = 0; j < (1 << R); ++j) {
-      if ((unsigned)j & zreg) continue;            // implied zero: a[j] is 0, not stored, adds 0 to the sum
-      uint64_t off = 0;
+        for (int j = 0; j < (1 << R); ++j) {
+          if ((unsigned)j & zreg) continue;        // implied zero: not stored, adds 0 to the sum
+          cplx a = decltype(grouped)::value ? cmul(s, A[j]) : A[j];
+          if (decltype(mixed)::value)
+            for (int k = km; k < km + cnt.nmixed; ++k) {
+              const ProdFactor& pf = fac[k];
+              int jr = 0;
 #pragma unroll
-      for (int c = 0; c < R; ++c) if ((j >> c) & 1) off |= ob[c];
-      if (store) { if (NT) st_nt((pblk + off) + base_thr, a[j]); else (pblk + off)[base_thr] = a[j]; }
-      psum = fma(a[j].x, a[j].x, fma(a[j].y, a[j].y, psum));
+              for (int c = 0; c < R; ++c) if ((j >> c) & 1) jr += pf.regw[c];
+              a = cmul(a, ldt(entry(gb0, gb1, k) + (uint32_t)jr * sizeof(cplx)));
+            }
+          uint64_t off = 0;
+#pragma unroll
+          for (int c = 0; c < R; ++c) if ((j >> c) & 1) off |= ob[c];
+          if (store) { if (NT) st_nt((pblk + off) + base_thr, a); else (pblk + off)[base_thr] = a; }
+          psum = fma(a.x, a.x, fma(a.y, a.y, psum));
+        }
+      };
+      if (cnt.nmixed) stores(std::true_type{}, std::true_type{});          // mixed factors exist with group bits only
+      else if (grp.nb) stores(std::true_type{}, std::false_type{});
+      else stores(std::false_type{}, std::false_type{});
+      if (tile_sums) {
+        psum = wave_sum(psum);
+        if (lane == 0) wpart[par][b][wave] = psum;
+      }
     }
-    if (tile_sums) {                               // two buffers: one barrier per tile orders both uses of one
-      psum = wave_sum(psum);
-      if (lane == 0) wpart[par][wave] = psum;
+    if (tile_sums) {                               // two buffers: one barrier per group orders both uses of one
       __syncthreads();
-      if (threadIdx.x == 0) tile_sums[tile] = (wpart[par][0] + wpart[par][1]) + (wpart[par][2] + wpart[par][3]);
+      const int t = threadIdx.x;
+      if (t < nsub)
+        tile_sums[tile0 | sub(gt, (uint32_t)t)] = (wpart[par][t][0] + wpart[par][t][1]) + (wpart[par][t][2] + wpart[par][t][3]);
       par ^= 1;
     }
   }

@@ -204,10 +204,12 @@ static bool group_is_init_product(const qsv_handle* h, const PendingGroup& g) {
 #define QSV_GEN_NT_MIN_L 30
 template <int R, bool NT, int ZR>
 static int launch_init_prod_k(const qsv_handle* h, const Shard& s, uint64_t ntiles, const BitIns& ins, const RegPos& rp,
-                              const LanePos& lp, const ProdFactor* f, const ProdCounts& cnt, const cplx* tab, int ntab,
-                              uint64_t nonmask, double initval, double* tsums, uint64_t zskip, unsigned zreg) {
+                              const LanePos& lp, const ProdFactor* f, const ProdCounts& cnt, const ProdGroup& grp,
+                              const cplx* tab, int ntab, uint64_t nonmask, double initval, double* tsums, uint64_t zskip,
+                              unsigned zreg) {
   // persistent grid: every workgroup the chip holds at once at this kernel's occupancy (option init_prod_grid: fewer)
-  const size_t lds = (size_t)ntab * sizeof(cplx) + (size_t)cnt.nfac * (16 + 64 * sizeof(uint16_t));
+  const size_t lds = (size_t)ntab * sizeof(cplx) + (size_t)cnt.nfac * (16 + 64 * sizeof(uint16_t)) +
+                     (grp.nb ? ((size_t)cnt.nfac << grp.nb) * sizeof(uint16_t) : 0);
   // (asked once per LDS size: the answer depends on nothing else, and the query is host time on every step)
   static thread_local std::unordered_map<size_t, int> occupancy;
   auto it = occupancy.find(lds);
@@ -221,22 +223,22 @@ static int launch_init_prod_k(const qsv_handle* h, const Shard& s, uint64_t ntil
   if (per_cu < 1) return fail(QSV_E_UNSUPPORTED, "k_init_prod does not fit a CU (%zu B of LDS)", lds);
   uint64_t grid = (uint64_t)per_cu * (uint64_t)s.n_cu;
   if (h->opt_init_prod_grid > 0) grid = std::min<uint64_t>(grid, (uint64_t)h->opt_init_prod_grid);
-  grid = std::min(grid, ntiles);
+  grid = std::min(grid, ntiles >> grp.nb);        // one workgroup per group at most
   hipLaunchKernelGGL((k_init_prod<R, NT, ZR>), dim3((unsigned)grid), dim3(QSV_TPB), std::max<size_t>(lds, 16), s.stream,
-                     s.amp, ntiles, ins, rp, lp, f, cnt, tab, ntab, nonmask, initval, tsums, zskip, zreg);
+                     s.amp, ntiles, ins, rp, lp, f, cnt, grp, tab, ntab, nonmask, initval, tsums, zskip, zreg);
   return QSV_OK;
 }
 template <int R>
 static int launch_init_prod(const qsv_handle* h, const Shard& s, uint64_t ntiles, const BitIns& ins, const RegPos& rp, const LanePos& lp,
-                            const ProdFactor* f, const ProdCounts& cnt, const cplx* tab, int ntab, uint64_t nonmask,
-                            double initval, double* tsums, uint64_t zskip, unsigned zreg) {
+                            const ProdFactor* f, const ProdCounts& cnt, const ProdGroup& grp, const cplx* tab, int ntab,
+                            uint64_t nonmask, double initval, double* tsums, uint64_t zskip, unsigned zreg) {
   // non-temporal stores pay on big shards (34 qubits: 6.86 -> 7.11 TB/s; 28 qubits: -1 %; profiles/r02_nt_variants.log)
   const bool nt = h->opt_nt > 0 || (h->opt_init_prod_nt < 0 && h->L >= QSV_GEN_NT_MIN_L) || h->opt_init_prod_nt > 0;
   // the top register bit as the only implied-zero register bit (the layout at 34 qubits) is a compile-time case; any
   // other zreg, none included, is read at run time (a compile-time zreg = 0 took 127 registers at R = 4 against 109
   // and wrote the full state 8 % slower)
   constexpr int ZTOP = 1 << (R - 1);
-#define QSV_LIP(NT, ZR) return launch_init_prod_k<R, NT, ZR>(h, s, ntiles, ins, rp, lp, f, cnt, tab, ntab, nonmask, initval, tsums, zskip, zreg)
+#define QSV_LIP(NT, ZR) return launch_init_prod_k<R, NT, ZR>(h, s, ntiles, ins, rp, lp, f, cnt, grp, tab, ntab, nonmask, initval, tsums, zskip, zreg)
   if (nt) { if (zreg == ZTOP) QSV_LIP(true, ZTOP); QSV_LIP(true, -1); }
   if (zreg == ZTOP) QSV_LIP(false, ZTOP);
   QSV_LIP(false, -1);
@@ -284,7 +286,41 @@ static int flush_init_product_r(qsv_handle* h, Shard& s, PendingGroup& g, bool f
     if (a && a < (1ull << h->L)) wbit_of[__builtin_ctzll(a)] = t;
   }
   if ((n >> R) / 64 > (1ull << QSV_PROD_NOBIT)) return fail(QSV_E_UNSUPPORTED, "init product: shard too large for 31-bit wave indices");
-  std::vector<ProdFactor> uni, multi, single[R];
+  const uint64_t ntiles = (n >> R) / QSV_TPB;
+  // Tile groups (k_init_prod): block bits of the tile index whose 2^B tiles a workgroup takes at once.  Option
+  // init_prod_group: -1 up to 3 of them, 0 none, 1..4 that many where they exist; never more than the tile index has.
+  // Never a nonmask bit: those are the provably-zero qubits, the same with implied zeros on or off, so the choice --
+  // and with it the product order of every amplitude -- is too.  First the bits the fewest factors touch, then bits
+  // that share no factor with a register bit (such a factor costs a multiply per amplitude), then the lowest.  The
+  // choice depends on the tile geometry and the factor list only.
+  ProdGroup grp;
+  memset(&grp, 0, sizeof grp);
+  int gbit_of[64];                                  // address bit -> group bit index, or -1
+  for (int q = 0; q < 64; ++q) gbit_of[q] = -1;
+  {
+    int ntb = 0;
+    while ((1ull << ntb) < ntiles) ++ntb;
+    const int want = std::min(h->opt_init_prod_group < 0 ? 3 : h->opt_init_prod_group, std::min(ntb, QSV_PROD_MAXG));
+    int nfq[64] = {0};
+    bool regq[64] = {false};
+    for (const LocalOp& lo : g.ops) {
+      bool reg = false;
+      for (int q : lo.list) reg |= q >= b0 && q < b0 + R;
+      for (int q : lo.list) { ++nfq[q]; regq[q] |= reg; }
+    }
+    std::vector<int> cand;                          // block bits: wave-index bits 2.. (the tile index)
+    for (int q = 0; q < h->L; ++q)
+      if (wbit_of[q] >= 2 && !((g.nonmask >> q) & 1ull)) cand.push_back(q);
+    std::sort(cand.begin(), cand.end(), [&](int a, int b) {
+      return std::make_tuple(nfq[a], regq[a], a) < std::make_tuple(nfq[b], regq[b], b);
+    });
+    if ((int)cand.size() > want) cand.resize(std::max(want, 0));
+    std::sort(cand.begin(), cand.end());            // the tile map keeps the order of the bits
+    grp.nb = (int)cand.size();
+    for (int i = 0; i < grp.nb; ++i) { grp.tpos[i] = wbit_of[cand[i]] - 2; gbit_of[cand[i]] = i; }
+  }
+  // factor classes: outer, group, register (single / multi), mixed (k_init_prod)
+  std::vector<ProdFactor> outer, grpf, multi, mixed, single[R];
   std::vector<double> tables;
   int nlmax = 0;
   for (const LocalOp& lo : g.ops) {
@@ -293,7 +329,7 @@ static int flush_init_product_r(qsv_handle* h, Shard& s, PendingGroup& g, bool f
     pf.nlist = (int)lo.list.size();
     pf.tab = (int)(tables.size() / 2);
     nlmax = std::max(nlmax, pf.nlist);
-    int nreg = 0, creg = 0;
+    int nreg = 0, creg = 0, ngb = 0;
     for (int e = 0; e < QSV_MULTI_MAXLIST; ++e) pf.wbit[e >> 2] |= (uint32_t)QSV_PROD_NOBIT << (8 * (e & 3));
     for (int e = 0; e < pf.nlist; ++e) {
       const int q = lo.list[e];
@@ -302,20 +338,30 @@ static int flush_init_product_r(qsv_handle* h, Shard& s, PendingGroup& g, bool f
       else if (q < 32 && ((lanemask >> q) & 1u)) pf.pos[e] = q;
       else {
         if (wbit_of[q] < 0) return fail(QSV_E_UNSUPPORTED, "init product: address bit %d has no class", q);
+        // a group bit is 0 in the wave index of a group's first tile, which is where the kernel gathers
         pf.wbit[e >> 2] = (pf.wbit[e >> 2] & ~(0xffu << (8 * (e & 3)))) | ((uint32_t)wbit_of[q] << (8 * (e & 3)));
+        if (gbit_of[q] >= 0) { pf.grpw[gbit_of[q]] = 1 << e; ++ngb; }
       }
     }
     tables.insert(tables.end(), lo.table.begin(), lo.table.end());
-    (nreg == 0 ? uni : nreg == 1 ? single[creg] : multi).push_back(pf);
+    if (nreg == 0) (ngb ? grpf : outer).push_back(pf);
+    else if (ngb) mixed.push_back(pf);
+    else (nreg == 1 ? single[creg] : multi).push_back(pf);
   }
   if (tables.size() / 2 > 2560) return fail(QSV_E_UNSUPPORTED, "init product tables exceed LDS");
   if (g.ops.size() > QSV_PROD_MAXF) return fail(QSV_E_UNSUPPORTED, "init product of %zu factors (limit %d)", g.ops.size(), QSV_PROD_MAXF);
   ProdCounts cnt;
   memset(&cnt, 0, sizeof cnt);
-  cnt.nuni = (int)uni.size();
+  std::vector<ProdFactor> uni;                      // the factor list in kernel order
+  cnt.nouter = (int)outer.size();
+  uni.insert(uni.end(), outer.begin(), outer.end());
+  cnt.ngrp = (int)grpf.size();
+  uni.insert(uni.end(), grpf.begin(), grpf.end());
   for (int c = 0; c < R; ++c) { cnt.nsingle[c] = (int)single[c].size(); uni.insert(uni.end(), single[c].begin(), single[c].end()); }
   cnt.nmulti = (int)multi.size();
   uni.insert(uni.end(), multi.begin(), multi.end());
+  cnt.nmixed = (int)mixed.size();
+  uni.insert(uni.end(), mixed.begin(), mixed.end());
   cnt.nfac = (int)uni.size();
   cnt.nlmax = nlmax;
   void* dfac = nullptr;
@@ -352,7 +398,7 @@ static int flush_init_product_r(qsv_handle* h, Shard& s, PendingGroup& g, bool f
   const double initval = g.initval;
   int lr = QSV_OK;
   const int r = launch(h, s, QSV_K_INIT_PROD, 16.0 * (double)(n >> __builtin_popcountll(zskip)), [&] {
-    lr = launch_init_prod<R>(h, s, nthreads / QSV_TPB, ins, rp, lp, reinterpret_cast<const ProdFactor*>(dfac), cnt,
+    lr = launch_init_prod<R>(h, s, ntiles, ins, rp, lp, reinterpret_cast<const ProdFactor*>(dfac), cnt, grp,
                              reinterpret_cast<const cplx*>(dtab), ntab, nonmask, initval, tsums, zskip, zreg);
   });
   CHK(lr);
