@@ -222,7 +222,10 @@ int qsv_copy_state(qsv_handle* dst, qsv_handle* src);
 
 enum {
   QSV_OP_INIT_ZERO = 0, QSV_OP_INIT_UNIFORM, QSV_OP_1Q, QSV_OP_MCX, QSV_OP_DIAG,
-  QSV_OP_MCPHASE, QSV_OP_MUX, QSV_OP_KQ, QSV_OP_SWAP
+  QSV_OP_MCPHASE, QSV_OP_MUX, QSV_OP_KQ, QSV_OP_SWAP,
+  QSV_OP_PAULI      /* random Pauli on qubits[0..n) (n <= 2), qsv_noisy_sample only: data_off points to the 4^n
+                       CUMULATIVE probabilities; Pauli index p holds for error qubit j the x bit (p >> 2j) & 1 and
+                       the z bit (p >> 2j+1) & 1 -- (x,z) = (0,0) I, (1,0) X, (0,1) Z, (1,1) Y               */
 };
 
 /* scheduling hint from the planner: close the current multi-gate pass before this gate (the
@@ -241,8 +244,26 @@ typedef struct {
   double   angle;                  /* MCPHASE                                              */
 } qsv_op;
 
-/* run a whole program in one call (one ctypes crossing per circuit) */
+/* run a whole program in one call (one ctypes crossing per circuit); QSV_OP_PAULI is refused */
 int qsv_exec(qsv_handle* h, const qsv_op* ops, int n_ops, const double* data, uint64_t n_data);
+
+/* ---- noisy shots: one trajectory per shot ------------------------------------------------ */
+
+#define QSV_NOISY_MAX_QUBITS 13
+
+/* Every shot s runs the program on its own copy of |0...0> (2^W amplitudes in the LDS of one workgroup; W = the
+ * handle's n_qubits <= QSV_NOISY_MAX_QUBITS on a single-shard handle, whose own amplitude vector is not used),
+ * drawing one Pauli per QSV_OP_PAULI record, then one basis state from |amp|^2, and records it as qsv_sample does:
+ * out_bits[s] bit j = the value of qubit meas_qubits[j] (-1: bit j stays 0; NULL: the full basis index), each
+ * measured bit flipped with probability readout[2j + value] (NULL: no readout error).
+ * Kinds: INIT_ZERO, INIT_UNIFORM, 1Q, MCX, DIAG, MCPHASE, PAULI; anything else returns QSV_E_UNSUPPORTED.
+ * Random numbers are Philox-4x32-10 draws keyed by the seed and counted by (shot, stream, draw): shot s of a call
+ * is the same whatever the number of shots or the grid.  Runs on the handle's stream (qsv_timer_* bracket it).
+ * Replaces: simulator.run(T, shots=SHOTS, noise_model=...) of an Aer Pauli noise model. */
+int qsv_noisy_sample(qsv_handle* h, const qsv_op* ops, int n_ops, const double* data, uint64_t n_data,
+                     uint64_t shots, uint64_t seed, const int* meas_qubits, int n_meas,
+                     const double* readout /* n_meas x 2: P(flip | 0), P(flip | 1); NULL = none */,
+                     uint64_t* out_bits);
 
 /* ---- instrumentation ---------------------------------------------------------------- */
 
@@ -273,6 +294,7 @@ int qsv_timer_end(qsv_handle* h, double* ms);
  *   kernels     unroll [4], lowt_shuffle [1], pair_variant [0], kq_mfma [1], blocks_per_cu [65536]
  *               swizzle [1]        one-gate kernels: lane bit 5 of a wave access carries address bit 11 (two 512-byte runs 32 KiB apart);
  *                                  1 from 2^26 amplitudes per shard, 2 from 2^14, 0 never        lane_map_min_l [26]  same for k_multi tiles other than bits 6..10
+ *   noisy       noisy_grid [0]     workgroups of qsv_noisy_sample: 0 = as many as the chip holds at once, else at most this many
  *   other       zero_tracking [0]  skip amplitudes known to be zero (opt-in)       exchange_chunk_log2 [24]  amplitudes per exchange chunk
  *               implied_zeros [1]  the generator as a program's last pass (and qsv_exec's end) leaves the provably-zero part
  *                                  of a shard unwritten; every reader honours that or writes the zeros first (0: write them always) */

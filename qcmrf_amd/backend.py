@@ -19,7 +19,7 @@ import time
 
 import numpy as np
 
-from . import _lib, ingest as _ingest, passes, planner, program
+from . import _lib, ingest as _ingest, noise as _noise, passes, planner, program
 from .comm import SingleProcess
 
 _NAMES = ("qasm_simulator", "aer_simulator", "aer_simulator_statevector", "statevector_simulator",
@@ -112,13 +112,16 @@ class QsvBackend:
                    (default off: in the only rehearsal available -- ranks sharing one GPU -- the extra collective cost more
                    than the reading it saved)
     device      HIP device of this rank when ``comm`` is given
+    noise_model a ``qcmrf_amd.noise.NoiseModel`` (Pauli gate errors, readout errors): every shot is its own trajectory
+                on the device (``qsv_noisy_sample``), W <= 13 qubits and <= 64 classical bits; None or an empty model
+                runs the ideal path
     """
 
     def __init__(self, name="qasm_simulator", **options):
         self._name = name
         self.options = {"fusion": 3, "layout": "auto", "devices": (0,), "comm": None, "device": 0,
                         "profile": False, "engine_options": None, "method": "statevector", "fold_fresh": True,
-                        "gather_counts": "root"}
+                        "gather_counts": "root", "noise_model": None}
         self.options.update(options)
         self._engine = None
         self._engine_key = None
@@ -204,6 +207,18 @@ class QsvBackend:
         if seed_simulator is None:
             seed_simulator = int(np.random.SeedSequence().entropy % (2 ** 63))
         exps = []
+        model = self._noise_of(opts)
+        if model is not None:
+            # host compile of circuit i+1 on a helper thread while the device runs the shots of circuit i
+            from concurrent.futures import ThreadPoolExecutor
+            with ThreadPoolExecutor(max_workers=1) as pool:
+                nxt = pool.submit(self._prepare_noisy, circs[0], model)
+                for i in range(len(circs)):
+                    prepared = nxt.result()
+                    if i + 1 < len(circs):
+                        nxt = pool.submit(self._prepare_noisy, circs[i + 1], model)
+                    exps.append(self._run_noisy(circs[i], int(shots), int(seed_simulator) + i, opts, prepared))
+            return Job(Result(exps, self._name))
         if len(circs) > 1 and opts.get("method", "statevector") == "statevector":
             # a batch (run_experiment.py:52-56 hands over 70 circuits): compile circuit i+1 on a
             # helper thread while the device evolves and samples circuit i (ctypes releases the GIL
@@ -221,6 +236,81 @@ class QsvBackend:
             for i, c in enumerate(circs):
                 exps.append(self._run_one(c, int(shots), int(seed_simulator) + i, opts))
         return Job(Result(exps, self._name))
+
+    @staticmethod
+    def _noise_of(opts):
+        """the noise model a run has to honour, or None (no model, or one without any error: the ideal path)"""
+        model = opts.get("noise_model")
+        if model is None:
+            return None
+        if not isinstance(model, _noise.NoiseModel):
+            raise TypeError("noise_model must be a qcmrf_amd.noise.NoiseModel, not %s" % type(model).__name__)
+        if model.is_ideal():
+            return None
+        if opts.get("method", "statevector") == "trajectory":
+            raise ValueError("method='trajectory' cannot be combined with a noise model (noisy runs are per-shot trajectories "
+                             "of at most %d qubits already)" % _lib.NOISY_MAX_QUBITS)
+        comm = opts["comm"] or SingleProcess()
+        if comm.world > 1:
+            raise ValueError("noisy runs take one process (a process group of %d ranks was given; limit 1)" % comm.world)
+        return model
+
+    @staticmethod
+    def _prepare_noisy(circuit, model):
+        """host half of a noisy run: ingest with the model's Pauli ops (identity layout) + encode"""
+        t0 = time.perf_counter()
+        ing = _ingest.ingest(circuit, noise=model)
+        if ing.num_qubits > _lib.NOISY_MAX_QUBITS:
+            raise ValueError("noisy runs keep one state per shot in on-chip memory: at most %d qubits, the circuit has %d"
+                             % (_lib.NOISY_MAX_QUBITS, ing.num_qubits))
+        if ing.num_clbits > 64:
+            raise ValueError("noisy runs record at most 64 classical bits, the circuit has %d" % ing.num_clbits)
+        rec, data = program.encode(ing.ops)
+        clist = sorted(ing.measure)
+        meas = [-1] * (clist[-1] + 1) if clist else []
+        readout = np.zeros((len(meas), 2))
+        for c in clist:
+            meas[c] = ing.measure[c]
+            readout[c] = ing.readout.get(c, (0.0, 0.0))
+        return ing, rec, data, clist, meas, readout, time.perf_counter() - t0
+
+    def _run_noisy(self, circuit, shots, seed, opts, prepared):
+        """one qsv_noisy_sample call: shots trajectories, sampled and read out on the device"""
+        ing, rec, data, clist, meas, readout, t_compile = prepared
+        t1 = time.perf_counter()
+        t0 = t1 - t_compile
+        counts = {}
+        t2 = t1
+        if clist and shots > 0:
+            eng = self._get_engine(ing.num_qubits, dict(opts, comm=None, devices=tuple(opts["devices"])[:1]))
+            self._apply_engine_options(eng, opts)
+            bits = eng.noisy_sample(rec, data, shots, seed, meas, readout if ing.readout else None)
+            t2 = time.perf_counter()
+            uv, uc = np.unique(bits, return_counts=True)
+            counts = _format_keys(uv, uc, ing.num_clbits, ing.creg_sizes)
+        t3 = time.perf_counter()
+        meta = {"method": "noisy", "n_qubits": ing.num_qubits, "n_source_ops": ing.n_source_ops, "n_device_ops": len(rec),
+                "n_pauli_ops": ing.n_pauli, "readout_errors": len(ing.readout), "time_compile": t1 - t0,
+                "time_evolve": t2 - t1, "time_sample": t3 - t2, "time_taken": t3 - t0, "seed_simulator": seed}
+        self.last_engine = None          # no resident state: every shot had its own
+        self.last_plan = None
+        self._last_comm = None
+        return {"name": getattr(circuit, "name", "circuit"), "shots": shots, "counts": counts, "metadata": meta}
+
+    def _apply_engine_options(self, eng, opts):
+        """engine options are per RUN: whatever an earlier call set on the cached engine and this one does not ask for
+        goes back to the library default first"""
+        want = dict(opts["engine_options"] or {})
+        applied = getattr(eng, "_applied_options", None)
+        if applied is None:
+            applied = eng._applied_options = {}
+        for k in [k for k in applied if k not in want]:
+            if k in _lib.OPTION_DEFAULTS:
+                eng.set_option(k, _lib.OPTION_DEFAULTS[k])
+            del applied[k]
+        for k, v in want.items():
+            eng.set_option(k, v)
+            applied[k] = v
 
     def _prepare(self, circuit, opts):
         """host half of a run: ingest + passes + plan + encode (no device work)"""
@@ -290,20 +380,7 @@ class QsvBackend:
         t0 = t1 - t_compile
 
         eng = self._get_engine(ing.num_qubits, opts)
-        # engine options are per RUN: whatever an earlier call set on the cached engine and this one
-        # does not ask for goes back to the library default first (the plan above was compiled for
-        # exactly this call's options)
-        want = dict(opts["engine_options"] or {})
-        applied = getattr(eng, "_applied_options", None)
-        if applied is None:
-            applied = eng._applied_options = {}
-        for k in [k for k in applied if k not in want]:
-            if k in _lib.OPTION_DEFAULTS:
-                eng.set_option(k, _lib.OPTION_DEFAULTS[k])
-            del applied[k]
-        for k, v in want.items():
-            eng.set_option(k, v)
-            applied[k] = v
+        self._apply_engine_options(eng, opts)      # (the plan above was compiled for exactly this call's options)
         if pl.n_exchanges and not eng._comm_ready:
             # collective: RCCL communicator over all ranks, or peer-mapped shards (ranks sharing a GPU)
             eng.comm_bootstrap(comm, device=opts["device"], transport=opts.get("exchange", "auto"))

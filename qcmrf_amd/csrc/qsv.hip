@@ -3,6 +3,7 @@
 // gfx950 only; no CPU fallback of any kind: without a HIP device every entry point fails.
 #include "qsv_kernels.h"
 #include "qsv_kmulti_inst.h"
+#include "qsv_noise.h"
 QSV_KMULTI_FOR_GENERAL(QSV_KMULTI_DECLARE)
 QSV_KMULTI_FOR_MODE(QSV_KMULTI_DECLARE, 1)
 QSV_KMULTI_FOR_MODE(QSV_KMULTI_DECLARE, 2)
@@ -161,6 +162,8 @@ struct Shard {
   hipEvent_t ev_copied = nullptr; // ... and this shard has been read completely (its own stream waits for that)
   double* d_red = nullptr;       // scratch of the reductions (marginals, expectation partial sums): grown on demand, kept
   size_t red_cap = 0;            // ... in doubles
+  char* d_noisy = nullptr;       // qsv_noisy_sample: compact ops, pool, measured-qubit map and the shots' words; grown on demand, kept
+  size_t noisy_cap = 0;          // ... in bytes
   std::vector<Pending> pending;
   std::vector<hipEvent_t> free_events;
 };
@@ -223,6 +226,7 @@ struct qsv_handle {
   int opt_xframe = 1;                 // uncontrolled X gates inside a pass become an XOR on its store addresses
   int opt_trace_passes = 0;           // 1: one stderr line per k_multi pass (R, mode, ops by update shape) -- a diagnostic
   int opt_pass_budget = 0;            // opt-in cap on the arithmetic of a general pass, percent of one read+write of the shard (0: none)
+  int opt_noisy_grid = 0;             // qsv_noisy_sample: workgroups at most (0: as many as the chip holds at once)
   uint64_t opt_xchunk = 1ull << 24;   // amplitudes per exchange chunk (256 MiB)
 };
 
@@ -400,6 +404,7 @@ extern "C" int qsv_destroy(qsv_handle* h) {
     if (s.d_sblk) { hipFree(s.d_sblk); hipFree(s.d_sres); hipFree(s.d_sout); }
     if (s.d_tsums) hipFree(s.d_tsums);
     if (s.d_red) hipFree(s.d_red);
+    if (s.d_noisy) hipFree(s.d_noisy);
     if (s.ev_copied) hipEventDestroy(s.ev_copied);
     if (s.ev_ready) hipEventDestroy(s.ev_ready);
     if (s.h_tsums) hipHostFree(s.h_tsums);

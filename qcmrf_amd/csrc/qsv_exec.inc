@@ -132,6 +132,8 @@ extern "C" int qsv_exec(qsv_handle* h, const qsv_op* ops, int n_ops, const doubl
         for (Shard& s : h->shards) CHK(materialize(h, s));
         CHK(qsv_swap_layout(h, o.n, o.qubits, o.vals));
         break;
+      case QSV_OP_PAULI:
+        return fail(QSV_E_BADARG, "op %d: QSV_OP_PAULI (a random Pauli) runs in qsv_noisy_sample only, not in qsv_exec", i);
       default:
         return fail(QSV_E_BADARG, "op %d: unknown kind %d", i, o.kind);
     }
@@ -143,6 +145,160 @@ extern "C" int qsv_exec(qsv_handle* h, const qsv_op* ops, int n_ops, const doubl
     s.tile_valid = s.tile_fresh;
     s.tile_fresh = false;
   }
+  return QSV_OK;
+}
+
+// ------------------------------------------------------------------------------------------
+// noisy shots: one trajectory per shot in LDS (kernel: qsv_noise.hip)
+// ------------------------------------------------------------------------------------------
+// The qsv_op records are re-encoded once per call into 32-byte NzOp records and a pool in which equal tables are
+// stored once (a lowered circuit repeats a handful of matrices thousands of times): every trajectory streams the
+// whole list.
+extern "C" int qsv_noisy_sample(qsv_handle* h, const qsv_op* ops, int n_ops, const double* data, uint64_t n_data,
+                                uint64_t shots, uint64_t seed, const int* meas_qubits, int n_meas,
+                                const double* readout, uint64_t* out_bits) {
+  if (!h || n_ops < 0 || (n_ops && !ops) || (shots && !out_bits)) return fail(QSV_E_BADARG, "NULL argument");
+  if (h->multiproc || h->shards.size() != 1) return fail(QSV_E_UNSUPPORTED, "noisy shots need a single-shard handle");
+  if (h->W > QSV_NOISY_MAX_QUBITS)
+    return fail(QSV_E_BADARG, "noisy shots keep one %d-qubit state per trajectory in LDS: at most %d qubits", h->W, QSV_NOISY_MAX_QUBITS);
+  if (meas_qubits && (n_meas < 0 || n_meas > 64)) return fail(QSV_E_BADARG, "n_meas %d out of range", n_meas);
+  if (readout && !meas_qubits) return fail(QSV_E_BADARG, "readout errors need meas_qubits");
+  if (meas_qubits) for (int j = 0; j < n_meas; ++j) if (meas_qubits[j] >= 0) CHK(check_qubit(h, meas_qubits[j], "measured"));
+  if (readout)
+    for (int j = 0; j < 2 * n_meas; ++j)
+      if (!(readout[j] >= 0.0 && readout[j] <= 1.0)) return fail(QSV_E_BADARG, "readout probability %d = %g not in [0, 1]", j, readout[j]);
+  std::vector<NzOp> cops;
+  cops.reserve(n_ops);
+  std::vector<double> pool;
+  std::unordered_map<std::string, uint32_t> seen;
+  auto put = [&](const double* v, size_t cnt) -> uint32_t {       // each table once, at an even offset (16-byte aligned)
+    std::string key(reinterpret_cast<const char*>(v), cnt * sizeof(double));
+    auto it = seen.find(key);
+    if (it != seen.end()) return it->second;
+    const uint32_t off = (uint32_t)pool.size();
+    pool.insert(pool.end(), v, v + cnt);
+    if (pool.size() & 1) pool.push_back(0.0);
+    seen.emplace(std::move(key), off);
+    return off;
+  };
+  for (int i = 0; i < n_ops; ++i) {
+    const qsv_op& o = ops[i];
+    if (o.n < 0 || o.n > QSV_MAX_CTRL) return fail(QSV_E_BADARG, "op %d: n=%d out of range", i, o.n);
+    const double* d = data ? data + o.data_off : nullptr;
+    auto need = [&](uint64_t cnt) -> int {
+      if (!data || o.data_off + cnt > n_data) return fail(QSV_E_BADARG, "op %d: data range [%llu,+%llu) outside pool of %llu", i,
+                                                          (unsigned long long)o.data_off, (unsigned long long)cnt, (unsigned long long)n_data);
+      return QSV_OK;
+    };
+    auto ctrl_mask = [&](NzOp& c) {
+      for (int b = 0; b < o.n; ++b) {
+        c.cmask |= (uint16_t)(1u << o.qubits[b]);
+        if (o.vals[b]) c.cval |= (uint16_t)(1u << o.qubits[b]);
+      }
+    };
+    NzOp c;
+    memset(&c, 0, sizeof c);
+    switch (o.kind) {
+      case QSV_OP_INIT_ZERO:
+      case QSV_OP_INIT_UNIFORM: {
+        const uint64_t mask = o.kind == QSV_OP_INIT_ZERO ? 0ull : o.mask;
+        if (mask >> h->W) return fail(QSV_E_BADARG, "op %d: mask has bits beyond qubit %d", i, h->W - 1);
+        const double val = std::pow(2.0, -0.5 * __builtin_popcountll(mask));
+        c.kind = NZ_INIT;
+        c.cmask = (uint16_t)mask;
+        c.off = put(&val, 1);
+        break;
+      }
+      case QSV_OP_1Q:
+      case QSV_OP_MCX:
+        CHK(check_qubit(h, o.target, "target"));
+        CHK(check_distinct(h, o.n, o.qubits, o.target));
+        c.kind = o.kind == QSV_OP_1Q ? NZ_1Q : NZ_MCX;
+        c.target = (uint16_t)o.target;
+        ctrl_mask(c);
+        if (o.kind == QSV_OP_1Q) { CHK(need(8)); c.off = put(d, 8); }
+        break;
+      case QSV_OP_DIAG:
+        CHK(check_distinct(h, o.n, o.qubits, -1));
+        CHK(need(2ull << o.n));
+        c.kind = NZ_DIAG;
+        c.n = (uint32_t)o.n;
+        for (int b = 0; b < o.n; ++b) c.qlist |= (uint64_t)o.qubits[b] << (4 * b);
+        c.off = put(d, 2ull << o.n);
+        break;
+      case QSV_OP_MCPHASE: {
+        if (o.n < 1) return fail(QSV_E_BADARG, "op %d: a controlled phase needs at least one qubit", i);
+        CHK(check_distinct(h, o.n, o.qubits, -1));
+        const double cs[2] = {std::cos(o.angle), std::sin(o.angle)};
+        c.kind = NZ_MCPHASE;
+        ctrl_mask(c);
+        c.off = put(cs, 2);
+        break;
+      }
+      case QSV_OP_PAULI: {
+        if (o.n < 1 || o.n > 2) return fail(QSV_E_BADARG, "op %d: a Pauli error acts on 1 or 2 qubits, not %d", i, o.n);
+        CHK(check_distinct(h, o.n, o.qubits, -1));
+        const uint64_t np = 1ull << (2 * o.n);
+        CHK(need(np));
+        for (uint64_t p = 0; p < np; ++p)
+          if (!(d[p] >= (p ? d[p - 1] : 0.0) && d[p] <= 1.0))
+            return fail(QSV_E_BADARG, "op %d: cumulative Pauli probabilities must rise from 0 to 1 (entry %llu = %g)", i,
+                        (unsigned long long)p, d[p]);
+        if (d[np - 1] != 1.0) return fail(QSV_E_BADARG, "op %d: cumulative Pauli probabilities end at %.17g, not 1", i, d[np - 1]);
+        c.kind = NZ_PAULI;
+        c.n = (uint32_t)o.n;
+        for (int b = 0; b < o.n; ++b) c.qlist |= (uint64_t)o.qubits[b] << (4 * b);
+        c.off = put(d, np);
+        break;
+      }
+      default:
+        return fail(QSV_E_UNSUPPORTED, "op %d: kind %d is not supported by noisy shots (INIT, 1Q, MCX, DIAG, MCPHASE, PAULI only)", i, o.kind);
+    }
+    cops.push_back(c);
+  }
+  NzMeas meas;
+  meas.n = meas_qubits ? n_meas : -1;
+  meas.readout = -1;
+  if (readout && n_meas > 0) meas.readout = (int)put(readout, 2 * (size_t)n_meas);
+  if (pool.empty()) pool.push_back(0.0);
+  if (pool.size() >= (1ull << 31)) return fail(QSV_E_BADARG, "tables of %zu doubles exceed the noisy op stream's offsets", pool.size());
+  if (shots == 0) return QSV_OK;
+  std::vector<int> pos(64, -1);
+  for (int j = 0; meas_qubits && j < n_meas; ++j) pos[j] = meas_qubits[j];
+  // one device buffer: [ops | pool | pos | out], each part 256-byte aligned
+  auto up = [](size_t b) { return (b + 255) & ~size_t(255); };
+  const size_t b_ops = up(cops.size() * sizeof(NzOp) + 1), b_pool = up(pool.size() * sizeof(double)), b_pos = up(64 * sizeof(int));
+  const size_t bytes = b_ops + b_pool + b_pos + up(shots * sizeof(uint64_t));
+  Shard& s = h->shards[0];
+  CHK(shard_set(s));
+  if (s.noisy_cap < bytes) {
+    if (s.d_noisy) { HIPCHK(hipStreamSynchronize(s.stream)); HIPCHK(hipFree(s.d_noisy)); }
+    s.d_noisy = nullptr;
+    s.noisy_cap = 0;
+    HIPCHK(hipMalloc(&s.d_noisy, bytes));
+    s.noisy_cap = bytes;
+  }
+  char* base = s.d_noisy;
+  NzLaunch l;
+  l.stream = s.stream;
+  l.W = h->W;
+  l.n_cu = s.n_cu;
+  l.max_grid = h->opt_noisy_grid;
+  l.d_ops = reinterpret_cast<const NzOp*>(base);
+  l.n_ops = (int)cops.size();
+  l.d_pool = reinterpret_cast<const double*>(base + b_ops);
+  l.shots = shots;
+  l.seed = seed;
+  meas.pos = reinterpret_cast<const int*>(base + b_ops + b_pool);
+  l.meas = meas;
+  l.d_out = reinterpret_cast<uint64_t*>(base + b_ops + b_pool + b_pos);
+  if (!cops.empty()) HIPCHK(hipMemcpyAsync(base, cops.data(), cops.size() * sizeof(NzOp), hipMemcpyHostToDevice, s.stream));
+  HIPCHK(hipMemcpyAsync(base + b_ops, pool.data(), pool.size() * sizeof(double), hipMemcpyHostToDevice, s.stream));
+  HIPCHK(hipMemcpyAsync(base + b_ops + b_pool, pos.data(), 64 * sizeof(int), hipMemcpyHostToDevice, s.stream));
+  unsigned grid = 0;
+  HIPCHK(qsv_noise_launch(l, &grid));
+  HIPCHK(hipMemcpyAsync(out_bits, l.d_out, shots * sizeof(uint64_t), hipMemcpyDeviceToHost, s.stream));
+  HIPCHK(hipStreamSynchronize(s.stream));
   return QSV_OK;
 }
 
@@ -215,6 +371,7 @@ extern "C" int qsv_set_option(qsv_handle* h, const char* name, int value) {
   else if (!strcmp(name, "pass_max_ops")) { if (value < 1 || value > 512) return fail(QSV_E_BADARG, "pass_max_ops out of range"); h->opt_pass_max_ops = value; }
   else if (!strcmp(name, "single_shortcut")) h->opt_single_shortcut = value != 0;
   else if (!strcmp(name, "trace_passes")) h->opt_trace_passes = value != 0;
+  else if (!strcmp(name, "noisy_grid")) { if (value < 0) return fail(QSV_E_BADARG, "noisy_grid < 0"); h->opt_noisy_grid = value; }
   else if (!strcmp(name, "pass_budget")) { if (value < 0) return fail(QSV_E_BADARG, "pass_budget < 0"); h->opt_pass_budget = value; }
   else if (!strcmp(name, "fold_init_h")) h->opt_fold_init_h = value != 0;
   else if (!strcmp(name, "general_combos")) h->opt_general_combos = value != 0;

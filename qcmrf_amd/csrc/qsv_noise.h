@@ -1,0 +1,50 @@
+// qsv_noise.h -- noisy shots as per-shot trajectories (qsv_noisy_sample): the compact op stream the kernel walks
+// and its launcher.  Shared by qsv_noise.hip (kernel) and qsv.hip (entry point, re-encoding of qsv_op records).
+#pragma once
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#define QSV_NZ_MAXW 13            // 2^13 complex128 = 128 KiB of LDS per trajectory
+#define QSV_NZ_WAVE_MAXW 10       // up to here one wavefront per trajectory (no workgroup barriers)
+
+enum { NZ_INIT = 0, NZ_1Q, NZ_MCX, NZ_DIAG, NZ_MCPHASE, NZ_PAULI };
+
+// One op of the compact stream, 32 bytes: every trajectory reads the whole list, so a record is a quarter of an
+// L2 line instead of the 168 bytes of a qsv_op.  Qubits < 16, so masks are 16 bits.
+struct NzOp {
+  uint16_t kind;       // NZ_*
+  uint16_t target;     // 1Q, MCX
+  uint16_t cmask;      // control qubits (1Q, MCX, MCPHASE: all its qubits); NZ_INIT: the uniform mask
+  uint16_t cval;       // values the control bits must have
+  uint32_t off;        // into the pool (doubles): 1Q 8 = m00 m01 m10 m11; DIAG 2^n complex; MCPHASE (cos, sin);
+                       // INIT the amplitude value; PAULI 4^n cumulative probabilities
+  uint32_t n;          // DIAG, PAULI: number of qubits in qlist
+  uint64_t qlist;      // DIAG, PAULI: qubit b in bits [4b, 4b + 4)
+  uint64_t pad;
+};
+static_assert(sizeof(NzOp) == 32, "NzOp is 32 bytes");
+
+// Philox-4x32-10 streams (counter word 1): every random number is a pure function of (seed, shot, stream, draw)
+enum { NZ_STREAM_PAULI = 0, NZ_STREAM_SAMPLE = 1, NZ_STREAM_READOUT = 2 };
+
+struct NzMeas {
+  int n;                    // measured bits (<= 64); < 0: out = the full basis index
+  int readout;              // pool offset of n x 2 flip probabilities, < 0: none
+  const int* pos;           // device: bit j <- qubit pos[j] (< 0: stays 0), n entries
+};
+
+struct NzLaunch {
+  hipStream_t stream;
+  int W;
+  int n_cu;
+  int max_grid;             // 0: as many workgroups as the chip holds at once
+  const NzOp* d_ops;        // device copies
+  int n_ops;
+  const double* d_pool;
+  uint64_t shots, seed;
+  NzMeas meas;
+  uint64_t* d_out;
+};
+
+// launches the trajectory kernel on l.stream (asynchronous); the workgroup count used goes to *grid
+hipError_t qsv_noise_launch(const NzLaunch& l, unsigned* grid);

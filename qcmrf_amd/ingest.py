@@ -36,6 +36,8 @@ class Ingested:
         self.creg_sizes = None        # [(name, size)] in declaration order, if the circuit has cregs
         self.n_source_ops = 0
         self.flat = None              # basis-gate circuits: what the flat walk already knows about each wire (see _walk_flat)
+        self.readout = {}             # clbit index -> (P(flip | 0), P(flip | 1)) of its measurement (noise models only)
+        self.n_pauli = 0              # "pauli" ops the noise model added
 
 
 def _index_of(circuit, bit, cache):
@@ -439,6 +441,14 @@ def _emit_conjugated_mcx(definition, qmap, out):
     return True
 
 
+def _noise_after(out, name, q):
+    """the Pauli error a noise model attaches to primitive ``name`` on qubits ``q``: one "pauli" op behind the gate"""
+    e = out.noise.quantum_error(name, tuple(q))
+    if e is not None:
+        out.ops.append(ir.Op("pauli", qubits=tuple(q), table=e.probabilities))
+        out.n_pauli += 1
+
+
 def _walk(circuit, qmap, cmap, out, depth):
     if depth > 32:
         raise ValueError("instruction definitions nest deeper than 32 levels")
@@ -464,6 +474,12 @@ def _walk(circuit, qmap, cmap, out, depth):
             out.measure[c[0]] = q[0]
             out._measured.add(q[0])
             out.n_source_ops += 1
+            if out.noise is not None:
+                flips = out.noise.readout_flips(q[0])
+                if flips is not None:
+                    out.readout[c[0]] = flips
+                else:
+                    out.readout.pop(c[0], None)
             if out.keep_measures:                       # trajectory mode needs WHEN it happens
                 out.ops.append(ir.Op("measure", target=q[0], mask=c[0]))
             continue
@@ -482,6 +498,8 @@ def _walk(circuit, qmap, cmap, out, depth):
         if handler is not None:
             handler(out.ops, op, q)
             out.n_source_ops += 1
+            if out.noise is not None:
+                _noise_after(out, name, q)
             continue
         definition = getattr(op, "definition", None)
         if definition is not None:
@@ -511,6 +529,8 @@ def _walk(circuit, qmap, cmap, out, depth):
         if to_matrix is not None and len(q) <= 5:
             out.ops.append(ir.op_kq(q, np.asarray(to_matrix(), dtype=np.complex128)))
             out.n_source_ops += 1
+            if out.noise is not None:
+                _noise_after(out, name, q)
             continue
         raise ValueError("unsupported operation %r on %d qubit(s): not a primitive of this engine and it "
                          "carries no definition" % (name, len(q)))
@@ -736,18 +756,24 @@ def _walk_flat(circuit, out, compact=False):
     return True
 
 
-def ingest(circuit, peephole=False, keep_measures=False, comm=None, compact=False):
+def ingest(circuit, peephole=False, keep_measures=False, comm=None, compact=False, noise=None):
     """peephole=True additionally folds X..X . MCX . X..X definitions (Qiskit's AND with negative
     flags) into one MCX with negated controls while walking -- exact, and 5x fewer ops to fuse.
     comm (a process group of world > 1, every rank calling with the same circuit): the composite top-level blocks are
     read by one rank each and exchanged in ONE all-gather; the result is the same Ingested on every rank.
     compact (basis-gate circuits only): ``ops`` are unlower's gate records (tuples), ``flat["compact"]`` says so; only
-    ``passes.optimise(..., flat=)`` at level 3 understands them."""
+    ``passes.optimise(..., flat=)`` at level 3 understands them.
+    noise (a ``qcmrf_amd.noise.NoiseModel``): the gate-by-gate walk with every composite unrolled to primitives (peephole,
+    compact and comm are ignored); behind each primitive the model names for its qubits comes one "pauli" op, and the readout
+    errors of the measured qubits land in ``readout`` (per classical bit)."""
+    if noise is not None:
+        peephole, compact, comm = False, False, None
     nq = int(circuit.num_qubits)
     nc = int(getattr(circuit, "num_clbits", 0))
     out = Ingested(nq, nc)
     out.peephole = bool(peephole)
     out.keep_measures = bool(keep_measures)
+    out.noise = noise
     out._measured = set()
     out._phase_blocks = []
     out._part = (comm.rank, comm.world) if (comm is not None and comm.world > 1 and peephole and not keep_measures) else None
@@ -774,7 +800,7 @@ def ingest(circuit, peephole=False, keep_measures=False, comm=None, compact=Fals
     cregs = getattr(circuit, "cregs", None)
     if cregs:
         out.creg_sizes = [(getattr(r, "name", "c"), len(r)) for r in cregs]
-    del out._measured
+    del out._measured, out.noise
     return out
 
 

@@ -13,6 +13,8 @@ mcphase  qubits, vals, angle        e^{i angle} where every qubit matches its va
 mux      ctrls, target, mats        uniformly controlled 2x2, mats[j] with j from ctrls (LSB first)
 kq       qubits, mat                dense 2^k x 2^k, index bit b <-> qubits[b]
 swap     a, b                       physical layout swap (planner output only)
+pauli    qubits, table              random Pauli (noise models, trajectory runs only): table[p] is the chance of Pauli
+                                    index p, error qubit j = qubits[j] (x bit p >> 2j & 1, z bit p >> 2j+1 & 1; qcmrf_amd.noise)
 """
 from __future__ import annotations
 
@@ -166,7 +168,7 @@ class Op:
             k = self.kind
             if k in ("u", "x", "mux"):
                 s = tuple(self.ctrls) + (self.target,)
-            elif k in ("diag", "mcphase", "kq"):
+            elif k in ("diag", "mcphase", "kq", "pauli"):
                 s = tuple(self.qubits)
             elif k == "swap":
                 s = tuple(self.a) + tuple(self.b)
@@ -195,6 +197,8 @@ class Op:
             return "mcphase(%s, %.6g)" % (list(self.qubits), self.angle)
         if self.kind == "kq":
             return "kq(%s)" % (list(self.qubits),)
+        if self.kind == "pauli":
+            return "pauli(%s)" % (list(self.qubits),)
         if self.kind == "init":
             return "init(mask=%#x)" % self.mask
         if self.kind == "swap":

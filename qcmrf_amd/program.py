@@ -23,6 +23,14 @@ def encode(ops):
         top += flat.size
         return off
 
+    def put_real(arr):
+        nonlocal top
+        flat = np.ascontiguousarray(arr, dtype=np.float64).ravel()
+        pool.append(flat)
+        off = top
+        top += flat.size
+        return off
+
     def fill(r, qs, vals=None):
         n = len(qs)
         if n > _lib.MAX_CTRL:
@@ -72,10 +80,25 @@ def encode(ops):
         elif k == "swap":
             r["kind"] = _lib.OP_SWAP
             fill(r, op.a, op.b)
+        elif k == "pauli":
+            r["kind"] = _lib.OP_PAULI
+            fill(r, op.qubits)
+            r["data_off"] = put_real(pauli_cumulative(op.table, len(op.qubits)))
         else:
             raise ValueError("cannot encode op kind %r" % k)
     data = np.concatenate(pool) if pool else np.zeros(0, dtype=np.float64)
     return rec, data
+
+
+def pauli_cumulative(probs, n):
+    """QSV_OP_PAULI data: the 4^n cumulative probabilities in Pauli index order (qcmrf_amd.noise), every entry
+    from the last non-zero probability on exactly 1.0 -- a draw u in [0, 1) picks the first p with u < cum[p]"""
+    p = np.asarray(probs, dtype=np.float64).ravel()
+    if n < 1 or n > 2 or p.size != 4 ** n:
+        raise ValueError("a Pauli op on %d qubit(s) needs 4^n = %d probabilities, got %d" % (n, 4 ** n, p.size))
+    cum = np.cumsum(p)
+    cum[int(np.flatnonzero(p > 0)[-1]):] = 1.0
+    return cum
 
 
 def run_stepwise(engine, ops):

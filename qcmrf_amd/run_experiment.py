@@ -1,6 +1,7 @@
 """The reference's experiment driver (/root/reference/run_experiment.py:1-61) on this engine.
 
     python -m qcmrf_amd.run_experiment [--scale 0.5] [--shots 10000] [--reps 10] [--outdir .]
+                                       [--depolarizing P1,P2] [--readout P]
 
 Same steps, same files: seed numpy with 1984, draw theta = -halfnorm.rvs(scale) for the 7
 hard-coded graphs x REPS, dump ``models_<SCALE>.json``, build the 70 ``QCMRF`` circuits, run them
@@ -9,6 +10,11 @@ on the simulator with SHOTS shots, dump ``result_simulation_<SCALE>.json``.  Dif
 for ``len(px.weights(...))``, which is the same number); ``transpile`` is applied only when Qiskit
 is importable (the engine ingests the nested circuits directly); the unreachable IBM-hardware
 tail (run_experiment.py:63-88) is not reproduced.
+
+With ``--depolarizing P1,P2`` and / or ``--readout P`` the run is noisy instead, with an IBM-like Pauli model: depolarizing
+P1 after every ``sx``, ``x`` and ``id``, P2 after every ``cx``, a symmetric readout error P on every qubit.  The circuits are
+then always lowered to {cx,id,rz,sx,x} (by ``qcmrf_amd.transpile`` when Qiskit is absent) so that those gates exist,
+and the counts go to ``result_simulation_noisy_<SCALE>.json``.
 """
 from __future__ import annotations
 
@@ -28,7 +34,11 @@ def main(argv=None):
     ap.add_argument("--reps", type=int, default=10)
     ap.add_argument("--outdir", default=".")
     ap.add_argument("--seed-simulator", type=int, default=None)
+    ap.add_argument("--depolarizing", default=None, metavar="P1,P2",
+                    help="depolarizing parameter after sx/x/id and after cx (noisy run)")
+    ap.add_argument("--readout", type=float, default=None, metavar="P", help="symmetric readout error (noisy run)")
     args = ap.parse_args(argv)
+    model = ibm_like_model(args.depolarizing, args.readout)
 
     np.random.seed(1984)
     from scipy.stats import halfnorm
@@ -48,17 +58,40 @@ def main(argv=None):
     if HAVE_QISKIT:                                   # pragma: no cover - Qiskit absent in this image
         from qiskit import transpile
         CIRCS = transpile(CIRCS, basis_gates=['cx', 'id', 'rz', 'sx', 'x'])
+    elif model is not None:                           # the model names basis gates: they have to be there
+        from .transpile import transpile
+        CIRCS = transpile(CIRCS, basis_gates=['cx', 'id', 'rz', 'sx', 'x'])
 
     simulator = Aer.get_backend('qasm_simulator')
     t0 = time.perf_counter()
-    result = simulator.run(CIRCS, shots=args.shots, seed_simulator=args.seed_simulator).result()
+    extra = {} if model is None else {"noise_model": model}
+    result = simulator.run(CIRCS, shots=args.shots, seed_simulator=args.seed_simulator, **extra).result()
     counts = result.get_counts()
     dt = time.perf_counter() - t0
     print("%d circuits x %d shots: %.3f s in run().result().get_counts() (%.2f ms per circuit)"
           % (len(CIRCS), args.shots, dt, dt / len(CIRCS) * 1e3), file=sys.stderr)
-    with open(os.path.join(args.outdir, "result_simulation_" + str(args.scale) + ".json"), "w") as f:
+    name = "result_simulation_" if model is None else "result_simulation_noisy_"
+    with open(os.path.join(args.outdir, name + str(args.scale) + ".json"), "w") as f:
         f.write(json.dumps(counts, indent=4))
     return counts
+
+
+def ibm_like_model(depolarizing=None, readout=None):
+    """``--depolarizing P1,P2`` / ``--readout P`` -> a NoiseModel (None when neither is given)"""
+    if depolarizing is None and readout is None:
+        return None
+    from .noise import NoiseModel, ReadoutError, depolarizing_error
+    nm = NoiseModel()
+    if depolarizing is not None:
+        parts = [float(x) for x in str(depolarizing).split(",")]
+        if len(parts) != 2:
+            raise ValueError("--depolarizing takes two numbers P1,P2, got %r" % (depolarizing,))
+        nm.add_all_qubit_quantum_error(depolarizing_error(parts[0], 1), ["sx", "x", "id"])
+        nm.add_all_qubit_quantum_error(depolarizing_error(parts[1], 2), ["cx"])
+    if readout is not None:
+        p = float(readout)
+        nm.add_all_qubit_readout_error(ReadoutError([[1.0 - p, p], [p, 1.0 - p]]))
+    return nm
 
 
 if __name__ == "__main__":
