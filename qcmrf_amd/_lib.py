@@ -358,8 +358,8 @@ class Engine:
         if meas_qubits is None:
             qa, qp, nm = None, None, 0
         else:
-            qa, qp = _ia(meas_qubits)
-            nm = len(qa)
+            nm = len(meas_qubits)
+            qa, qp = _ia(meas_qubits if nm else [-1])        # no bits: all-zero words; never NULL, which means the full index
         ra, rp = (None, None) if readout is None else _da(readout)
         if ra is not None and (meas_qubits is None or ra.size != 2 * nm):
             raise ValueError("readout needs 2 probabilities per measured bit (%d), got %d" % (nm, ra.size))

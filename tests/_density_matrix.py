@@ -1,11 +1,15 @@
 """Numpy references for noisy runs (test infrastructure).
 
-Both read the same ``qsv_op`` records (``program.encode``) that ``qsv_noisy_sample`` consumes:
+All read the same ``qsv_op`` records (``program.encode``) that ``qsv_noisy_sample`` consumes:
 
-  density_distribution   exact: rho -> U rho U^dg per gate, rho -> sum_p P(p) P rho P^dg per Pauli op, then the
-                         distribution over the recorded classical words with the readout flips applied
+  density_distribution   exact as a DISTRIBUTION: rho -> U rho U^dg per gate, rho -> sum_p P(p) P rho P^dg per Pauli op,
+                         then the distribution over the recorded classical words with the readout flips applied.
+                         Counts are held to it by a chi^2 test; it says nothing about a single shot.
   NoisyNumpyEngine       oracle.sharded_numpy.NumpyEngine plus ``noisy_sample``: one trajectory per shot, all shots of a
-                         call evolved side by side (the backend's noisy path on a CPU)
+                         call evolved side by side (the backend's noisy path on a CPU).  Distributional only: its random
+                         numbers are numpy's, so its words are not the engine's.  A stand-in backend for host tests.
+  _philox_reference.exact_noisy_sample   exact PER SHOT: the same walk with the engine's documented Philox-4x32-10 draws,
+                         so it predicts every output word of a call (test_gpu_noise_exact.py holds the kernel to it).
 
 Pauli index p on error qubits j: x bit p >> 2j & 1, z bit p >> 2j+1 & 1 (qcmrf_amd.noise).
 """
@@ -181,7 +185,8 @@ def density_distribution(rec, data, n_qubits, meas_qubits, readout=None):
 
 
 class NoisyNumpyEngine(NumpyEngine):
-    """NumpyEngine with the noisy-shots entry point of qcmrf_amd._lib.Engine (numpy random numbers, not Philox)"""
+    """NumpyEngine with the noisy-shots entry point of qcmrf_amd._lib.Engine.  Numpy random numbers, not Philox: right
+    in distribution only, never shot by shot (the per-shot reference is _philox_reference.exact_noisy_sample)"""
 
     calls = 0
 
