@@ -223,9 +223,13 @@ int qsv_copy_state(qsv_handle* dst, qsv_handle* src);
 enum {
   QSV_OP_INIT_ZERO = 0, QSV_OP_INIT_UNIFORM, QSV_OP_1Q, QSV_OP_MCX, QSV_OP_DIAG,
   QSV_OP_MCPHASE, QSV_OP_MUX, QSV_OP_KQ, QSV_OP_SWAP,
-  QSV_OP_PAULI      /* random Pauli on qubits[0..n) (n <= 2), qsv_noisy_sample only: data_off points to the 4^n
+  QSV_OP_PAULI,     /* random Pauli on qubits[0..n) (n <= 2), qsv_noisy_sample only: data_off points to the 4^n
                        CUMULATIVE probabilities; Pauli index p holds for error qubit j the x bit (p >> 2j) & 1 and
                        the z bit (p >> 2j+1) & 1 -- (x,z) = (0,0) I, (1,0) X, (0,1) Z, (1,1) Y               */
+  QSV_OP_KRAUS = 10 /* one-qubit Kraus channel of m = vals[0] operators (1 <= m <= 4) on qubits[0] (n = 1),
+                       qsv_noisy_sample only: data_off points to m x 8 doubles, each K_k row-major with (re, im) pairs as
+                       for QSV_OP_1Q, followed by m x 4 doubles, E_k = K_k^dg K_k as (E00, E11, Re E01, Im E01).  Per
+                       shot one k is drawn with weight <psi|E_k|psi> and K_k applied, the state keeping its mass. */
 };
 
 /* scheduling hint from the planner: close the current multi-gate pass before this gate (the
@@ -244,7 +248,7 @@ typedef struct {
   double   angle;                  /* MCPHASE                                              */
 } qsv_op;
 
-/* run a whole program in one call (one ctypes crossing per circuit); QSV_OP_PAULI is refused */
+/* run a whole program in one call (one ctypes crossing per circuit); QSV_OP_PAULI and QSV_OP_KRAUS are refused */
 int qsv_exec(qsv_handle* h, const qsv_op* ops, int n_ops, const double* data, uint64_t n_data);
 
 /* ---- noisy shots: one trajectory per shot ------------------------------------------------ */
@@ -253,13 +257,19 @@ int qsv_exec(qsv_handle* h, const qsv_op* ops, int n_ops, const double* data, ui
 
 /* Every shot s runs the program on its own copy of |0...0> (2^W amplitudes in the LDS of one workgroup; W = the
  * handle's n_qubits <= QSV_NOISY_MAX_QUBITS on a single-shard handle, whose own amplitude vector is not used),
- * drawing one Pauli per QSV_OP_PAULI record, then one basis state from |amp|^2, and records it as qsv_sample does:
+ * drawing one Pauli per QSV_OP_PAULI record and one Kraus operator per QSV_OP_KRAUS record (below), then one basis
+ * state from |amp|^2, and records it as qsv_sample does:
  * out_bits[s] bit j = the value of qubit meas_qubits[j] (-1: bit j stays 0; NULL: the full basis index), each
  * measured bit flipped with probability readout[2j + value] (NULL: no readout error).
- * Kinds: INIT_ZERO, INIT_UNIFORM, 1Q, MCX, DIAG, MCPHASE, PAULI; anything else returns QSV_E_UNSUPPORTED.
+ * Kinds: INIT_ZERO, INIT_UNIFORM, 1Q, MCX, DIAG, MCPHASE, PAULI, KRAUS; anything else returns QSV_E_UNSUPPORTED.
+ * A KRAUS record on qubit t: u = the next draw of stream 0 (PAULI and KRAUS records share one draw counter, which
+ * advances at every such record, m = 1 included); r00 = sum |a_i0|^2, r11 = sum |a_i1|^2, r10 = sum a_i1 conj(a_i0) over
+ * the pairs (a_i0, a_i1) of t, total = r00 + r11; w_k = E00_k r00 + E11_k r11 + 2 Re(E01_k r10); the first k with w_k > 0
+ * whose inclusive cumulative sum of the positive w exceeds u total is taken (none: the last k with w_k > 0), and every
+ * pair is multiplied by K_k sqrt(total / w_k).
  * Random numbers are Philox-4x32-10 draws keyed by the seed and counted by (shot, stream, draw): shot s of a call
  * is the same whatever the number of shots or the grid.  Runs on the handle's stream (qsv_timer_* bracket it).
- * Replaces: simulator.run(T, shots=SHOTS, noise_model=...) of an Aer Pauli noise model. */
+ * Replaces: simulator.run(T, shots=SHOTS, noise_model=...) of an Aer noise model of Pauli and one-qubit Kraus errors. */
 int qsv_noisy_sample(qsv_handle* h, const qsv_op* ops, int n_ops, const double* data, uint64_t n_data,
                      uint64_t shots, uint64_t seed, const int* meas_qubits, int n_meas,
                      const double* readout /* n_meas x 2: P(flip | 0), P(flip | 1); NULL = none */,

@@ -112,7 +112,7 @@ class QsvBackend:
                    (default off: in the only rehearsal available -- ranks sharing one GPU -- the extra collective cost more
                    than the reading it saved)
     device      HIP device of this rank when ``comm`` is given
-    noise_model a ``qcmrf_amd.noise.NoiseModel`` (Pauli gate errors, readout errors): every shot is its own trajectory
+    noise_model a ``qcmrf_amd.noise.NoiseModel`` (Pauli and one-qubit Kraus gate errors, readout errors): every shot is its own trajectory
                 on the device (``qsv_noisy_sample``), W <= 13 qubits and <= 64 classical bits; None or an empty model
                 runs the ideal path
     """
@@ -257,7 +257,7 @@ class QsvBackend:
 
     @staticmethod
     def _prepare_noisy(circuit, model):
-        """host half of a noisy run: ingest with the model's Pauli ops (identity layout) + encode"""
+        """host half of a noisy run: ingest with the model's Pauli and Kraus ops (identity layout) + encode"""
         t0 = time.perf_counter()
         ing = _ingest.ingest(circuit, noise=model)
         if ing.num_qubits > _lib.NOISY_MAX_QUBITS:
@@ -290,7 +290,7 @@ class QsvBackend:
             counts = _format_keys(uv, uc, ing.num_clbits, ing.creg_sizes)
         t3 = time.perf_counter()
         meta = {"method": "noisy", "n_qubits": ing.num_qubits, "n_source_ops": ing.n_source_ops, "n_device_ops": len(rec),
-                "n_pauli_ops": ing.n_pauli, "readout_errors": len(ing.readout), "time_compile": t1 - t0,
+                "n_pauli_ops": ing.n_pauli, "n_kraus_ops": ing.n_kraus, "readout_errors": len(ing.readout), "time_compile": t1 - t0,
                 "time_evolve": t2 - t1, "time_sample": t3 - t2, "time_taken": t3 - t0, "seed_simulator": seed}
         self.last_engine = None          # no resident state: every shot had its own
         self.last_plan = None

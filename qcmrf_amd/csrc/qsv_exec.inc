@@ -134,6 +134,8 @@ extern "C" int qsv_exec(qsv_handle* h, const qsv_op* ops, int n_ops, const doubl
         break;
       case QSV_OP_PAULI:
         return fail(QSV_E_BADARG, "op %d: QSV_OP_PAULI (a random Pauli) runs in qsv_noisy_sample only, not in qsv_exec", i);
+      case QSV_OP_KRAUS:
+        return fail(QSV_E_BADARG, "op %d: QSV_OP_KRAUS (a Kraus channel) runs in qsv_noisy_sample only, not in qsv_exec", i);
       default:
         return fail(QSV_E_BADARG, "op %d: unknown kind %d", i, o.kind);
     }
@@ -169,6 +171,7 @@ extern "C" int qsv_noisy_sample(qsv_handle* h, const qsv_op* ops, int n_ops, con
       if (!(readout[j] >= 0.0 && readout[j] <= 1.0)) return fail(QSV_E_BADARG, "readout probability %d = %g not in [0, 1]", j, readout[j]);
   std::vector<NzOp> cops;
   cops.reserve(n_ops);
+  bool has_kraus = false;
   std::vector<double> pool;
   std::unordered_map<std::string, uint32_t> seen;
   auto put = [&](const double* v, size_t cnt) -> uint32_t {       // each table once, at an even offset (16-byte aligned)
@@ -251,8 +254,31 @@ extern "C" int qsv_noisy_sample(qsv_handle* h, const qsv_op* ops, int n_ops, con
         c.off = put(d, np);
         break;
       }
+      case QSV_OP_KRAUS: {
+        if (o.n != 1) return fail(QSV_E_BADARG, "op %d: a Kraus channel acts on 1 qubit, not %d", i, o.n);
+        CHK(check_qubit(h, o.qubits[0], "Kraus"));
+        const int m = o.vals[0];
+        if (m < 1 || m > 4) return fail(QSV_E_BADARG, "op %d: a Kraus channel has 1 to 4 operators, not %d", i, m);
+        CHK(need(12ull * m));
+        double e00 = 0.0, e11 = 0.0, e01r = 0.0, e01i = 0.0;
+        for (int j = 0; j < 12 * m; ++j)
+          if (!std::isfinite(d[j])) return fail(QSV_E_BADARG, "op %d: Kraus entry %d is not finite", i, j);
+        for (int k = 0; k < m; ++k) {
+          const double* e = d + 8 * m + 4 * k;
+          if (e[0] < 0.0 || e[1] < 0.0) return fail(QSV_E_BADARG, "op %d: K^dg K of operator %d has a negative diagonal", i, k);
+          e00 += e[0]; e11 += e[1]; e01r += e[2]; e01i += e[3];
+        }
+        if (std::fabs(e00 - 1.0) > 1e-9 || std::fabs(e11 - 1.0) > 1e-9 || std::fabs(e01r) > 1e-9 || std::fabs(e01i) > 1e-9)
+          return fail(QSV_E_BADARG, "op %d: the K^dg K of a Kraus channel must sum to the identity (diagonal %.17g, %.17g)", i, e00, e11);
+        c.kind = NZ_KRAUS;
+        c.target = (uint16_t)o.qubits[0];
+        c.n = (uint32_t)m;
+        c.off = put(d, 12 * (size_t)m);
+        has_kraus = true;
+        break;
+      }
       default:
-        return fail(QSV_E_UNSUPPORTED, "op %d: kind %d is not supported by noisy shots (INIT, 1Q, MCX, DIAG, MCPHASE, PAULI only)", i, o.kind);
+        return fail(QSV_E_UNSUPPORTED, "op %d: kind %d is not supported by noisy shots (INIT, 1Q, MCX, DIAG, MCPHASE, PAULI, KRAUS only)", i, o.kind);
     }
     cops.push_back(c);
   }
@@ -286,6 +312,7 @@ extern "C" int qsv_noisy_sample(qsv_handle* h, const qsv_op* ops, int n_ops, con
   l.max_grid = h->opt_noisy_grid;
   l.d_ops = reinterpret_cast<const NzOp*>(base);
   l.n_ops = (int)cops.size();
+  l.kraus = has_kraus;
   l.d_pool = reinterpret_cast<const double*>(base + b_ops);
   l.shots = shots;
   l.seed = seed;

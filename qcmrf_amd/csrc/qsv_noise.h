@@ -6,19 +6,21 @@
 
 #define QSV_NZ_MAXW 13            // 2^13 complex128 = 128 KiB of LDS per trajectory
 #define QSV_NZ_WAVE_MAXW 10       // up to here one wavefront per trajectory (no workgroup barriers)
+#define QSV_NZ_KRAUS_1PAIR_MAXW 7 // up to here a lane owns at most one pair of a Kraus op's target (2^6 pairs, 64 lanes)
 
-enum { NZ_INIT = 0, NZ_1Q, NZ_MCX, NZ_DIAG, NZ_MCPHASE, NZ_PAULI };
+enum { NZ_INIT = 0, NZ_1Q, NZ_MCX, NZ_DIAG, NZ_MCPHASE, NZ_PAULI, NZ_KRAUS };
 
 // One op of the compact stream, 32 bytes: every trajectory reads the whole list, so a record is a quarter of an
 // L2 line instead of the 168 bytes of a qsv_op.  Qubits < 16, so masks are 16 bits.
 struct NzOp {
   uint16_t kind;       // NZ_*
-  uint16_t target;     // 1Q, MCX
+  uint16_t target;     // 1Q, MCX, KRAUS
   uint16_t cmask;      // control qubits (1Q, MCX, MCPHASE: all its qubits); NZ_INIT: the uniform mask
   uint16_t cval;       // values the control bits must have
   uint32_t off;        // into the pool (doubles): 1Q 8 = m00 m01 m10 m11; DIAG 2^n complex; MCPHASE (cos, sin);
-                       // INIT the amplitude value; PAULI 4^n cumulative probabilities
-  uint32_t n;          // DIAG, PAULI: number of qubits in qlist
+                       // INIT the amplitude value; PAULI 4^n cumulative probabilities; KRAUS n x 8 = the K_k as 1Q, then
+                       // n x 4 = (E00, E11, Re E01, Im E01) of E_k = K_k^dg K_k
+  uint32_t n;          // DIAG, PAULI: number of qubits in qlist; KRAUS: number of operators (1..4)
   uint64_t qlist;      // DIAG, PAULI: qubit b in bits [4b, 4b + 4)
   uint64_t pad;
 };
@@ -40,6 +42,7 @@ struct NzLaunch {
   int max_grid;             // 0: as many workgroups as the chip holds at once
   const NzOp* d_ops;        // device copies
   int n_ops;
+  bool kraus;               // the stream holds an NZ_KRAUS op: a kernel instantiation that knows the kind is launched
   const double* d_pool;
   uint64_t shots, seed;
   NzMeas meas;

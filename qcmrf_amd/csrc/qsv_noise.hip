@@ -9,6 +9,11 @@
 // W <= 10: one wavefront per workgroup (16 KiB of LDS at most), so the "barriers" compile to LDS waits only.
 // W 11..13: 256 threads share one trajectory.
 //
+// A Kraus op (NZ_KRAUS) is the one op whose branch depends on the state: the workgroup reduces the target's reduced density
+// matrix over the trajectory, every lane ending with bitwise the same sums, draws one operator, applies it and rescales
+// the state to the mass it had (kraus_op).  Only k_noisy<TPB, KRAUS > 0> knows the kind; the host launches one of those
+// when the stream holds such an op, so every other program runs k_noisy<TPB, 0>, the kernel as it was without the kind.
+//
 // Random numbers: Philox-4x32-10 keyed by the 64-bit seed, counter (draw, stream, shot lo, shot hi).  Every lane of a
 // workgroup computes the same draw (the branch on the drawn Pauli is uniform), and a shot's draws depend on nothing
 // but (seed, shot, stream, draw): not on the grid, the thread count or how many shots the call has.
@@ -43,7 +48,105 @@ __device__ __forceinline__ cplx pauli_phase(cplx a, uint32_t ny, bool neg) {
   return neg ? make_double2(-r.x, -r.y) : r;
 }
 
-template <int TPB>
+// One Kraus channel on one trajectory (the contract is in include/qsv.h, QSV_OP_KRAUS): r = the reduced density matrix
+// of the target summed over all pairs, w_k = tr(E_k r), the first k whose cumulative weight exceeds u total, then every
+// pair times K_k sqrt(total / w_k).  TPB 64 (W <= 10): a lane owns at most R pairs and keeps them in registers between
+// the reduction and the apply, so the op reads and writes the state once, as a 1Q op does.  R = 8 covers W <= 10 and
+// costs 112 VGPRs (4 waves per SIMD); R = 1 covers W <= 7 with 67, the 7 waves per SIMD of the kernel without the kind,
+// and small trajectories live on having many in flight.  TPB 256 (R unused): 16 pairs per thread would take 128
+// registers, so the pairs are read again; the four waves' sums cross through 128 bytes of static LDS and every thread
+// adds them in one order.  The caller's barrier after the op also fences that scratch.
+template <int TPB, int R>
+__device__ __forceinline__ void kraus_op(cplx* st, const NzOp& o, const double* __restrict__ pool, uint32_t half, uint32_t tid,
+                                         double u) {
+  const uint32_t tb = 1u << o.target, lo = tb - 1u;
+  cplx a0[R], a1[R];
+  double r00 = 0.0, r11 = 0.0, rre = 0.0, rim = 0.0;               // r10 = sum a1 conj(a0) = rre + i rim
+  if constexpr (TPB == 64) {
+#pragma unroll
+    for (int j = 0; j < R; ++j) {
+      const uint32_t p = tid + 64u * (uint32_t)j;
+      a0[j] = a1[j] = make_double2(0.0, 0.0);
+      if (p < half) {
+        const uint32_t i0 = ((p & ~lo) << 1) | (p & lo);
+        a0[j] = st[i0];
+        a1[j] = st[i0 | tb];
+      }
+      r00 += fma(a0[j].x, a0[j].x, a0[j].y * a0[j].y);
+      r11 += fma(a1[j].x, a1[j].x, a1[j].y * a1[j].y);
+      rre += fma(a1[j].x, a0[j].x, a1[j].y * a0[j].y);
+      rim += fma(a1[j].y, a0[j].x, -(a1[j].x * a0[j].y));
+    }
+  } else {
+    for (uint32_t p = tid; p < half; p += TPB) {
+      const uint32_t i0 = ((p & ~lo) << 1) | (p & lo);
+      const cplx b0 = st[i0], b1 = st[i0 | tb];
+      r00 += fma(b0.x, b0.x, b0.y * b0.y);
+      r11 += fma(b1.x, b1.x, b1.y * b1.y);
+      rre += fma(b1.x, b0.x, b1.y * b0.y);
+      rim += fma(b1.y, b0.x, -(b1.x * b0.y));
+    }
+  }
+  r00 = wave_sum(r00);                                             // xor butterfly: the partners of a step add the same two
+  r11 = wave_sum(r11);                                             // numbers, so all 64 lanes end with the same bits
+  rre = wave_sum(rre);
+  rim = wave_sum(rim);
+  if constexpr (TPB > 64) {
+    static_assert(TPB == 256, "four waves cross their sums");
+    __shared__ double part[4][4];
+    if ((tid & 63u) == 0) {
+      double* mine = part[tid >> 6];
+      mine[0] = r00; mine[1] = r11; mine[2] = rre; mine[3] = rim;
+    }
+    __syncthreads();
+    r00 = ((part[0][0] + part[1][0]) + part[2][0]) + part[3][0];
+    r11 = ((part[0][1] + part[1][1]) + part[2][1]) + part[3][1];
+    rre = ((part[0][2] + part[1][2]) + part[2][2]) + part[3][2];
+    rim = ((part[0][3] + part[1][3]) + part[2][3]) + part[3][3];
+  }
+  const double* K = pool + o.off;
+  const double* E = K + 8u * o.n;
+  const double total = r00 + r11, r = u * total;
+  double cum = 0.0, wk = 0.0, wlast = 0.0;
+  int pick = -1, last = -1;
+  for (uint32_t k = 0; k < o.n; ++k) {
+    const double* e = E + 4u * k;
+    const double w = e[0] * r00 + e[1] * r11 + 2.0 * (e[2] * rre - e[3] * rim);
+    if (w > 0.0) {
+      cum += w;
+      last = (int)k;
+      wlast = w;
+      if (pick < 0 && cum > r) { pick = (int)k; wk = w; }
+    }
+  }
+  if (pick < 0) { pick = last; wk = wlast; }                       // rounding at the top boundary: the last k with weight
+  if (pick < 0) return;                                            // a state without mass stays as it is
+  pick = __builtin_amdgcn_readfirstlane(pick);                     // every lane holds the same k: say so, the loads go scalar
+  const double s = sqrt(total / wk);
+  const double* m = K + 8 * pick;
+  const cplx m00 = make_double2(m[0] * s, m[1] * s), m01 = make_double2(m[2] * s, m[3] * s);
+  const cplx m10 = make_double2(m[4] * s, m[5] * s), m11 = make_double2(m[6] * s, m[7] * s);
+  if constexpr (TPB == 64) {
+#pragma unroll
+    for (int j = 0; j < R; ++j) {
+      const uint32_t p = tid + 64u * (uint32_t)j;
+      if (p < half) {
+        const uint32_t i0 = ((p & ~lo) << 1) | (p & lo);
+        st[i0] = cmad(m00, a0[j], cmul(m01, a1[j]));
+        st[i0 | tb] = cmad(m10, a0[j], cmul(m11, a1[j]));
+      }
+    }
+  } else {
+    for (uint32_t p = tid; p < half; p += TPB) {
+      const uint32_t i0 = ((p & ~lo) << 1) | (p & lo);
+      const cplx b0 = st[i0], b1 = st[i0 | tb];
+      st[i0] = cmad(m00, b0, cmul(m01, b1));
+      st[i0 | tb] = cmad(m10, b0, cmul(m11, b1));
+    }
+  }
+}
+
+template <int TPB, int KRAUS>
 __global__ __launch_bounds__(TPB) void k_noisy(const NzOp* __restrict__ ops, int n_ops, const double* __restrict__ pool,
                                                int W, uint64_t shots, uint64_t seed, NzMeas meas,
                                                uint64_t* __restrict__ out) {
@@ -140,6 +243,10 @@ __global__ __launch_bounds__(TPB) void k_noisy(const NzOp* __restrict__ ops, int
           }
           break;
         }
+        case NZ_KRAUS: {
+          if constexpr (KRAUS > 0) kraus_op<TPB, KRAUS>(st, o, pool, half, tid, philox_u01(seed, t, NZ_STREAM_PAULI, draw++));
+          break;
+        }
         default: break;
       }
       __syncthreads();
@@ -201,19 +308,19 @@ __global__ __launch_bounds__(TPB) void k_noisy(const NzOp* __restrict__ ops, int
   }
 }
 
-template <int TPB>
+template <int TPB, int KRAUS>
 static hipError_t launch_noisy(const NzLaunch& l, unsigned* grid) {
   const size_t lds = (size_t)16 << l.W;
-  hipError_t e = hipFuncSetAttribute((const void*)k_noisy<TPB>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+  hipError_t e = hipFuncSetAttribute((const void*)k_noisy<TPB, KRAUS>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
   if (e != hipSuccess) return e;
   int per_cu = 0;
-  e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k_noisy<TPB>, TPB, lds);
+  e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, (k_noisy<TPB, KRAUS>), TPB, lds);
   if (e != hipSuccess) return e;
   uint64_t g = (uint64_t)(per_cu > 0 ? per_cu : 1) * (uint64_t)(l.n_cu > 0 ? l.n_cu : 1);
   if (l.max_grid > 0 && (uint64_t)l.max_grid < g) g = (uint64_t)l.max_grid;
   if (l.shots < g) g = l.shots;
   *grid = (unsigned)g;
-  hipLaunchKernelGGL(k_noisy<TPB>, dim3((unsigned)g), dim3(TPB), lds, l.stream, l.d_ops, l.n_ops, l.d_pool, l.W, l.shots,
+  hipLaunchKernelGGL((k_noisy<TPB, KRAUS>), dim3((unsigned)g), dim3(TPB), lds, l.stream, l.d_ops, l.n_ops, l.d_pool, l.W, l.shots,
                      l.seed, l.meas, l.d_out);
   return hipGetLastError();
 }
@@ -222,5 +329,9 @@ hipError_t qsv_noise_launch(const NzLaunch& l, unsigned* grid) {
   *grid = 0;
   if (l.W < 1 || l.W > QSV_NZ_MAXW) return hipErrorInvalidValue;
   if (l.shots == 0) return hipSuccess;
-  return l.W <= QSV_NZ_WAVE_MAXW ? launch_noisy<64>(l, grid) : launch_noisy<256>(l, grid);
+  if (l.kraus) {
+    if (l.W <= QSV_NZ_KRAUS_1PAIR_MAXW) return launch_noisy<64, 1>(l, grid);
+    return l.W <= QSV_NZ_WAVE_MAXW ? launch_noisy<64, 8>(l, grid) : launch_noisy<256, 1>(l, grid);
+  }
+  return l.W <= QSV_NZ_WAVE_MAXW ? launch_noisy<64, 0>(l, grid) : launch_noisy<256, 0>(l, grid);
 }

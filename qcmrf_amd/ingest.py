@@ -38,6 +38,7 @@ class Ingested:
         self.flat = None              # basis-gate circuits: what the flat walk already knows about each wire (see _walk_flat)
         self.readout = {}             # clbit index -> (P(flip | 0), P(flip | 1)) of its measurement (noise models only)
         self.n_pauli = 0              # "pauli" ops the noise model added
+        self.n_kraus = 0              # "kraus" ops the noise model added
 
 
 def _index_of(circuit, bit, cache):
@@ -442,11 +443,16 @@ def _emit_conjugated_mcx(definition, qmap, out):
 
 
 def _noise_after(out, name, q):
-    """the Pauli error a noise model attaches to primitive ``name`` on qubits ``q``: one "pauli" op behind the gate"""
+    """the error a noise model attaches to primitive ``name`` on qubits ``q``: its terms in order behind the gate, each one
+    "pauli" or one "kraus" op, error qubit j on q[j]"""
     e = out.noise.quantum_error(name, tuple(q))
     if e is not None:
-        out.ops.append(ir.Op("pauli", qubits=tuple(q), table=e.probabilities))
-        out.n_pauli += 1
+        for kind, qs, table in e.terms():
+            out.ops.append(ir.Op(kind, qubits=tuple(q[j] for j in qs), table=table))
+            if kind == "pauli":
+                out.n_pauli += 1
+            else:
+                out.n_kraus += 1
 
 
 def _walk(circuit, qmap, cmap, out, depth):
@@ -764,7 +770,7 @@ def ingest(circuit, peephole=False, keep_measures=False, comm=None, compact=Fals
     compact (basis-gate circuits only): ``ops`` are unlower's gate records (tuples), ``flat["compact"]`` says so; only
     ``passes.optimise(..., flat=)`` at level 3 understands them.
     noise (a ``qcmrf_amd.noise.NoiseModel``): the gate-by-gate walk with every composite unrolled to primitives (peephole,
-    compact and comm are ignored); behind each primitive the model names for its qubits comes one "pauli" op, and the readout
+    compact and comm are ignored); behind each primitive the model names for its qubits come the "pauli" and "kraus" ops of its error, and the readout
     errors of the measured qubits land in ``readout`` (per classical bit)."""
     if noise is not None:
         peephole, compact, comm = False, False, None

@@ -15,6 +15,8 @@ kq       qubits, mat                dense 2^k x 2^k, index bit b <-> qubits[b]
 swap     a, b                       physical layout swap (planner output only)
 pauli    qubits, table              random Pauli (noise models, trajectory runs only): table[p] is the chance of Pauli
                                     index p, error qubit j = qubits[j] (x bit p >> 2j & 1, z bit p >> 2j+1 & 1; qcmrf_amd.noise)
+kraus    qubits, table              one-qubit Kraus channel on qubits[0] (noise models, trajectory runs only): table is the stack
+                                    of its m <= 4 operators, shape (m, 2, 2); one is drawn per shot with weight <psi|K^dg K|psi>
 """
 from __future__ import annotations
 
@@ -168,7 +170,7 @@ class Op:
             k = self.kind
             if k in ("u", "x", "mux"):
                 s = tuple(self.ctrls) + (self.target,)
-            elif k in ("diag", "mcphase", "kq", "pauli"):
+            elif k in ("diag", "mcphase", "kq", "pauli", "kraus"):
                 s = tuple(self.qubits)
             elif k == "swap":
                 s = tuple(self.a) + tuple(self.b)
@@ -199,6 +201,8 @@ class Op:
             return "kq(%s)" % (list(self.qubits),)
         if self.kind == "pauli":
             return "pauli(%s)" % (list(self.qubits),)
+        if self.kind == "kraus":
+            return "kraus(%s, m=%d)" % (list(self.qubits), len(self.table))
         if self.kind == "init":
             return "init(mask=%#x)" % self.mask
         if self.kind == "swap":

@@ -1,4 +1,4 @@
-"""Pauli noise models with the names and conventions of ``qiskit_aer.noise``.
+"""Noise models with the names and conventions of ``qiskit_aer.noise``: Pauli and one-qubit Kraus channels.
 
     from qcmrf_amd.noise import NoiseModel, depolarizing_error, ReadoutError
     nm = NoiseModel()
@@ -7,9 +7,23 @@
     nm.add_all_qubit_readout_error(ReadoutError([[0.98, 0.02], [0.02, 0.98]]))
     counts = backend.run(circuits, shots=10000, noise_model=nm).result().get_counts()
 
-Only Pauli channels (and readout errors) are represented: every ``QuantumError`` is a table of
-4^n probabilities over the n-qubit Pauli group, run on the device as one random Pauli per shot
-(a trajectory, ``qsv_noisy_sample``).
+A Pauli ``QuantumError`` is a table of 4^n probabilities over the n-qubit Pauli group, run on the device as one random
+Pauli per shot (a trajectory, ``qsv_noisy_sample``).  One-qubit Kraus channels are represented too:
+
+    from qcmrf_amd.noise import thermal_relaxation_error, amplitude_damping_error, kraus_error
+    t = thermal_relaxation_error(100e3, 80e3, 35.0)                       # t1, t2, gate time in one unit
+    nm.add_all_qubit_quantum_error(t, ["sx", "x", "id"])
+    nm.add_all_qubit_quantum_error(t.expand(t).compose(depolarizing_error(1e-2, 2)), ["cx"])
+
+``kraus_error``, ``amplitude_damping_error``, ``phase_damping_error``, ``phase_amplitude_damping_error``,
+``thermal_relaxation_error`` and ``reset_error`` have Aer's names and argument order.  A one-qubit non-Pauli error holds
+its 4 x 4 superoperator (column-stacking: S = sum_k conj(K_k) (x) K_k) and, unless Kraus operators were given, gets its
+canonical Kraus set from the eigen-decomposition of its Choi matrix (at most four operators, descending eigenvalues).  A
+two-qubit error is an ordered list of terms, each a Pauli table on both qubits or a one-qubit channel on error qubit j:
+tensor products of one-qubit channels composed with two-qubit Pauli errors, which is how Aer's device models build
+their ``cx`` errors.  A general two-qubit Kraus set is refused.  On the device a channel term is one ``kraus`` op: per
+shot the kernel reduces the branch weights <psi|K_k^dg K_k|psi> over the trajectory's state, draws one k, applies K_k and
+renormalises (``qsv_noise.hip``).
 
 Pauli index order (shared with the encoder ``program.encode`` and the kernel ``qsv_noise.hip``):
 index p of an n-qubit Pauli holds, for error qubit j, an x bit ``p >> 2j & 1`` and a z bit
@@ -46,8 +60,105 @@ def index_to_label(p, n):
     return "".join(_CHAR[((p >> (2 * j)) & 1, (p >> (2 * j + 1)) & 1)] for j in reversed(range(n)))
 
 
+_PAULIS = (np.eye(2, dtype=np.complex128), np.array([[0, 1], [1, 0]], dtype=np.complex128),
+           np.array([[1, 0], [0, -1]], dtype=np.complex128), np.array([[0, -1j], [1j, 0]], dtype=np.complex128))   # I X Z Y
+_EIG_DROP = 1e-14
+
+
+def _superop_of_kraus(ks):
+    """sum_k conj(K_k) (x) K_k: acts on the column-stacked density matrix (rho_ij at index i + 2j)"""
+    return sum(np.kron(k.conj(), k) for k in ks)
+
+
+def _superop_of_pauli(p):
+    return sum(w * np.kron(P.conj(), P) for w, P in zip(p, _PAULIS))
+
+
+def _choi(S):
+    """Choi matrix sum_k vec(K_k) vec(K_k)^dg (vec column-stacking) of a one-qubit superoperator"""
+    return S.reshape(2, 2, 2, 2).transpose(3, 1, 2, 0).reshape(4, 4)
+
+
+def _canonical_kraus(S):
+    """<= 4 Kraus operators from the eigen-decomposition of the Choi matrix, descending eigenvalues; eigenvalues below
+    1e-14 are dropped; each operator's phase is fixed by making its largest entry real and positive"""
+    lam, vec = np.linalg.eigh(_choi(S))
+    out = []
+    for i in np.argsort(-lam, kind="stable"):
+        if lam[i] < _EIG_DROP:
+            continue
+        k = np.sqrt(lam[i]) * vec[:, i].reshape(2, 2).T
+        big = k.ravel()[np.argmax(np.abs(k.ravel()))]
+        out.append(k * (abs(big) / big))
+    return out
+
+
+def _check_cptp(S, what):
+    lam = np.linalg.eigvalsh(_choi(S))
+    if not np.all(np.isfinite(S)) or lam.min() < -1e-10:
+        raise ValueError("%s is not completely positive (Choi eigenvalue %.3g)" % (what, lam.min()))
+    tp = S[0] + S[3]                                           # trace of the output as a functional of the input
+    if np.abs(tp - np.array([1, 0, 0, 1])).max() > 1e-10:
+        raise ValueError("%s does not preserve the trace" % what)
+
+
+def _pauli_table_of(S):
+    """the four probabilities if the superoperator is a Pauli channel, else None"""
+    C = _choi(S)
+    p = np.array([np.real(np.vdot(P.T.ravel(), C @ P.T.ravel())) / 4.0 for P in _PAULIS])
+    if np.abs(S - _superop_of_pauli(p)).max() > _TOL or (p < -_TOL).any():
+        return None
+    p = np.clip(p, 0.0, None)
+    return p / p.sum()
+
+
+class _Chan:
+    """a one-qubit channel: its superoperator and, when they were given, its Kraus operators"""
+    __slots__ = ("S", "given")
+
+    def __init__(self, S, given=None):
+        self.S = S
+        self.given = given
+
+    def kraus(self):
+        return list(self.given) if self.given is not None else _canonical_kraus(self.S)
+
+
+def _merge(terms):
+    """ordered terms with adjacent terms of one shape on the same qubits merged (one-qubit channels on different qubits
+    commute, so a channel also merges with the last channel on its qubit across channels on the other one)"""
+    out = []
+    for kind, qs, x in terms:
+        if kind == "pauli":
+            if out and out[-1][0] == "pauli":
+                out[-1] = ("pauli", qs, _convolve(out[-1][2], x))
+            else:
+                out.append((kind, qs, x))
+            continue
+        k = len(out) - 1
+        while k >= 0 and out[k][0] == "chan" and out[k][1] != qs:
+            k -= 1
+        if k >= 0 and out[k][0] == "chan":
+            out[k] = ("chan", qs, _Chan(x.S @ out[k][2].S))
+        else:
+            out.append((kind, qs, x))
+    return out
+
+
+def _convolve(p, q):
+    """Pauli table q after Pauli table p: the convolution over the Pauli group (phases dropped)"""
+    idx = np.arange(p.size)
+    out = np.zeros(p.size)
+    for b, w in enumerate(q):
+        if w:
+            out[idx ^ b] += p * w
+    return out / out.sum()
+
+
 class QuantumError:
-    """An n-qubit Pauli channel: ``probabilities[p]`` is the chance of Pauli index p."""
+    """An n-qubit error (n = 1 or 2).  ``QuantumError(probabilities, n)`` is a Pauli channel: ``probabilities[p]`` is the
+    chance of Pauli index p.  The constructors below and ``compose`` / ``tensor`` also give one-qubit Kraus channels and
+    two-qubit products of them (module docstring)."""
 
     def __init__(self, probabilities, num_qubits):
         n = int(num_qubits)
@@ -64,60 +175,232 @@ class QuantumError:
         p.setflags(write=False)
         self._p = p
         self._n = n
+        self._chain = None            # non-Pauli errors: ordered ("pauli", (0, 1), table) / ("chan", (j,), _Chan) terms
+        self._emit = None
+
+    @classmethod
+    def _from_terms(cls, terms, n):
+        """an error from ordered terms; one that is a single Pauli table becomes a plain Pauli error"""
+        terms = _merge(terms)
+        if len(terms) == 1 and terms[0][0] == "pauli":
+            return cls(terms[0][2], n)
+        e = cls.__new__(cls)
+        e._p, e._n, e._chain, e._emit = None, n, terms, None
+        return e
+
+    def _terms(self):
+        return [("pauli", tuple(range(self._n)), self._p)] if self._chain is None else list(self._chain)
+
+    def _chan(self):
+        """this one-qubit error as a _Chan (Pauli tables are lifted)"""
+        if self._n != 1:
+            raise ValueError("a two-qubit error has no one-qubit superoperator")
+        return _Chan(_superop_of_pauli(self._p)) if self._chain is None else self._chain[0][2]
 
     @property
     def num_qubits(self):
         return self._n
 
+    def is_pauli(self):
+        return self._chain is None
+
     @property
     def probabilities(self):
-        """4^n probabilities in Pauli index order (read-only array)"""
+        """4^n probabilities in Pauli index order (read-only array); Pauli errors only"""
+        if self._p is None:
+            raise ValueError("this error is not a Pauli channel: it has terms() and, on one qubit, kraus()")
         return self._p
 
     def is_ideal(self):
-        return bool(self._p[0] >= 1.0 - _TOL)
+        if self._chain is None:
+            return bool(self._p[0] >= 1.0 - _TOL)
+        return all(np.abs(x.S - np.eye(4)).max() <= _TOL if k == "chan" else x[0] >= 1.0 - _TOL for k, _, x in self._chain)
 
     def to_dict(self):
         """{Qiskit label: probability} for the Paulis with non-zero probability"""
-        return {index_to_label(i, self._n): float(v) for i, v in enumerate(self._p) if v > 0}
+        return {index_to_label(i, self._n): float(v) for i, v in enumerate(self.probabilities) if v > 0}
+
+    def kraus(self):
+        """the Kraus operators of a one-qubit error: as given to ``kraus_error``, else canonical (Pauli errors:
+        sqrt(p) P for every Pauli with p > 0)"""
+        if self._n != 1:
+            raise ValueError("kraus() is for one-qubit errors; a two-qubit error has terms()")
+        if self._chain is None:
+            return [np.sqrt(w) * P for w, P in zip(self._p, _PAULIS) if w > 0]
+        return [k.copy() for k in self._chain[0][2].kraus()]
+
+    def superoperator(self):
+        """the 4 x 4 superoperator of a one-qubit error on the column-stacked density matrix (rho_ij at index i + 2j);
+        for a two-qubit error the 16 x 16 one, error qubit 0 the low bit of the row and column indices"""
+        if self._n == 1:
+            return self._chan().S.copy()
+        S = np.eye(16, dtype=np.complex128)
+        I2 = _PAULIS[0]
+        for kind, qs, x in self._terms():
+            if kind == "pauli":
+                ks = [np.sqrt(w) * np.kron(_PAULIS[p >> 2], _PAULIS[p & 3]) for p, w in enumerate(x) if w > 0]
+            else:
+                ks = [np.kron(I2, k) if qs[0] == 0 else np.kron(k, I2) for k in x.kraus()]
+            S = sum(np.kron(k.conj(), k) for k in ks) @ S
+        return S
+
+    def terms(self):
+        """what ingest walks, in order: ("pauli", error qubits, probability table) or ("kraus", (error qubit,), stack of m
+        2 x 2 operators).  A one-qubit channel without given Kraus operators that is a Pauli channel comes as "pauli"."""
+        if self._emit is None:
+            out = []
+            for kind, qs, x in self._terms():
+                if kind == "chan":
+                    p = _pauli_table_of(x.S) if x.given is None else None
+                    if p is not None:
+                        p.setflags(write=False)
+                        out.append(("pauli", qs, p))
+                    else:
+                        ks = np.array(x.kraus(), dtype=np.complex128).reshape(-1, 2, 2)
+                        ks.setflags(write=False)
+                        out.append(("kraus", qs, ks))
+                else:
+                    out.append((kind, qs, x))
+            self._emit = tuple(out)
+        return self._emit
 
     def compose(self, other):
-        """``other`` after ``self``: the Pauli tables convolve over the Pauli group (phases dropped)"""
+        """``other`` after ``self``.  Pauli tables convolve over the Pauli group (phases dropped); one-qubit channels
+        multiply their superoperators (a Pauli table is lifted when it meets a non-Pauli partner); on two qubits the
+        ordered terms are concatenated and adjacent terms of one shape on the same qubits merged"""
         other = _as_error(other)
         if other.num_qubits != self._n:
             raise ValueError("cannot compose a %d-qubit error with a %d-qubit one" % (self._n, other.num_qubits))
-        idx = np.arange(4 ** self._n)
-        out = np.zeros(4 ** self._n)
-        for b, q in enumerate(other.probabilities):
-            if q:
-                out[idx ^ b] += self._p * q
-        return QuantumError(out / out.sum(), self._n)
+        if self._chain is None and other._chain is None:
+            idx = np.arange(4 ** self._n)
+            out = np.zeros(4 ** self._n)
+            for b, q in enumerate(other.probabilities):
+                if q:
+                    out[idx ^ b] += self._p * q
+            return QuantumError(out / out.sum(), self._n)
+        if self._n == 1:
+            return QuantumError._from_terms([("chan", (0,), _Chan(other._chan().S @ self._chan().S))], 1)
+        return QuantumError._from_terms(self._terms() + other._terms(), 2)
 
     def tensor(self, other):
         """``self`` (x) ``other``: ``other`` acts on error qubit 0, ``self`` on error qubit 1 (Qiskit order)"""
         other = _as_error(other)
         if self._n + other.num_qubits > 2:
             raise ValueError("tensor products beyond 2 qubits are not supported")
-        p = np.outer(self._p, other.probabilities).ravel()          # index = self_index * 4 + other_index
-        return QuantumError(p / p.sum(), 2)
+        if self._chain is None and other._chain is None:
+            p = np.outer(self._p, other.probabilities).ravel()          # index = self_index * 4 + other_index
+            return QuantumError(p / p.sum(), 2)
+        return QuantumError._from_terms([("chan", (0,), other._chan()), ("chan", (1,), self._chan())], 2)
 
     def expand(self, other):
         """``other`` (x) ``self``"""
         return _as_error(other).tensor(self)
 
     def __eq__(self, other):
-        return isinstance(other, QuantumError) and other.num_qubits == self._n and np.allclose(other._p, self._p, atol=_TOL, rtol=0)
+        if not isinstance(other, QuantumError) or other.num_qubits != self._n:
+            return False
+        if self._chain is None and other._chain is None:
+            return bool(np.allclose(other._p, self._p, atol=_TOL, rtol=0))
+        return bool(np.allclose(other.superoperator(), self.superoperator(), atol=1e-10, rtol=0))
 
     __hash__ = None
 
     def __repr__(self):
-        return "QuantumError(%s)" % self.to_dict()
+        if self._chain is None:
+            return "QuantumError(%s)" % self.to_dict()
+        return "QuantumError(%d qubit(s): %s)" % (self._n, ", ".join(
+            "%s on %s" % ("Pauli table" if k == "pauli" else "%d Kraus operators" % len(x.kraus()), list(qs))
+            for k, qs, x in self._chain))
 
 
 def _as_error(e):
     if not isinstance(e, QuantumError):
         raise TypeError("expected a qcmrf_amd.noise.QuantumError, got %s" % type(e).__name__)
     return e
+
+
+def kraus_error(noise_ops):
+    """a one-qubit channel from 1 to 4 Kraus operators (2 x 2), kept as given and in order; more than four are reduced
+    to the canonical set.  sum K^dg K must be the identity to 1e-12.  Two-qubit Kraus sets are refused: build a
+    two-qubit error as a tensor product of one-qubit channels, composed with two-qubit Pauli errors"""
+    ks = [np.array(k, dtype=np.complex128) for k in noise_ops]
+    if not ks:
+        raise ValueError("kraus_error needs at least one operator")
+    if any(k.shape == (4, 4) for k in ks):
+        raise ValueError("a general two-qubit Kraus set is not supported: only tensor products of one-qubit channels "
+                         "(a.tensor(b) / a.expand(b)), composed with two-qubit Pauli errors")
+    if any(k.shape != (2, 2) for k in ks):
+        raise ValueError("Kraus operators are 2 x 2 matrices, got shapes %s" % sorted({k.shape for k in ks}))
+    if not all(np.all(np.isfinite(k)) for k in ks):
+        raise ValueError("Kraus operators must be finite")
+    tp = sum(k.conj().T @ k for k in ks)
+    if np.abs(tp - np.eye(2)).max() > _TOL:
+        raise ValueError("not a channel: sum K^dg K differs from the identity by %.3g" % np.abs(tp - np.eye(2)).max())
+    S = _superop_of_kraus(ks)
+    for k in ks:
+        k.setflags(write=False)
+    return QuantumError._from_terms([("chan", (0,), _Chan(S, ks if len(ks) <= 4 else None))], 1)
+
+
+def phase_amplitude_damping_error(param_amp, param_phase, excited_state_population=0):
+    """Aer's combined damping channel: with a = param_amp, b = param_phase, p1 = the excited state population and
+    c = 1 - a - b >= 0 the Kraus operators sqrt(1 - p1) {diag(1, sqrt c), sqrt a |0><1|, sqrt b diag(0, 1)} and
+    sqrt(p1) {diag(sqrt c, 1), sqrt a |1><0|, sqrt b diag(1, 0)}"""
+    a, b, p1 = float(param_amp), float(param_phase), float(excited_state_population)
+    if not (0.0 <= a <= 1.0 and 0.0 <= b <= 1.0):
+        raise ValueError("damping parameters %r, %r outside [0, 1]" % (param_amp, param_phase))
+    if a + b > 1.0 + _TOL:
+        raise ValueError("param_amp + param_phase = %.17g exceeds 1" % (a + b))
+    if not 0.0 <= p1 <= 1.0:
+        raise ValueError("excited state population %r outside [0, 1]" % (excited_state_population,))
+    c = np.sqrt(max(0.0, 1.0 - a - b))
+    sa, sb, s0, s1 = np.sqrt(a), np.sqrt(b), np.sqrt(1.0 - p1), np.sqrt(p1)
+    ks = [s0 * np.diag([1.0, c]), s0 * sa * np.array([[0, 1], [0, 0]]), s0 * sb * np.diag([0.0, 1.0]),
+          s1 * np.diag([c, 1.0]), s1 * sa * np.array([[0, 0], [1, 0]]), s1 * sb * np.diag([1.0, 0.0])]
+    return kraus_error([k for k in ks if np.abs(k).max() > 0])
+
+
+def amplitude_damping_error(param_amp, excited_state_population=0):
+    return phase_amplitude_damping_error(param_amp, 0.0, excited_state_population)
+
+
+def phase_damping_error(param_phase):
+    return phase_amplitude_damping_error(0.0, param_phase, 0)
+
+
+def _from_superop(S, what):
+    S = np.asarray(S, dtype=np.complex128)
+    _check_cptp(S, what)
+    return QuantumError._from_terms([("chan", (0,), _Chan(S))], 1)
+
+
+def thermal_relaxation_error(t1, t2, time, excited_state_population=0):
+    """T1 / T2 relaxation over ``time`` (all three in one unit): with p_r = 1 - exp(-time / t1), e2 = exp(-time / t2),
+    p1 = the excited state population and p0 = 1 - p1,
+        rho00' = (1 - p1 p_r) rho00 + p0 p_r rho11,  rho11' = p1 p_r rho00 + (1 - p0 p_r) rho11,  rho01' = e2 rho01:
+    one CPTP map for t2 <= t1 and for t1 < t2 <= 2 t1.  Trajectories agree with Aer's in distribution."""
+    t1, t2, time, p1 = float(t1), float(t2), float(time), float(excited_state_population)
+    if not (t1 > 0 and t2 > 0):
+        raise ValueError("t1 and t2 must be positive (inf allowed), got %r, %r" % (t1, t2))
+    if not (time >= 0 and np.isfinite(time)):
+        raise ValueError("the gate time must be finite and >= 0, got %r" % (time,))
+    if t2 > 2.0 * t1:
+        raise ValueError("t2 = %r exceeds 2 t1 = %r" % (t2, 2.0 * t1))
+    if not 0.0 <= p1 <= 1.0:
+        raise ValueError("excited state population %r outside [0, 1]" % (excited_state_population,))
+    pr, e2, p0 = -np.expm1(-time / t1), np.exp(-time / t2), 1.0 - p1
+    S = np.array([[1.0 - p1 * pr, 0, 0, p0 * pr], [0, e2, 0, 0], [0, 0, e2, 0], [p1 * pr, 0, 0, 1.0 - p0 * pr]])
+    return _from_superop(S, "thermal relaxation")
+
+
+def reset_error(prob0, prob1=0):
+    """with probability prob0 the qubit is set to |0>, with prob1 to |1>, otherwise it is left alone"""
+    a, b = float(prob0), float(prob1)
+    if not (a >= 0 and b >= 0 and a + b <= 1.0 + _TOL):
+        raise ValueError("reset probabilities %r, %r must be non-negative and sum to at most 1" % (prob0, prob1))
+    r0 = np.array([[1, 0, 0, 1], [0, 0, 0, 0], [0, 0, 0, 0], [0, 0, 0, 0]], dtype=np.float64)
+    r1 = r0[::-1].copy()
+    return _from_superop(max(0.0, 1.0 - a - b) * np.eye(4) + a * r0 + b * r1, "reset error")
 
 
 def pauli_error(noise_ops):
@@ -204,7 +487,7 @@ def _names(instructions):
 
 
 class NoiseModel:
-    """Pauli gate errors and readout errors, keyed by instruction name as in ``qiskit_aer.noise.NoiseModel``.
+    """Gate errors (Pauli and Kraus) and readout errors, keyed by instruction name as in ``qiskit_aer.noise.NoiseModel``.
 
     A local error (``add_quantum_error``) replaces the all-qubit error of the same instruction on exactly those
     qubits (in that order); adding a second error for the same key composes it after the first."""

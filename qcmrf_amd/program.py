@@ -14,6 +14,7 @@ def encode(ops):
     rec = np.zeros(len(ops), dtype=_lib.OP_DTYPE)
     pool = []
     top = 0
+    kraus_seen = {}
 
     def put(arr):
         nonlocal top
@@ -84,6 +85,14 @@ def encode(ops):
             r["kind"] = _lib.OP_PAULI
             fill(r, op.qubits)
             r["data_off"] = put_real(pauli_cumulative(op.table, len(op.qubits)))
+        elif k == "kraus":
+            ks = np.asarray(op.table, dtype=np.complex128)
+            r["kind"] = _lib.OP_KRAUS
+            fill(r, op.qubits, [len(ks)])
+            flat = kraus_seen.get(id(op.table))                 # a model hands every gate the same stack
+            if flat is None:
+                flat = kraus_seen[id(op.table)] = kraus_tables(ks)
+            r["data_off"] = put_real(flat)
         else:
             raise ValueError("cannot encode op kind %r" % k)
     data = np.concatenate(pool) if pool else np.zeros(0, dtype=np.float64)
@@ -99,6 +108,19 @@ def pauli_cumulative(probs, n):
     cum = np.cumsum(p)
     cum[int(np.flatnonzero(p > 0)[-1]):] = 1.0
     return cum
+
+
+def kraus_tables(ks):
+    """QSV_OP_KRAUS data: the m operators (each row-major, re / im as for QSV_OP_1Q: 8 doubles), then for each
+    E_k = K_k^dg K_k as (E00, E11, Re E01, Im E01): the branch weights of a shot are tr(E_k rho) of its own state"""
+    ks = np.ascontiguousarray(ks, dtype=np.complex128)
+    if ks.ndim != 3 or ks.shape[1:] != (2, 2) or not 1 <= len(ks) <= 4:
+        raise ValueError("a Kraus op holds 1 to 4 operators of 2 x 2, got shape %s" % (ks.shape,))
+    E = np.einsum("kai,kaj->kij", ks.conj(), ks)
+    if np.abs(E.sum(axis=0) - np.eye(2)).max() > 1e-9:
+        raise ValueError("the operators of a Kraus op do not sum to a channel (sum K^dg K != 1)")
+    e = np.stack([E[:, 0, 0].real, E[:, 1, 1].real, E[:, 0, 1].real, E[:, 0, 1].imag], axis=1)
+    return np.concatenate([ks.view(np.float64).ravel(), e.ravel()])
 
 
 def run_stepwise(engine, ops):

@@ -1,7 +1,7 @@
 """The reference's experiment driver (/root/reference/run_experiment.py:1-61) on this engine.
 
     python -m qcmrf_amd.run_experiment [--scale 0.5] [--shots 10000] [--reps 10] [--outdir .]
-                                       [--depolarizing P1,P2] [--readout P]
+                                       [--depolarizing P1,P2] [--readout P] [--t1 US --t2 US --gate-time NS1,NS2]
 
 Same steps, same files: seed numpy with 1984, draw theta = -halfnorm.rvs(scale) for the 7
 hard-coded graphs x REPS, dump ``models_<SCALE>.json``, build the 70 ``QCMRF`` circuits, run them
@@ -12,8 +12,10 @@ is importable (the engine ingests the nested circuits directly); the unreachable
 tail (run_experiment.py:63-88) is not reproduced.
 
 With ``--depolarizing P1,P2`` and / or ``--readout P`` the run is noisy instead, with an IBM-like Pauli model: depolarizing
-P1 after every ``sx``, ``x`` and ``id``, P2 after every ``cx``, a symmetric readout error P on every qubit.  The circuits are
-then always lowered to {cx,id,rz,sx,x} (by ``qcmrf_amd.transpile`` when Qiskit is absent) so that those gates exist,
+P1 after every ``sx``, ``x`` and ``id``, P2 after every ``cx``, a symmetric readout error P on every qubit.
+``--t1 US --t2 US --gate-time NS1,NS2`` adds thermal relaxation (T1 and T2 in microseconds): over NS1 nanoseconds after
+every ``sx``, ``x`` and ``id``, over NS2 on both qubits of every ``cx``, each composed with the depolarizing error of
+the gate when that is given too.  The circuits are then always lowered to {cx,id,rz,sx,x} (by ``qcmrf_amd.transpile`` when Qiskit is absent) so that those gates exist,
 and the counts go to ``result_simulation_noisy_<SCALE>.json``.
 """
 from __future__ import annotations
@@ -37,8 +39,11 @@ def main(argv=None):
     ap.add_argument("--depolarizing", default=None, metavar="P1,P2",
                     help="depolarizing parameter after sx/x/id and after cx (noisy run)")
     ap.add_argument("--readout", type=float, default=None, metavar="P", help="symmetric readout error (noisy run)")
+    ap.add_argument("--t1", type=float, default=None, metavar="US", help="T1 in microseconds (noisy run, with --t2 and --gate-time)")
+    ap.add_argument("--t2", type=float, default=None, metavar="US", help="T2 in microseconds, at most 2 T1")
+    ap.add_argument("--gate-time", default=None, metavar="NS1,NS2", help="duration of sx/x/id and of cx in nanoseconds")
     args = ap.parse_args(argv)
-    model = ibm_like_model(args.depolarizing, args.readout)
+    model = ibm_like_model(args.depolarizing, args.readout, args.t1, args.t2, args.gate_time)
 
     np.random.seed(1984)
     from scipy.stats import halfnorm
@@ -76,12 +81,24 @@ def main(argv=None):
     return counts
 
 
-def ibm_like_model(depolarizing=None, readout=None):
-    """``--depolarizing P1,P2`` / ``--readout P`` -> a NoiseModel (None when neither is given)"""
-    if depolarizing is None and readout is None:
+def ibm_like_model(depolarizing=None, readout=None, t1=None, t2=None, gate_time=None):
+    """``--depolarizing P1,P2`` / ``--readout P`` / ``--t1 US --t2 US --gate-time NS1,NS2`` -> a NoiseModel (None when none
+    is given).  Thermal relaxation comes first on a gate, the depolarizing error is composed after it."""
+    thermal = [x is not None for x in (t1, t2, gate_time)]
+    if any(thermal) and not all(thermal):
+        raise ValueError("thermal relaxation needs all of --t1, --t2 and --gate-time")
+    if depolarizing is None and readout is None and not any(thermal):
         return None
-    from .noise import NoiseModel, ReadoutError, depolarizing_error
+    from .noise import NoiseModel, ReadoutError, depolarizing_error, thermal_relaxation_error
     nm = NoiseModel()
+    if any(thermal):
+        times = [float(x) for x in str(gate_time).split(",")]
+        if len(times) != 2:
+            raise ValueError("--gate-time takes two numbers NS1,NS2, got %r" % (gate_time,))
+        one = thermal_relaxation_error(float(t1) * 1e3, float(t2) * 1e3, times[0])
+        two = thermal_relaxation_error(float(t1) * 1e3, float(t2) * 1e3, times[1])
+        nm.add_all_qubit_quantum_error(one, ["sx", "x", "id"])
+        nm.add_all_qubit_quantum_error(two.expand(two), ["cx"])
     if depolarizing is not None:
         parts = [float(x) for x in str(depolarizing).split(",")]
         if len(parts) != 2:
