@@ -275,6 +275,41 @@ int qsv_noisy_sample(qsv_handle* h, const qsv_op* ops, int n_ops, const double* 
                      const double* readout /* n_meas x 2: P(flip | 0), P(flip | 1); NULL = none */,
                      uint64_t* out_bits);
 
+/* ---- density matrix: exact noisy distributions ------------------------------------------- */
+
+#define QSV_DENSITY_MAX_QUBITS 17
+
+/* A density matrix of W qubits is the amplitude vector of a single-shard handle of n_qubits = 2W (W <=
+ * QSV_DENSITY_MAX_QUBITS: 16 x 4^W bytes): amplitude v = i | (j << W) holds rho[i, j], ket bits low, bra bits high.
+ *
+ * qsv_density_exec runs the record stream of qsv_noisy_sample from |0..0><0..0|, exactly: a unitary record U as
+ * U rho U^dg (the record on the ket bits and its mirror on the bra bits -- qubits + W, matrix and table conjugated, angle
+ * negated -- through the sweeps of qsv_exec), QSV_OP_PAULI as sum_p P(p) P rho P^dg with P(p) the differences of the
+ * record's cumulative table, QSV_OP_KRAUS as sum_k K_k rho K_k^dg (its E tables are not read).
+ * Kinds: INIT_ZERO, INIT_UNIFORM, 1Q, MCX, DIAG, MCPHASE, PAULI (n = 1, 2), KRAUS (n = 1, 1..4 operators); MUX, KQ, SWAP and
+ * handles of several shards or ranks return QSV_E_UNSUPPORTED; an odd n_qubits or a record qubit >= W QSV_E_BADARG.  Every
+ * record is checked before the first one runs.
+ * Replaces: simulator.run(T, noise_model=..., method="density_matrix") of Qiskit Aer. */
+int qsv_density_exec(qsv_handle* h, const qsv_op* ops, int n_ops, const double* data, uint64_t n_data);
+
+/* the 4^n real coefficients a PAULI record (n = 1, 2) comes to on a density matrix (host only, no device needed):
+ * out[x * 2^n + d] = sum_z P(x, z) (-1)^(z . d), with x, z the x and z bits of the Pauli index (QSV_OP_PAULI) and P the
+ * differences of `cum`; then rho'[v] = sum_x out[x][d(v)] rho[v ^ m_x], m_x = the x bits on both sides, d(v) = (i xor j)
+ * on the error qubits. */
+int qsv_density_pauli_table(int n, const double* cum, double* out);
+
+/* out[j] = sum Re rho[i, i] over the i whose bits qubits[b] spell j (k <= W, 2^k doubles, not clipped); *trace = the sum
+ * over all i (trace may be NULL).  One strided read of 2^W elements, summed in ascending i: the same bits every time. */
+int qsv_density_diagonal(qsv_handle* h, const int* qubits, int k, double* out, double* trace);
+
+/* `shots` basis states of the W qubits from P_i = max(Re rho[i, i], 0), recorded as qsv_noisy_sample records them
+ * (meas_qubits, n_meas, readout, out_bits as there).  u = the Philox draw (seed, shot, stream 1, draw 0); the state is the
+ * first i whose inclusive cumulative sum (ascending i) exceeds u sum P, none: the last i with P_i > 0; each measured bit j
+ * is flipped when the draw (seed, shot, stream 2, draw j) is below readout[2j + value].  A shot depends on (seed, shot)
+ * alone. */
+int qsv_density_sample(qsv_handle* h, uint64_t shots, uint64_t seed, const int* meas_qubits, int n_meas,
+                       const double* readout /* n_meas x 2; NULL = none */, uint64_t* out_bits);
+
 /* ---- instrumentation ---------------------------------------------------------------- */
 
 /* on: bracket every kernel launch with HIP events on its own stream (costs a little) */

@@ -30,6 +30,7 @@ OPTION_DEFAULTS = {"blocks_per_cu": 1 << 16, "unroll": 4, "lowt_shuffle": 1, "no
 
 OP_INIT_ZERO, OP_INIT_UNIFORM, OP_1Q, OP_MCX, OP_DIAG, OP_MCPHASE, OP_MUX, OP_KQ, OP_SWAP, OP_PAULI, OP_KRAUS = range(11)
 NOISY_MAX_QUBITS = 13     # qsv_noisy_sample: one trajectory's state lives in the LDS of one workgroup
+DENSITY_MAX_QUBITS = 17   # qsv_density_*: rho of W qubits is a vector of 2W qubits, 16 * 4^W bytes
 OPF_NEW_PASS = 1
 
 
@@ -86,6 +87,10 @@ SIGNATURES = {
     "qsv_copy_state": (_i, [_vp, _vp]),
     "qsv_exec": (_i, [_vp, _vp, _i, _dp, _u64]),
     "qsv_noisy_sample": (_i, [_vp, _vp, _i, _dp, _u64, _u64, _u64, _ip, _i, _dp, _u64p]),
+    "qsv_density_exec": (_i, [_vp, _vp, _i, _dp, _u64]),
+    "qsv_density_pauli_table": (_i, [_i, _dp, _dp]),
+    "qsv_density_diagonal": (_i, [_vp, _ip, _i, _dp, _dp]),
+    "qsv_density_sample": (_i, [_vp, _u64, _u64, _ip, _i, _dp, _u64p]),
     "qsv_set_profiling": (_i, [_vp, _i]),
     "qsv_reset_stats": (_i, [_vp]),
     "qsv_get_stats": (_i, [_vp, _P(Stats)]),
@@ -184,6 +189,16 @@ def device_bus_id(device=0):
     buf = C.create_string_buffer(64)
     _chk(load().qsv_device_bus_id(int(device), buf, 64))
     return buf.value.decode()
+
+
+def density_pauli_table(n, cum):
+    """the (2^n, 2^n) real coefficients c[x, d] of a PAULI record on a density matrix (qsv_density_pauli_table; host only)"""
+    ca, cp = _da(cum)
+    if ca.size != 4 ** int(n):
+        raise ValueError("a Pauli error on %d qubits has %d cumulative probabilities, got %d" % (n, 4 ** int(n), ca.size))
+    out = np.zeros(4 ** int(n), dtype=np.float64)
+    _chk(load().qsv_density_pauli_table(int(n), cp, out.ctypes.data_as(_dp)))
+    return out.reshape(1 << int(n), 1 << int(n))
 
 
 def comm_unique_id():
@@ -365,6 +380,35 @@ class Engine:
             raise ValueError("readout needs 2 probabilities per measured bit (%d), got %d" % (nm, ra.size))
         _chk(self._lib.qsv_noisy_sample(self._h, ops.ctypes.data_as(_vp), len(ops), dp, len(data), int(shots), int(seed),
                                         qp, nm, rp, out.ctypes.data_as(_u64p)))
+        return out
+
+    # -- density matrix: this engine's 2W qubits hold rho of W qubits, rho[i, j] at i | (j << W)
+    def density_exec(self, ops, data):
+        """the record stream of ``noisy_sample`` applied exactly to rho from |0..0><0..0| (qsv_density_exec)"""
+        ops = np.ascontiguousarray(ops, dtype=OP_DTYPE)
+        da, dp = _da(data if len(data) else np.zeros(1))
+        _chk(self._lib.qsv_density_exec(self._h, ops.ctypes.data_as(_vp), len(ops), dp, len(data)))
+
+    def density_diagonal(self, qubits):
+        """(marginal of Re rho_ii over ``qubits`` -- index bit b <-> qubits[b], not clipped --, trace)"""
+        qa, qp = _ia(qubits if len(qubits) else [0])
+        out = np.zeros(1 << len(qubits), dtype=np.float64)
+        tr = C.c_double()
+        _chk(self._lib.qsv_density_diagonal(self._h, qp, len(qubits), out.ctypes.data_as(_dp), C.byref(tr)))
+        return out, tr.value
+
+    def density_sample(self, shots, seed, meas_qubits=None, readout=None):
+        """``shots`` words drawn from the diagonal of rho, recorded as ``noisy_sample`` records them (qsv_density_sample)"""
+        out = np.zeros(int(shots), dtype=np.uint64)
+        if meas_qubits is None:
+            qa, qp, nm = None, None, 0
+        else:
+            nm = len(meas_qubits)
+            qa, qp = _ia(meas_qubits if nm else [-1])
+        ra, rp = (None, None) if readout is None else _da(readout)
+        if ra is not None and (meas_qubits is None or ra.size != 2 * nm):
+            raise ValueError("readout needs 2 probabilities per measured bit (%d), got %d" % (nm, ra.size))
+        _chk(self._lib.qsv_density_sample(self._h, int(shots), int(seed), qp, nm, rp, out.ctypes.data_as(_u64p)))
         return out
 
     # -- measurement

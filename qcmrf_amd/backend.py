@@ -22,6 +22,9 @@ import numpy as np
 from . import _lib, ingest as _ingest, noise as _noise, passes, planner, program
 from .comm import SingleProcess
 
+_METHODS = ("statevector", "trajectory", "density_matrix")
+DENSITY_MAX_CLBITS = 20       # method="density_matrix" returns 2^k probabilities over the k written classical bits
+
 _NAMES = ("qasm_simulator", "aer_simulator", "aer_simulator_statevector", "statevector_simulator",
           "qsv_simulator")
 
@@ -46,6 +49,23 @@ class Result:
         for e in self._exps:
             if e["name"] == getattr(experiment, "name", experiment):
                 return dict(e["counts"])
+        raise KeyError("no experiment %r" % (experiment,))
+
+    def get_probabilities(self, experiment=None):
+        """exact distribution over the written classical bits, ``{bitstring: p}`` with the keys of ``get_counts`` and the
+        entries with p > 0 only (``method="density_matrix"`` runs; a list when more than one circuit ran)"""
+        def one(e):
+            if "probabilities" not in e:
+                raise ValueError("experiment %r holds no exact distribution: run it with method='density_matrix'" % (e["name"],))
+            return dict(e["probabilities"])
+        if experiment is None:
+            ps = [one(e) for e in self._exps]
+            return ps[0] if len(ps) == 1 else ps
+        if isinstance(experiment, int):
+            return one(self._exps[experiment])
+        for e in self._exps:
+            if e["name"] == getattr(experiment, "name", experiment):
+                return one(e)
         raise KeyError("no experiment %r" % (experiment,))
 
     def metadata(self, i=0):
@@ -105,7 +125,10 @@ class QsvBackend:
     devices     HIP device id per shard owned by this process (repeat an id for virtual shards)
     method      'statevector' (default: all measurements deferred, one evolution, W qubits) |
                 'trajectory' (mid-circuit measurements taken when they occur, measured qubits
-                released: n+2 live qubits for a QCMRF circuit, see qcmrf_amd.trajectory)
+                released: n+2 live qubits for a QCMRF circuit, see qcmrf_amd.trajectory) |
+                'density_matrix' (the circuit under ``noise_model``, or ideal, evolved exactly as rho -> sum K rho K^dg in a
+                vector of 2W qubits: ``Result.get_probabilities()`` is the exact distribution over the written classical
+                bits, the counts are drawn from it; W <= 17, one process, <= 20 written classical bits)
     comm        process group for one-process-per-GPU launches (qcmrf_amd.comm)
     gather_counts  'root' (default: rank 0 returns the merged counts, the other ranks an empty dict) | 'all'
     spmd_ingest    (multi-rank) each rank reads 1/N of the circuit's composite blocks, one all-gather completes the program
@@ -207,6 +230,20 @@ class QsvBackend:
         if seed_simulator is None:
             seed_simulator = int(np.random.SeedSequence().entropy % (2 ** 63))
         exps = []
+        method = opts.get("method", "statevector")
+        if method not in _METHODS:
+            raise ValueError("unknown method %r; this backend runs %s" % (method, ", ".join(_METHODS)))
+        if method == "density_matrix":
+            model = self._density_model_of(opts)
+            from concurrent.futures import ThreadPoolExecutor
+            with ThreadPoolExecutor(max_workers=1) as pool:     # host compile of circuit i+1 while the device evolves circuit i
+                nxt = pool.submit(self._prepare_density, circs[0], model)
+                for i in range(len(circs)):
+                    prepared = nxt.result()
+                    if i + 1 < len(circs):
+                        nxt = pool.submit(self._prepare_density, circs[i + 1], model)
+                    exps.append(self._run_density(circs[i], int(shots), int(seed_simulator) + i, opts, prepared))
+            return Job(Result(exps, self._name))
         model = self._noise_of(opts)
         if model is not None:
             # host compile of circuit i+1 on a helper thread while the device runs the shots of circuit i
@@ -296,6 +333,95 @@ class QsvBackend:
         self.last_plan = None
         self._last_comm = None
         return {"name": getattr(circuit, "name", "circuit"), "shots": shots, "counts": counts, "metadata": meta}
+
+    # ---- method="density_matrix": rho of W qubits in a vector of 2W ---------------------------------
+    @staticmethod
+    def _density_model_of(opts):
+        """the model of a density-matrix run: the given one, or an empty one (no model, the ideal distribution)"""
+        model = opts.get("noise_model")
+        if model is not None and not isinstance(model, _noise.NoiseModel):
+            raise TypeError("noise_model must be a qcmrf_amd.noise.NoiseModel, not %s" % type(model).__name__)
+        comm = opts["comm"] or SingleProcess()
+        if comm.world > 1:
+            raise ValueError("method='density_matrix' takes one process (a process group of %d ranks was given; limit 1)" % comm.world)
+        return model if model is not None else _noise.NoiseModel()
+
+    @staticmethod
+    def _prepare_density(circuit, model):
+        """host half of a density-matrix run: the record stream of a noisy run (ingest with the model + encode)"""
+        t0 = time.perf_counter()
+        ing = _ingest.ingest(circuit, noise=model)
+        if ing.num_qubits > _lib.DENSITY_MAX_QUBITS:
+            raise ValueError("method='density_matrix' holds rho of at most %d qubits (16 * 4^W bytes), the circuit has %d"
+                             % (_lib.DENSITY_MAX_QUBITS, ing.num_qubits))
+        clist = sorted(ing.measure)
+        if len(clist) > DENSITY_MAX_CLBITS:
+            raise ValueError("method='density_matrix' returns the distribution over at most %d written classical bits, the "
+                             "circuit writes %d" % (DENSITY_MAX_CLBITS, len(clist)))
+        if clist and clist[-1] >= 64:
+            raise ValueError("method='density_matrix' records at most 64 classical bits, the circuit writes bit %d" % clist[-1])
+        rec, data = program.encode(ing.ops)
+        meas = [-1] * (clist[-1] + 1) if clist else []
+        readout = np.zeros((len(meas), 2))
+        for c in clist:
+            meas[c] = ing.measure[c]
+            readout[c] = ing.readout.get(c, (0.0, 0.0))
+        return ing, rec, data, clist, meas, readout, time.perf_counter() - t0
+
+    @staticmethod
+    def _confuse(dist, flips):
+        """readout confusion on the host: bit j of the index flipped with flips[j][value]"""
+        words = np.arange(dist.size)
+        for j, (f0, f1) in enumerate(flips):
+            if f0 == 0.0 and f1 == 0.0:
+                continue
+            go = np.where((words >> j) & 1, f1, f0)
+            new = dist * (1.0 - go)
+            new[words ^ (1 << j)] += dist * go
+            dist = new
+        return dist
+
+    def _run_density(self, circuit, shots, seed, opts, prepared):
+        """qsv_density_exec, then the exact distribution (qsv_density_diagonal + readout confusion) and the shots (qsv_density_sample)"""
+        ing, rec, data, clist, meas, readout, t_compile = prepared
+        t1 = time.perf_counter()
+        t0 = t1 - t_compile
+        W = ing.num_qubits
+        state_bytes = 16 * 4 ** W
+        dev = tuple(opts["devices"])[0]
+        memory = _lib.device_memory if self._engine_factory is None else getattr(self._engine_factory, "device_memory", None)
+        if memory is not None and not (self._engine is not None and self._engine_key == (2 * W, (dev,))):
+            free = memory(dev)[0]
+            if state_bytes > free:
+                raise ValueError("method='density_matrix': rho of %d qubits takes 16 * 4^%d = %d bytes, device %d has %d free"
+                                 % (W, W, state_bytes, dev, free))
+        eng = self._get_engine(2 * W, dict(opts, comm=None, devices=tuple(opts["devices"])[:1]))
+        self._apply_engine_options(eng, opts)
+        eng.density_exec(rec, data)
+        eng.sync()
+        t2 = time.perf_counter()
+        marg, trace = eng.density_diagonal([ing.measure[c] for c in clist])
+        dist = self._confuse(marg, [tuple(readout[c]) for c in clist])
+        keep = np.flatnonzero(dist > 0)
+        words = np.zeros(keep.size, dtype=np.uint64)            # bit j of the index is classical bit clist[j]
+        for j, c in enumerate(clist):
+            words |= ((keep.astype(np.uint64) >> np.uint64(j)) & np.uint64(1)) << np.uint64(c)
+        probs = dict(zip(_format_keys(words, np.arange(keep.size), ing.num_clbits, ing.creg_sizes).keys(), dist[keep].tolist())) if clist else {}
+        counts = {}
+        if clist and shots > 0:
+            bits = eng.density_sample(shots, seed, meas, readout if ing.readout else None)
+            uv, uc = np.unique(bits, return_counts=True)
+            counts = _format_keys(uv, uc, ing.num_clbits, ing.creg_sizes)
+        t3 = time.perf_counter()
+        meta = {"method": "density_matrix", "n_qubits": W, "n_source_ops": ing.n_source_ops, "n_device_ops": len(rec),
+                "n_pauli_ops": ing.n_pauli, "n_kraus_ops": ing.n_kraus, "readout_errors": len(ing.readout), "trace": float(trace),
+                "state_bytes": state_bytes, "time_compile": t1 - t0, "time_evolve": t2 - t1, "time_sample": t3 - t2,
+                "time_taken": t3 - t0, "seed_simulator": seed}
+        self.last_engine = None          # the resident vector is rho, not a state: statevector() has nothing to show
+        self.last_plan = None
+        self._last_comm = None
+        return {"name": getattr(circuit, "name", "circuit"), "shots": shots, "counts": counts, "probabilities": probs,
+                "metadata": meta}
 
     def _apply_engine_options(self, eng, opts):
         """engine options are per RUN: whatever an earlier call set on the cached engine and this one does not ask for

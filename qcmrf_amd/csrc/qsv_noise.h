@@ -29,6 +29,23 @@ static_assert(sizeof(NzOp) == 32, "NzOp is 32 bytes");
 // Philox-4x32-10 streams (counter word 1): every random number is a pure function of (seed, shot, stream, draw)
 enum { NZ_STREAM_PAULI = 0, NZ_STREAM_SAMPLE = 1, NZ_STREAM_READOUT = 2 };
 
+// the draw itself, in [0, 1): 53 bits of counter (draw, stream, shot lo, shot hi) under the 64-bit seed
+__device__ __forceinline__ double philox_u01(uint64_t seed, uint64_t shot, uint32_t stream, uint32_t draw) {
+  uint32_t c0 = draw, c1 = stream, c2 = (uint32_t)shot, c3 = (uint32_t)(shot >> 32);
+  uint32_t k0 = (uint32_t)seed, k1 = (uint32_t)(seed >> 32);
+#pragma unroll
+  for (int r = 0; r < 10; ++r) {
+    if (r) { k0 += 0x9E3779B9u; k1 += 0xBB67AE85u; }
+    const uint32_t hi0 = __umulhi(0xD2511F53u, c0), lo0 = 0xD2511F53u * c0;
+    const uint32_t hi1 = __umulhi(0xCD9E8D57u, c2), lo1 = 0xCD9E8D57u * c2;
+    c0 = hi1 ^ c1 ^ k0;
+    c1 = lo1;
+    c2 = hi0 ^ c3 ^ k1;
+    c3 = lo0;
+  }
+  return (double)((((uint64_t)c0 << 32) | c1) >> 11) * 0x1.0p-53;      // 53 bits: [0, 1)
+}
+
 struct NzMeas {
   int n;                    // measured bits (<= 64); < 0: out = the full basis index
   int readout;              // pool offset of n x 2 flip probabilities, < 0: none

@@ -20,22 +20,6 @@
 #include "qsv_noise.h"
 #include "qsv_common.h"
 
-__device__ __forceinline__ double philox_u01(uint64_t seed, uint64_t shot, uint32_t stream, uint32_t draw) {
-  uint32_t c0 = draw, c1 = stream, c2 = (uint32_t)shot, c3 = (uint32_t)(shot >> 32);
-  uint32_t k0 = (uint32_t)seed, k1 = (uint32_t)(seed >> 32);
-#pragma unroll
-  for (int r = 0; r < 10; ++r) {
-    if (r) { k0 += 0x9E3779B9u; k1 += 0xBB67AE85u; }
-    const uint32_t hi0 = __umulhi(0xD2511F53u, c0), lo0 = 0xD2511F53u * c0;
-    const uint32_t hi1 = __umulhi(0xCD9E8D57u, c2), lo1 = 0xCD9E8D57u * c2;
-    c0 = hi1 ^ c1 ^ k0;
-    c1 = lo1;
-    c2 = hi0 ^ c3 ^ k1;
-    c3 = lo0;
-  }
-  return (double)((((uint64_t)c0 << 32) | c1) >> 11) * 0x1.0p-53;      // 53 bits: [0, 1)
-}
-
 // amplitude times i^ny, negated if neg
 __device__ __forceinline__ cplx pauli_phase(cplx a, uint32_t ny, bool neg) {
   cplx r = a;

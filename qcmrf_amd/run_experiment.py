@@ -2,6 +2,7 @@
 
     python -m qcmrf_amd.run_experiment [--scale 0.5] [--shots 10000] [--reps 10] [--outdir .]
                                        [--depolarizing P1,P2] [--readout P] [--t1 US --t2 US --gate-time NS1,NS2]
+                                       [--method density_matrix]
 
 Same steps, same files: seed numpy with 1984, draw theta = -halfnorm.rvs(scale) for the 7
 hard-coded graphs x REPS, dump ``models_<SCALE>.json``, build the 70 ``QCMRF`` circuits, run them
@@ -17,6 +18,10 @@ P1 after every ``sx``, ``x`` and ``id``, P2 after every ``cx``, a symmetric read
 every ``sx``, ``x`` and ``id``, over NS2 on both qubits of every ``cx``, each composed with the depolarizing error of
 the gate when that is given too.  The circuits are then always lowered to {cx,id,rz,sx,x} (by ``qcmrf_amd.transpile`` when Qiskit is absent) so that those gates exist,
 and the counts go to ``result_simulation_noisy_<SCALE>.json``.
+
+``--method density_matrix`` evolves every circuit exactly as a density matrix (noisy or not): the counts are drawn from the
+exact distributions, and those are written as well, one ``{bitstring: p}`` per circuit, to ``probs_simulation_<SCALE>.json``
+(``probs_simulation_noisy_<SCALE>.json`` for a noisy run).
 """
 from __future__ import annotations
 
@@ -42,6 +47,8 @@ def main(argv=None):
     ap.add_argument("--t1", type=float, default=None, metavar="US", help="T1 in microseconds (noisy run, with --t2 and --gate-time)")
     ap.add_argument("--t2", type=float, default=None, metavar="US", help="T2 in microseconds, at most 2 T1")
     ap.add_argument("--gate-time", default=None, metavar="NS1,NS2", help="duration of sx/x/id and of cx in nanoseconds")
+    ap.add_argument("--method", default=None, choices=["density_matrix"],
+                    help="density_matrix: exact distributions (probs_simulation_*.json) next to the counts drawn from them")
     args = ap.parse_args(argv)
     model = ibm_like_model(args.depolarizing, args.readout, args.t1, args.t2, args.gate_time)
 
@@ -70,6 +77,8 @@ def main(argv=None):
     simulator = Aer.get_backend('qasm_simulator')
     t0 = time.perf_counter()
     extra = {} if model is None else {"noise_model": model}
+    if args.method is not None:
+        extra["method"] = args.method
     result = simulator.run(CIRCS, shots=args.shots, seed_simulator=args.seed_simulator, **extra).result()
     counts = result.get_counts()
     dt = time.perf_counter() - t0
@@ -78,6 +87,11 @@ def main(argv=None):
     name = "result_simulation_" if model is None else "result_simulation_noisy_"
     with open(os.path.join(args.outdir, name + str(args.scale) + ".json"), "w") as f:
         f.write(json.dumps(counts, indent=4))
+    if args.method == "density_matrix":
+        probs = result.get_probabilities()
+        name = "probs_simulation_" if model is None else "probs_simulation_noisy_"
+        with open(os.path.join(args.outdir, name + str(args.scale) + ".json"), "w") as f:
+            f.write(json.dumps(probs if isinstance(probs, list) else [probs], indent=4))
     return counts
 
 
