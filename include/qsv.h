@@ -275,6 +275,21 @@ int qsv_noisy_sample(qsv_handle* h, const qsv_op* ops, int n_ops, const double* 
                      const double* readout /* n_meas x 2: P(flip | 0), P(flip | 1); NULL = none */,
                      uint64_t* out_bits);
 
+#define QSV_NOISY_HBM_MAX_QUBITS 24
+
+/* qsv_noisy_sample for up to QSV_NOISY_HBM_MAX_QUBITS qubits: the same arguments, checks, record kinds, draws and words, with
+ * every trajectory's 2^W amplitudes in a slot of 16 x 2^W bytes of device memory instead of LDS.  A persistent workgroup
+ * owns one slot and runs shots b, b + grid, ... in it; grid = min(shots, the noisy_grid option if set, the workgroups the
+ * chip holds at once, the slots that fit into 90 % of the free device memory).  The slots are one allocation per call,
+ * freed before the call returns; if not even one fits, QSV_E_NOMEM names the bytes needed and the bytes free
+ * (qsv_device_memory).  Widths up to QSV_NOISY_MAX_QUBITS are accepted too (the two paths can be compared on them):
+ * a shot's Pauli, Kraus and readout draws are those of qsv_noisy_sample; sums of |amp|^2 are added in another order, so
+ * a draw within rounding distance of a boundary may fall on its other side.  Opt-in: qsv_noisy_sample is unchanged. */
+int qsv_noisy_sample_hbm(qsv_handle* h, const qsv_op* ops, int n_ops, const double* data, uint64_t n_data,
+                         uint64_t shots, uint64_t seed, const int* meas_qubits, int n_meas,
+                         const double* readout /* n_meas x 2: P(flip | 0), P(flip | 1); NULL = none */,
+                         uint64_t* out_bits);
+
 /* ---- density matrix: exact noisy distributions ------------------------------------------- */
 
 #define QSV_DENSITY_MAX_QUBITS 17
@@ -339,7 +354,7 @@ int qsv_timer_end(qsv_handle* h, double* ms);
  *   kernels     unroll [4], lowt_shuffle [1], pair_variant [0], kq_mfma [1], blocks_per_cu [65536]
  *               swizzle [1]        one-gate kernels: lane bit 5 of a wave access carries address bit 11 (two 512-byte runs 32 KiB apart);
  *                                  1 from 2^26 amplitudes per shard, 2 from 2^14, 0 never        lane_map_min_l [26]  same for k_multi tiles other than bits 6..10
- *   noisy       noisy_grid [0]     workgroups of qsv_noisy_sample: 0 = as many as the chip holds at once, else at most this many
+ *   noisy       noisy_grid [0]     workgroups of qsv_noisy_sample and qsv_noisy_sample_hbm: 0 = as many as the chip holds at once, else at most this many
  *   other       zero_tracking [0]  skip amplitudes known to be zero (opt-in)       exchange_chunk_log2 [24]  amplitudes per exchange chunk
  *               implied_zeros [1]  the generator as a program's last pass (and qsv_exec's end) leaves the provably-zero part
  *                                  of a shard unwritten; every reader honours that or writes the zeros first (0: write them always) */

@@ -30,6 +30,7 @@ OPTION_DEFAULTS = {"blocks_per_cu": 1 << 16, "unroll": 4, "lowt_shuffle": 1, "no
 
 OP_INIT_ZERO, OP_INIT_UNIFORM, OP_1Q, OP_MCX, OP_DIAG, OP_MCPHASE, OP_MUX, OP_KQ, OP_SWAP, OP_PAULI, OP_KRAUS = range(11)
 NOISY_MAX_QUBITS = 13     # qsv_noisy_sample: one trajectory's state lives in the LDS of one workgroup
+NOISY_HBM_MAX_QUBITS = 24 # qsv_noisy_sample_hbm: one trajectory's state lives in a slot of device memory
 DENSITY_MAX_QUBITS = 17   # qsv_density_*: rho of W qubits is a vector of 2W qubits, 16 * 4^W bytes
 OPF_NEW_PASS = 1
 
@@ -87,6 +88,7 @@ SIGNATURES = {
     "qsv_copy_state": (_i, [_vp, _vp]),
     "qsv_exec": (_i, [_vp, _vp, _i, _dp, _u64]),
     "qsv_noisy_sample": (_i, [_vp, _vp, _i, _dp, _u64, _u64, _u64, _ip, _i, _dp, _u64p]),
+    "qsv_noisy_sample_hbm": (_i, [_vp, _vp, _i, _dp, _u64, _u64, _u64, _ip, _i, _dp, _u64p]),
     "qsv_density_exec": (_i, [_vp, _vp, _i, _dp, _u64]),
     "qsv_density_pauli_table": (_i, [_i, _dp, _dp]),
     "qsv_density_diagonal": (_i, [_vp, _ip, _i, _dp, _dp]),
@@ -367,6 +369,14 @@ class Engine:
         """one trajectory per shot from |0..0> (qsv_noisy_sample): ops (OP_DTYPE records, QSV_OP_PAULI and QSV_OP_KRAUS included) on a
         single-shard handle of at most NOISY_MAX_QUBITS qubits; out[s] as ``sample``.  readout: n_meas x 2 array of
         (P(flip | 0), P(flip | 1)) per output bit, or None"""
+        return self._noisy(self._lib.qsv_noisy_sample, ops, data, shots, seed, meas_qubits, readout)
+
+    def noisy_sample_hbm(self, ops, data, shots, seed, meas_qubits=None, readout=None):
+        """``noisy_sample`` with every trajectory in a slot of device memory (qsv_noisy_sample_hbm): at most
+        NOISY_HBM_MAX_QUBITS qubits, the same arguments, draws and words"""
+        return self._noisy(self._lib.qsv_noisy_sample_hbm, ops, data, shots, seed, meas_qubits, readout)
+
+    def _noisy(self, fn, ops, data, shots, seed, meas_qubits, readout):
         ops = np.ascontiguousarray(ops, dtype=OP_DTYPE)
         da, dp = _da(data if len(data) else np.zeros(1))
         out = np.zeros(int(shots), dtype=np.uint64)
@@ -378,8 +388,7 @@ class Engine:
         ra, rp = (None, None) if readout is None else _da(readout)
         if ra is not None and (meas_qubits is None or ra.size != 2 * nm):
             raise ValueError("readout needs 2 probabilities per measured bit (%d), got %d" % (nm, ra.size))
-        _chk(self._lib.qsv_noisy_sample(self._h, ops.ctypes.data_as(_vp), len(ops), dp, len(data), int(shots), int(seed),
-                                        qp, nm, rp, out.ctypes.data_as(_u64p)))
+        _chk(fn(self._h, ops.ctypes.data_as(_vp), len(ops), dp, len(data), int(shots), int(seed), qp, nm, rp, out.ctypes.data_as(_u64p)))
         return out
 
     # -- density matrix: this engine's 2W qubits hold rho of W qubits, rho[i, j] at i | (j << W)

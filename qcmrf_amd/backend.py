@@ -23,6 +23,7 @@ from . import _lib, ingest as _ingest, noise as _noise, passes, planner, program
 from .comm import SingleProcess
 
 _METHODS = ("statevector", "trajectory", "density_matrix")
+_NOISY_STATES = ("lds", "hbm", "auto")
 DENSITY_MAX_CLBITS = 20       # method="density_matrix" returns 2^k probabilities over the k written classical bits
 
 _NAMES = ("qasm_simulator", "aer_simulator", "aer_simulator_statevector", "statevector_simulator",
@@ -138,13 +139,16 @@ class QsvBackend:
     noise_model a ``qcmrf_amd.noise.NoiseModel`` (Pauli and one-qubit Kraus gate errors, readout errors): every shot is its own trajectory
                 on the device (``qsv_noisy_sample``), W <= 13 qubits and <= 64 classical bits; None or an empty model
                 runs the ideal path
+    noisy_state where a noisy shot keeps its state: 'lds' (default: on-chip memory, W <= 13) | 'hbm' (a slot of device
+                memory per resident shot, ``qsv_noisy_sample_hbm``, W <= 24; the same draws and words) | 'auto' ('lds' up to
+                13 qubits, 'hbm' above)
     """
 
     def __init__(self, name="qasm_simulator", **options):
         self._name = name
         self.options = {"fusion": 3, "layout": "auto", "devices": (0,), "comm": None, "device": 0,
                         "profile": False, "engine_options": None, "method": "statevector", "fold_fresh": True,
-                        "gather_counts": "root", "noise_model": None}
+                        "gather_counts": "root", "noise_model": None, "noisy_state": "lds"}
         self.options.update(options)
         self._engine = None
         self._engine_key = None
@@ -233,6 +237,9 @@ class QsvBackend:
         method = opts.get("method", "statevector")
         if method not in _METHODS:
             raise ValueError("unknown method %r; this backend runs %s" % (method, ", ".join(_METHODS)))
+        state = opts.get("noisy_state", "lds")
+        if state not in _NOISY_STATES:
+            raise ValueError("unknown noisy_state %r; a noisy shot keeps its state in %s" % (state, ", ".join(_NOISY_STATES)))
         if method == "density_matrix":
             model = self._density_model_of(opts)
             from concurrent.futures import ThreadPoolExecutor
@@ -249,11 +256,11 @@ class QsvBackend:
             # host compile of circuit i+1 on a helper thread while the device runs the shots of circuit i
             from concurrent.futures import ThreadPoolExecutor
             with ThreadPoolExecutor(max_workers=1) as pool:
-                nxt = pool.submit(self._prepare_noisy, circs[0], model)
+                nxt = pool.submit(self._prepare_noisy, circs[0], model, state)
                 for i in range(len(circs)):
                     prepared = nxt.result()
                     if i + 1 < len(circs):
-                        nxt = pool.submit(self._prepare_noisy, circs[i + 1], model)
+                        nxt = pool.submit(self._prepare_noisy, circs[i + 1], model, state)
                     exps.append(self._run_noisy(circs[i], int(shots), int(seed_simulator) + i, opts, prepared))
             return Job(Result(exps, self._name))
         if len(circs) > 1 and opts.get("method", "statevector") == "statevector":
@@ -293,13 +300,20 @@ class QsvBackend:
         return model
 
     @staticmethod
-    def _prepare_noisy(circuit, model):
-        """host half of a noisy run: ingest with the model's Pauli and Kraus ops (identity layout) + encode"""
+    def _prepare_noisy(circuit, model, state="lds"):
+        """host half of a noisy run: ingest with the model's Pauli and Kraus ops (identity layout) + encode; ``state`` is
+        the run option noisy_state, returned resolved ('lds' or 'hbm')"""
         t0 = time.perf_counter()
         ing = _ingest.ingest(circuit, noise=model)
-        if ing.num_qubits > _lib.NOISY_MAX_QUBITS:
-            raise ValueError("noisy runs keep one state per shot in on-chip memory: at most %d qubits, the circuit has %d"
-                             % (_lib.NOISY_MAX_QUBITS, ing.num_qubits))
+        if state == "auto":
+            state = "lds" if ing.num_qubits <= _lib.NOISY_MAX_QUBITS else "hbm"
+        if state == "lds" and ing.num_qubits > _lib.NOISY_MAX_QUBITS:
+            raise ValueError("noisy runs keep one state per shot in on-chip memory: at most %d qubits, the circuit has %d "
+                             "(noisy_state='hbm' or 'auto' keeps it in device memory: at most %d qubits)"
+                             % (_lib.NOISY_MAX_QUBITS, ing.num_qubits, _lib.NOISY_HBM_MAX_QUBITS))
+        if state == "hbm" and ing.num_qubits > _lib.NOISY_HBM_MAX_QUBITS:
+            raise ValueError("noisy runs with noisy_state='hbm' keep one state per shot in device memory: at most %d qubits, "
+                             "the circuit has %d" % (_lib.NOISY_HBM_MAX_QUBITS, ing.num_qubits))
         if ing.num_clbits > 64:
             raise ValueError("noisy runs record at most 64 classical bits, the circuit has %d" % ing.num_clbits)
         rec, data = program.encode(ing.ops)
@@ -309,11 +323,11 @@ class QsvBackend:
         for c in clist:
             meas[c] = ing.measure[c]
             readout[c] = ing.readout.get(c, (0.0, 0.0))
-        return ing, rec, data, clist, meas, readout, time.perf_counter() - t0
+        return ing, rec, data, clist, meas, readout, time.perf_counter() - t0, state
 
     def _run_noisy(self, circuit, shots, seed, opts, prepared):
-        """one qsv_noisy_sample call: shots trajectories, sampled and read out on the device"""
-        ing, rec, data, clist, meas, readout, t_compile = prepared
+        """one qsv_noisy_sample (or qsv_noisy_sample_hbm) call: shots trajectories, sampled and read out on the device"""
+        ing, rec, data, clist, meas, readout, t_compile, state = prepared
         t1 = time.perf_counter()
         t0 = t1 - t_compile
         counts = {}
@@ -321,12 +335,13 @@ class QsvBackend:
         if clist and shots > 0:
             eng = self._get_engine(ing.num_qubits, dict(opts, comm=None, devices=tuple(opts["devices"])[:1]))
             self._apply_engine_options(eng, opts)
-            bits = eng.noisy_sample(rec, data, shots, seed, meas, readout if ing.readout else None)
+            sample = eng.noisy_sample_hbm if state == "hbm" else eng.noisy_sample
+            bits = sample(rec, data, shots, seed, meas, readout if ing.readout else None)
             t2 = time.perf_counter()
             uv, uc = np.unique(bits, return_counts=True)
             counts = _format_keys(uv, uc, ing.num_clbits, ing.creg_sizes)
         t3 = time.perf_counter()
-        meta = {"method": "noisy", "n_qubits": ing.num_qubits, "n_source_ops": ing.n_source_ops, "n_device_ops": len(rec),
+        meta = {"method": "noisy", "noisy_state": state, "n_qubits": ing.num_qubits, "n_source_ops": ing.n_source_ops, "n_device_ops": len(rec),
                 "n_pauli_ops": ing.n_pauli, "n_kraus_ops": ing.n_kraus, "readout_errors": len(ing.readout), "time_compile": t1 - t0,
                 "time_evolve": t2 - t1, "time_sample": t3 - t2, "time_taken": t3 - t0, "seed_simulator": seed}
         self.last_engine = None          # no resident state: every shot had its own

@@ -4,6 +4,7 @@
 #include "qsv_kernels.h"
 #include "qsv_kmulti_inst.h"
 #include "qsv_noise.h"
+#include "qsv_noise_hbm.h"
 #include "qsv_density.h"
 QSV_KMULTI_FOR_GENERAL(QSV_KMULTI_DECLARE)
 QSV_KMULTI_FOR_MODE(QSV_KMULTI_DECLARE, 1)

@@ -151,30 +151,27 @@ extern "C" int qsv_exec(qsv_handle* h, const qsv_op* ops, int n_ops, const doubl
 }
 
 // ------------------------------------------------------------------------------------------
-// noisy shots: one trajectory per shot in LDS (kernel: qsv_noise.hip)
+// noisy shots: one trajectory per shot, in LDS (kernel: qsv_noise.hip) or in a slot of device memory (qsv_noise_hbm.hip)
 // ------------------------------------------------------------------------------------------
-// The qsv_op records are re-encoded once per call into 32-byte NzOp records and a pool in which equal tables are
-// stored once (a lowered circuit repeats a handful of matrices thousands of times): every trajectory streams the
-// whole list.
-extern "C" int qsv_noisy_sample(qsv_handle* h, const qsv_op* ops, int n_ops, const double* data, uint64_t n_data,
-                                uint64_t shots, uint64_t seed, const int* meas_qubits, int n_meas,
-                                const double* readout, uint64_t* out_bits) {
-  if (!h || n_ops < 0 || (n_ops && !ops) || (shots && !out_bits)) return fail(QSV_E_BADARG, "NULL argument");
-  if (h->multiproc || h->shards.size() != 1) return fail(QSV_E_UNSUPPORTED, "noisy shots need a single-shard handle");
-  if (h->W > QSV_NOISY_MAX_QUBITS)
-    return fail(QSV_E_BADARG, "noisy shots keep one %d-qubit state per trajectory in LDS: at most %d qubits", h->W, QSV_NOISY_MAX_QUBITS);
-  if (meas_qubits && (n_meas < 0 || n_meas > 64)) return fail(QSV_E_BADARG, "n_meas %d out of range", n_meas);
-  if (readout && !meas_qubits) return fail(QSV_E_BADARG, "readout errors need meas_qubits");
-  if (meas_qubits) for (int j = 0; j < n_meas; ++j) if (meas_qubits[j] >= 0) CHK(check_qubit(h, meas_qubits[j], "measured"));
-  if (readout)
-    for (int j = 0; j < 2 * n_meas; ++j)
-      if (!(readout[j] >= 0.0 && readout[j] <= 1.0)) return fail(QSV_E_BADARG, "readout probability %d = %g not in [0, 1]", j, readout[j]);
-  std::vector<NzOp> cops;
-  cops.reserve(n_ops);
-  bool has_kraus = false;
+// The qsv_op records are re-encoded once per call into 32-byte records (NzOp, or NzWideOp for the slot path) and a pool in
+// which equal tables are stored once (a lowered circuit repeats a handful of matrices thousands of times): every
+// trajectory streams the whole list.  One validator (nz_encode) fills both record formats; what differs between them
+// is how a control bit and a listed qubit are stored, which the two pairs of overloads below say.
+static inline void nz_put_ctrl(NzOp& c, int q, bool one) {
+  c.cmask |= (uint16_t)(1u << q);
+  if (one) c.cval |= (uint16_t)(1u << q);
+}
+static inline void nz_put_ctrl(NzWideOp& c, int q, bool one) {
+  c.cmask |= 1u << q;
+  if (one) c.cval |= 1u << q;
+}
+static inline void nz_put_qubit(NzOp& c, int b, int q) { c.qlist |= (uint64_t)q << (4 * b); }
+static inline void nz_put_qubit(NzWideOp& c, int b, int q) { c.ql[b >> 3] |= (uint64_t)q << (8 * (b & 7)); }
+
+struct NzPool {                                                   // each table once, at an even offset (16-byte aligned)
   std::vector<double> pool;
   std::unordered_map<std::string, uint32_t> seen;
-  auto put = [&](const double* v, size_t cnt) -> uint32_t {       // each table once, at an even offset (16-byte aligned)
+  uint32_t put(const double* v, size_t cnt) {
     std::string key(reinterpret_cast<const char*>(v), cnt * sizeof(double));
     auto it = seen.find(key);
     if (it != seen.end()) return it->second;
@@ -183,7 +180,31 @@ extern "C" int qsv_noisy_sample(qsv_handle* h, const qsv_op* ops, int n_ops, con
     if (pool.size() & 1) pool.push_back(0.0);
     seen.emplace(std::move(key), off);
     return off;
-  };
+  }
+};
+
+// the checks both entry points make on everything but the records
+static int nz_check_args(qsv_handle* h, const qsv_op* ops, int n_ops, uint64_t shots, const uint64_t* out_bits) {
+  if (!h || n_ops < 0 || (n_ops && !ops) || (shots && !out_bits)) return fail(QSV_E_BADARG, "NULL argument");
+  if (h->multiproc || h->shards.size() != 1) return fail(QSV_E_UNSUPPORTED, "noisy shots need a single-shard handle");
+  return QSV_OK;
+}
+static int nz_check_meas(qsv_handle* h, const int* meas_qubits, int n_meas, const double* readout) {
+  if (meas_qubits && (n_meas < 0 || n_meas > 64)) return fail(QSV_E_BADARG, "n_meas %d out of range", n_meas);
+  if (readout && !meas_qubits) return fail(QSV_E_BADARG, "readout errors need meas_qubits");
+  if (meas_qubits) for (int j = 0; j < n_meas; ++j) if (meas_qubits[j] >= 0) CHK(check_qubit(h, meas_qubits[j], "measured"));
+  if (readout)
+    for (int j = 0; j < 2 * n_meas; ++j)
+      if (!(readout[j] >= 0.0 && readout[j] <= 1.0)) return fail(QSV_E_BADARG, "readout probability %d = %g not in [0, 1]", j, readout[j]);
+  return QSV_OK;
+}
+
+// validates every record and appends its compact form (Rec = NzOp or NzWideOp) to cops, its tables to pool
+template <class Rec>
+static int nz_encode(qsv_handle* h, const qsv_op* ops, int n_ops, const double* data, uint64_t n_data, std::vector<Rec>& cops,
+                     NzPool& pool, bool* has_kraus) {
+  cops.reserve(n_ops);
+  *has_kraus = false;
   for (int i = 0; i < n_ops; ++i) {
     const qsv_op& o = ops[i];
     if (o.n < 0 || o.n > QSV_MAX_CTRL) return fail(QSV_E_BADARG, "op %d: n=%d out of range", i, o.n);
@@ -193,13 +214,10 @@ extern "C" int qsv_noisy_sample(qsv_handle* h, const qsv_op* ops, int n_ops, con
                                                           (unsigned long long)o.data_off, (unsigned long long)cnt, (unsigned long long)n_data);
       return QSV_OK;
     };
-    auto ctrl_mask = [&](NzOp& c) {
-      for (int b = 0; b < o.n; ++b) {
-        c.cmask |= (uint16_t)(1u << o.qubits[b]);
-        if (o.vals[b]) c.cval |= (uint16_t)(1u << o.qubits[b]);
-      }
+    auto ctrl_mask = [&](Rec& c) {
+      for (int b = 0; b < o.n; ++b) nz_put_ctrl(c, o.qubits[b], o.vals[b] != 0);
     };
-    NzOp c;
+    Rec c;
     memset(&c, 0, sizeof c);
     switch (o.kind) {
       case QSV_OP_INIT_ZERO:
@@ -208,8 +226,8 @@ extern "C" int qsv_noisy_sample(qsv_handle* h, const qsv_op* ops, int n_ops, con
         if (mask >> h->W) return fail(QSV_E_BADARG, "op %d: mask has bits beyond qubit %d", i, h->W - 1);
         const double val = std::pow(2.0, -0.5 * __builtin_popcountll(mask));
         c.kind = NZ_INIT;
-        c.cmask = (uint16_t)mask;
-        c.off = put(&val, 1);
+        c.cmask = (decltype(c.cmask))mask;
+        c.off = pool.put(&val, 1);
         break;
       }
       case QSV_OP_1Q:
@@ -217,17 +235,17 @@ extern "C" int qsv_noisy_sample(qsv_handle* h, const qsv_op* ops, int n_ops, con
         CHK(check_qubit(h, o.target, "target"));
         CHK(check_distinct(h, o.n, o.qubits, o.target));
         c.kind = o.kind == QSV_OP_1Q ? NZ_1Q : NZ_MCX;
-        c.target = (uint16_t)o.target;
+        c.target = (decltype(c.target))o.target;
         ctrl_mask(c);
-        if (o.kind == QSV_OP_1Q) { CHK(need(8)); c.off = put(d, 8); }
+        if (o.kind == QSV_OP_1Q) { CHK(need(8)); c.off = pool.put(d, 8); }
         break;
       case QSV_OP_DIAG:
         CHK(check_distinct(h, o.n, o.qubits, -1));
         CHK(need(2ull << o.n));
         c.kind = NZ_DIAG;
-        c.n = (uint32_t)o.n;
-        for (int b = 0; b < o.n; ++b) c.qlist |= (uint64_t)o.qubits[b] << (4 * b);
-        c.off = put(d, 2ull << o.n);
+        c.n = (decltype(c.n))o.n;
+        for (int b = 0; b < o.n; ++b) nz_put_qubit(c, b, o.qubits[b]);
+        c.off = pool.put(d, 2ull << o.n);
         break;
       case QSV_OP_MCPHASE: {
         if (o.n < 1) return fail(QSV_E_BADARG, "op %d: a controlled phase needs at least one qubit", i);
@@ -235,7 +253,7 @@ extern "C" int qsv_noisy_sample(qsv_handle* h, const qsv_op* ops, int n_ops, con
         const double cs[2] = {std::cos(o.angle), std::sin(o.angle)};
         c.kind = NZ_MCPHASE;
         ctrl_mask(c);
-        c.off = put(cs, 2);
+        c.off = pool.put(cs, 2);
         break;
       }
       case QSV_OP_PAULI: {
@@ -249,9 +267,9 @@ extern "C" int qsv_noisy_sample(qsv_handle* h, const qsv_op* ops, int n_ops, con
                         (unsigned long long)p, d[p]);
         if (d[np - 1] != 1.0) return fail(QSV_E_BADARG, "op %d: cumulative Pauli probabilities end at %.17g, not 1", i, d[np - 1]);
         c.kind = NZ_PAULI;
-        c.n = (uint32_t)o.n;
-        for (int b = 0; b < o.n; ++b) c.qlist |= (uint64_t)o.qubits[b] << (4 * b);
-        c.off = put(d, np);
+        c.n = (decltype(c.n))o.n;
+        for (int b = 0; b < o.n; ++b) nz_put_qubit(c, b, o.qubits[b]);
+        c.off = pool.put(d, np);
         break;
       }
       case QSV_OP_KRAUS: {
@@ -271,10 +289,10 @@ extern "C" int qsv_noisy_sample(qsv_handle* h, const qsv_op* ops, int n_ops, con
         if (std::fabs(e00 - 1.0) > 1e-9 || std::fabs(e11 - 1.0) > 1e-9 || std::fabs(e01r) > 1e-9 || std::fabs(e01i) > 1e-9)
           return fail(QSV_E_BADARG, "op %d: the K^dg K of a Kraus channel must sum to the identity (diagonal %.17g, %.17g)", i, e00, e11);
         c.kind = NZ_KRAUS;
-        c.target = (uint16_t)o.qubits[0];
-        c.n = (uint32_t)m;
-        c.off = put(d, 12 * (size_t)m);
-        has_kraus = true;
+        c.target = (decltype(c.target))o.qubits[0];
+        c.n = (decltype(c.n))m;
+        c.off = pool.put(d, 12 * (size_t)m);
+        *has_kraus = true;
         break;
       }
       default:
@@ -282,21 +300,25 @@ extern "C" int qsv_noisy_sample(qsv_handle* h, const qsv_op* ops, int n_ops, con
     }
     cops.push_back(c);
   }
-  NzMeas meas;
-  meas.n = meas_qubits ? n_meas : -1;
-  meas.readout = -1;
-  if (readout && n_meas > 0) meas.readout = (int)put(readout, 2 * (size_t)n_meas);
-  if (pool.empty()) pool.push_back(0.0);
-  if (pool.size() >= (1ull << 31)) return fail(QSV_E_BADARG, "tables of %zu doubles exceed the noisy op stream's offsets", pool.size());
-  if (shots == 0) return QSV_OK;
+  return QSV_OK;
+}
+
+// the device copies of one call in the shard's noisy buffer: [ops | pool | pos | out], each part 256-byte aligned
+struct NzStaged {
+  char* ops;
+  const double* pool;
+  const int* pos;
+  uint64_t* out;
+};
+template <class Rec>
+static int nz_stage(Shard& s, const std::vector<Rec>& cops, const std::vector<double>& pool, const int* meas_qubits, int n_meas,
+                    uint64_t shots, NzStaged* st) {
+  static_assert(sizeof(Rec) == 32, "compact records are 32 bytes");
   std::vector<int> pos(64, -1);
   for (int j = 0; meas_qubits && j < n_meas; ++j) pos[j] = meas_qubits[j];
-  // one device buffer: [ops | pool | pos | out], each part 256-byte aligned
   auto up = [](size_t b) { return (b + 255) & ~size_t(255); };
-  const size_t b_ops = up(cops.size() * sizeof(NzOp) + 1), b_pool = up(pool.size() * sizeof(double)), b_pos = up(64 * sizeof(int));
+  const size_t b_ops = up(cops.size() * sizeof(Rec) + 1), b_pool = up(pool.size() * sizeof(double)), b_pos = up(64 * sizeof(int));
   const size_t bytes = b_ops + b_pool + b_pos + up(shots * sizeof(uint64_t));
-  Shard& s = h->shards[0];
-  CHK(shard_set(s));
   if (s.noisy_cap < bytes) {
     if (s.d_noisy) { HIPCHK(hipStreamSynchronize(s.stream)); HIPCHK(hipFree(s.d_noisy)); }
     s.d_noisy = nullptr;
@@ -305,27 +327,130 @@ extern "C" int qsv_noisy_sample(qsv_handle* h, const qsv_op* ops, int n_ops, con
     s.noisy_cap = bytes;
   }
   char* base = s.d_noisy;
+  st->ops = base;
+  st->pool = reinterpret_cast<const double*>(base + b_ops);
+  st->pos = reinterpret_cast<const int*>(base + b_ops + b_pool);
+  st->out = reinterpret_cast<uint64_t*>(base + b_ops + b_pool + b_pos);
+  if (!cops.empty()) HIPCHK(hipMemcpyAsync(base, cops.data(), cops.size() * sizeof(Rec), hipMemcpyHostToDevice, s.stream));
+  HIPCHK(hipMemcpyAsync(base + b_ops, pool.data(), pool.size() * sizeof(double), hipMemcpyHostToDevice, s.stream));
+  HIPCHK(hipMemcpyAsync(base + b_ops + b_pool, pos.data(), 64 * sizeof(int), hipMemcpyHostToDevice, s.stream));
+  return QSV_OK;
+}
+
+// records -> compact records, pool and measurement map of one call
+template <class Rec>
+static int nz_prepare(qsv_handle* h, const qsv_op* ops, int n_ops, const double* data, uint64_t n_data, const int* meas_qubits,
+                      int n_meas, const double* readout, std::vector<Rec>& cops, NzPool& pool, bool* has_kraus, NzMeas* meas) {
+  CHK(nz_check_meas(h, meas_qubits, n_meas, readout));
+  CHK(nz_encode(h, ops, n_ops, data, n_data, cops, pool, has_kraus));
+  meas->n = meas_qubits ? n_meas : -1;
+  meas->readout = -1;
+  meas->pos = nullptr;
+  if (readout && n_meas > 0) meas->readout = (int)pool.put(readout, 2 * (size_t)n_meas);
+  if (pool.pool.empty()) pool.pool.push_back(0.0);
+  if (pool.pool.size() >= (1ull << 31)) return fail(QSV_E_BADARG, "tables of %zu doubles exceed the noisy op stream's offsets", pool.pool.size());
+  return QSV_OK;
+}
+
+extern "C" int qsv_noisy_sample(qsv_handle* h, const qsv_op* ops, int n_ops, const double* data, uint64_t n_data,
+                                uint64_t shots, uint64_t seed, const int* meas_qubits, int n_meas,
+                                const double* readout, uint64_t* out_bits) {
+  CHK(nz_check_args(h, ops, n_ops, shots, out_bits));
+  if (h->W > QSV_NOISY_MAX_QUBITS)
+    return fail(QSV_E_BADARG, "noisy shots keep one %d-qubit state per trajectory in LDS: at most %d qubits", h->W, QSV_NOISY_MAX_QUBITS);
+  std::vector<NzOp> cops;
+  NzPool pool;
+  bool has_kraus = false;
+  NzMeas meas;
+  CHK(nz_prepare(h, ops, n_ops, data, n_data, meas_qubits, n_meas, readout, cops, pool, &has_kraus, &meas));
+  if (shots == 0) return QSV_OK;
+  Shard& s = h->shards[0];
+  CHK(shard_set(s));
+  NzStaged st;
+  CHK(nz_stage(s, cops, pool.pool, meas_qubits, n_meas, shots, &st));
   NzLaunch l;
   l.stream = s.stream;
   l.W = h->W;
   l.n_cu = s.n_cu;
   l.max_grid = h->opt_noisy_grid;
-  l.d_ops = reinterpret_cast<const NzOp*>(base);
+  l.d_ops = reinterpret_cast<const NzOp*>(st.ops);
   l.n_ops = (int)cops.size();
   l.kraus = has_kraus;
-  l.d_pool = reinterpret_cast<const double*>(base + b_ops);
+  l.d_pool = st.pool;
   l.shots = shots;
   l.seed = seed;
-  meas.pos = reinterpret_cast<const int*>(base + b_ops + b_pool);
+  meas.pos = st.pos;
   l.meas = meas;
-  l.d_out = reinterpret_cast<uint64_t*>(base + b_ops + b_pool + b_pos);
-  if (!cops.empty()) HIPCHK(hipMemcpyAsync(base, cops.data(), cops.size() * sizeof(NzOp), hipMemcpyHostToDevice, s.stream));
-  HIPCHK(hipMemcpyAsync(base + b_ops, pool.data(), pool.size() * sizeof(double), hipMemcpyHostToDevice, s.stream));
-  HIPCHK(hipMemcpyAsync(base + b_ops + b_pool, pos.data(), 64 * sizeof(int), hipMemcpyHostToDevice, s.stream));
+  l.d_out = st.out;
   unsigned grid = 0;
   HIPCHK(qsv_noise_launch(l, &grid));
   HIPCHK(hipMemcpyAsync(out_bits, l.d_out, shots * sizeof(uint64_t), hipMemcpyDeviceToHost, s.stream));
   HIPCHK(hipStreamSynchronize(s.stream));
+  return QSV_OK;
+}
+
+// The slot path: as qsv_noisy_sample up to the launch.  The slots are one allocation per call, sized for the grid and
+// freed on every way out (NzSlots); nothing of them stays on the handle, so a handle that ran 64 GiB of trajectories
+// holds no more memory afterwards than one that did not.
+struct NzSlots {
+  char* p = nullptr;
+  ~NzSlots() { if (p) hipFree(p); }
+};
+extern "C" int qsv_noisy_sample_hbm(qsv_handle* h, const qsv_op* ops, int n_ops, const double* data, uint64_t n_data,
+                                    uint64_t shots, uint64_t seed, const int* meas_qubits, int n_meas,
+                                    const double* readout, uint64_t* out_bits) {
+  CHK(nz_check_args(h, ops, n_ops, shots, out_bits));
+  if (h->W > QSV_NOISY_HBM_MAX_QUBITS)
+    return fail(QSV_E_BADARG, "noisy shots keep one %d-qubit state per trajectory in a slot of device memory: at most %d qubits",
+                h->W, QSV_NOISY_HBM_MAX_QUBITS);
+  std::vector<NzWideOp> cops;
+  NzPool pool;
+  bool has_kraus = false;
+  NzMeas meas;
+  CHK(nz_prepare(h, ops, n_ops, data, n_data, meas_qubits, n_meas, readout, cops, pool, &has_kraus, &meas));
+  if (shots == 0) return QSV_OK;
+  Shard& s = h->shards[0];
+  CHK(shard_set(s));
+  NzStaged st;
+  CHK(nz_stage(s, cops, pool.pool, meas_qubits, n_meas, shots, &st));
+  // grid = min(shots, noisy_grid if set, workgroups resident at once, slots that fit into 90 % of the free memory)
+  const uint64_t slot = (uint64_t)16 << h->W;
+  uint64_t grid = 0;
+  HIPCHK(qsv_noise_hbm_resident(s.n_cu, &grid));
+  if (h->opt_noisy_grid > 0 && (uint64_t)h->opt_noisy_grid < grid) grid = (uint64_t)h->opt_noisy_grid;
+  if (shots < grid) grid = shots;
+  size_t free_b = 0, total_b = 0;
+  HIPCHK(hipMemGetInfo(&free_b, &total_b));
+  const uint64_t fit = (uint64_t)((double)free_b * 0.9) / slot;
+  if (fit < 1)
+    return fail(QSV_E_NOMEM, "noisy shots in device memory: one %d-qubit trajectory needs %llu bytes, %llu bytes are free (qsv_device_memory)",
+                h->W, (unsigned long long)slot, (unsigned long long)free_b);
+  if (fit < grid) grid = fit;
+  NzSlots slots;
+  if (hipMalloc(&slots.p, grid * slot) != hipSuccess) {
+    slots.p = nullptr;
+    (void)hipGetLastError();
+    return fail(QSV_E_NOMEM, "noisy shots in device memory: %llu slots of %llu bytes need %llu bytes, %llu bytes are free (qsv_device_memory)",
+                (unsigned long long)grid, (unsigned long long)slot, (unsigned long long)(grid * slot), (unsigned long long)free_b);
+  }
+  NzHbmLaunch l;
+  l.stream = s.stream;
+  l.W = h->W;
+  l.grid = (unsigned)grid;
+  l.d_ops = reinterpret_cast<const NzWideOp*>(st.ops);
+  l.n_ops = (int)cops.size();
+  l.d_pool = st.pool;
+  l.shots = shots;
+  l.seed = seed;
+  meas.pos = st.pos;
+  l.meas = meas;
+  l.d_slots = slots.p;
+  l.d_out = st.out;
+  hipError_t e = qsv_noise_hbm_launch(l);
+  if (e == hipSuccess) e = hipMemcpyAsync(out_bits, l.d_out, shots * sizeof(uint64_t), hipMemcpyDeviceToHost, s.stream);
+  const hipError_t e2 = hipStreamSynchronize(s.stream);             // the kernel is done with the slots before they are freed
+  HIPCHK(e);
+  HIPCHK(e2);
   return QSV_OK;
 }
 
