@@ -1,7 +1,10 @@
 """GPU box: differential stress of qsv_exec's pass construction -- random programs of table ops
 (multiplexed 2x2 with RX-like or general matrices, diagonals), controlled gates, X and phases on
 random bits, with and without a leading init, random pass hints and engine options -- against the
-numpy engine.  Not part of the test suite (minutes); run after touching qsv_multi.inc."""
+numpy engine.  Not part of the test suite (minutes); run after touching qsv_multi.inc.
+With sample_shots > 0 every program is also sampled and the words are held to the exact sampling contract
+(tests/_sampler_reference.py): the tile layouts drawn here are the walk orders of the tile-order sampler."""
+import os
 import sys
 sys.path.insert(0, ".")
 import numpy as np
@@ -9,9 +12,32 @@ from qcmrf_amd import _lib, ir, program
 from oracle.sharded_numpy import NumpyEngine
 
 
+def sample_violations(eng, got, shots, seed, exact):
+    """draw ``shots`` words from the state ``got`` was read from and return the sampling rules they break: the
+    order-free contract over |got|^2, plus "exact" (word equality with the index-order reference, off the shots that lie
+    within the tolerance of a prefix boundary) when the sampler walked in index order.  The programs are unnormalised:
+    the tolerance scales with the engine's total."""
+    tests = os.path.join(os.path.dirname(os.path.abspath(__file__)), os.pardir, "tests")
+    if tests not in sys.path:
+        sys.path.insert(0, tests)
+    import _sampler_reference as sr
+    p = got.real * got.real + got.imag * got.imag
+    total = eng.norm()
+    tol = sr.TOL_REL * total
+    r = sr.sorted_uniforms(seed, shots, total)
+    x = sr.unshuffle(seed, shots, eng.sample(shots, seed))
+    rules = sr.rules_of(sr.check_inverse_cdf(p, r, x, tol, total))
+    if exact:
+        want, dist = sr.exact_index_order(p, r)
+        if ((x != want) & (dist > tol)).any():
+            rules.append("exact")
+    return rules
 
-def run(n_cases=300, seed=7, verbose=True, only=None, override=None, widths=(14, 15, 16, 17), poison=False):
-    """returns the number of mismatching programs.  widths: state sizes drawn from; at >= 21 qubits the
+
+
+def run(n_cases=300, seed=7, verbose=True, only=None, override=None, widths=(14, 15, 16, 17), poison=False, sample_shots=0):
+    """returns the number of mismatching programs.  sample_shots: words drawn from every program (seed from the case number)
+    and checked shot by shot; a violated rule counts as a mismatch.  widths: state sizes drawn from; at >= 21 qubits the
     workgroups of a pass no longer run all at once (in-place permutations that cross workgroups show)"""
     rs = np.random.RandomState(seed)
     bad = 0
@@ -114,6 +140,12 @@ def run(n_cases=300, seed=7, verbose=True, only=None, override=None, widths=(14,
             bad += 1
             print("MISMATCH case %d W=%d P=%d style=%d err=%.3e normerr=%.3e opts=%s" % (case, W, P, style, err, nerr, opts), flush=True)
             print("   ops:", [repr(o) + ("*" if o.new_pass else "") for o in ops], flush=True)
+        elif sample_shots > 0:
+            rules = sample_violations(eng, got, sample_shots, 1000003 * seed + case, exact=not opts["fused_sums"])
+            if rules:
+                bad += 1
+                print("SAMPLING case %d W=%d P=%d style=%d rules=%s opts=%s" % (case, W, P, style, rules, opts), flush=True)
+                print("   ops:", [repr(o) + ("*" if o.new_pass else "") for o in ops], flush=True)
         if verbose and min(widths) >= 24:
             print("case %d W=%d P=%d ok so far (%d mismatches)" % (case, W, P, bad), flush=True)     # slow cases: keep the log alive
         if case % 50 == 49 and verbose:
