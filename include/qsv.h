@@ -332,6 +332,20 @@ int qsv_set_profiling(qsv_handle* h, int on);
 int qsv_reset_stats(qsv_handle* h);
 int qsv_get_stats(qsv_handle* h, qsv_stats* out);
 
+/* Deferred state (option defer_state).  A program whose last pass is the generator and leaves tile sums may store no
+ * amplitude at all: the shard keeps the generator's recipe, qsv_sample stores the tiles its shots fall into, qsv_norm
+ * answers from the sums, and every other entry that reads or changes the state first has the generator write it
+ * ("realises" it; booked under QSV_K_INIT_PROD with the bytes stored).  Entries that realise: qsv_get_amplitudes,
+ * qsv_set_amplitudes, qsv_copy_state (source), qsv_probabilities*, qsv_expect_diag, qsv_apply_*, qsv_swap_layout (and
+ * its exchanges), qsv_ipc_export, qsv_density_*, a qsv_exec that does not start with an init, and qsv_norm / qsv_sample
+ * when they cannot use the tile sums (cache_sums or fused_sums 0).  Entries that do not: qsv_sample on the tile path,
+ * qsv_norm from the cached sums, qsv_noisy_sample* (they keep their own states), stats, timers, options, qsv_sync.
+ * Deferred state ends with realisation or with the next init that writes; a program refused before its init writes
+ * leaves the deferred state, recipe included, as it was.
+ * deferred: 1 if a shard of this process is deferred; realize_calls / listed_launches: generator launches so far that
+ * realised a shard / that stored a sampler's tile list.  Any out pointer may be NULL. */
+int qsv_state_info(qsv_handle* h, int* deferred, uint64_t* realize_calls, uint64_t* listed_launches);
+
 /* HIP-event stopwatch on shard 0's stream: begin records, end records+synchronises */
 int qsv_timer_begin(qsv_handle* h);
 int qsv_timer_end(qsv_handle* h, double* ms);
@@ -349,6 +363,8 @@ int qsv_timer_end(qsv_handle* h, double* ms);
  *   generator   init_prod [1]      init x diagonal factors in one write-only pass   init_prod_r [0 = by shard size], init_prod_bit0 [0 = by size]
  *                                  init_prod_grid [0 = every workgroup the chip holds at once; else at most this many]
  *                                  init_prod_group [-1 = up to 3 group bits; 0 = one tile per group; 1..4 = that many]
+ *                                  defer_state [-1]  the generator as a program's last pass, leaving tile sums, stores nothing (qsv_state_info):
+ *                                  -1 from 30 local qubits, 0 never, 1 always
  *   memory      nontemporal [-1], multi_nt [-1], init_prod_nt [-1]   non-temporal loads/stores: -1 by shard size, 0 never, 1 always
  *   measurement cache_sums [1], fused_sums [1]   keep / produce per-tile |amp|^2 sums in the last pass of a program
  *   kernels     unroll [4], lowt_shuffle [1], pair_variant [0], kq_mfma [1], blocks_per_cu [65536]

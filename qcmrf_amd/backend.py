@@ -522,6 +522,11 @@ class QsvBackend:
 
         eng = self._get_engine(ing.num_qubits, opts)
         self._apply_engine_options(eng, opts)      # (the plan above was compiled for exactly this call's options)
+        if (shots <= 0 or not ing.measure) and "defer_state" not in (opts["engine_options"] or {}):
+            # nothing will be sampled, so the caller is after the state: have the generator write it at once instead of
+            # leaving tile sums first and writing it on the first read (the next run's options undo this)
+            eng.set_option("defer_state", 0)
+            eng._applied_options["defer_state"] = 0
         if pl.n_exchanges and not eng._comm_ready:
             # collective: RCCL communicator over all ranks, or peer-mapped shards (ranks sharing a GPU)
             eng.comm_bootstrap(comm, device=opts["device"], transport=opts.get("exchange", "auto"))

@@ -116,6 +116,27 @@ struct StdoutToStderr {
 // ------------------------------------------------------------------------------------------
 struct Pending { int kind; hipEvent_t e0, e1; };
 
+// What the generator needs to produce the state again (k_init_prod): an amplitude is a fixed function of its
+// position, the factor list and the group bits, so a launch with the same recipe stores the same bits at any later time.
+// The factor descriptors and tables live in a device buffer of the shard's own (the arena is recycled).
+struct GenRecipe {
+  int R = 0;
+  uint64_t ntiles = 0;
+  BitIns ins;
+  RegPos rp;
+  LanePos lp;
+  ProdCounts cnt;
+  ProdGroup grp;
+  int ntab = 0;
+  uint64_t nonmask = 0, zskip = 0;
+  double initval = 0.0;
+  unsigned zreg = 0;
+  char* d_buf = nullptr;         // [factor descriptors | tables], grown on demand, kept
+  size_t cap = 0;
+  const ProdFactor* dfac = nullptr;
+  const cplx* dtab = nullptr;
+};
+
 struct Shard {
   int device = 0;
   int index = 0;                 // global shard number (= rank in multi-process mode)
@@ -140,6 +161,11 @@ struct Shard {
   hipEvent_t ev_start = nullptr;
   int n_cu = 256;
   uint64_t zmask = 0;            // local bits known |0>: memory at an address with such a bit set is undefined (implied zeros, materialize)
+  // Deferred state (option defer_state): the last program's final pass was the sums-only generator.  amp then holds
+  // nothing that may be read except the tiles the sampler stored; every other reader calls realize() first, which runs
+  // the writing generator from the recipe.  Ends with realize() or the next write of an init.
+  bool deferred = false;
+  GenRecipe recipe;
   std::vector<double> h_sums;    // host copy of the block sums, valid until the state changes
   bool sums_valid = false;
   // sums left behind by the last k_multi pass of a program, one per workgroup tile (no read pass)
@@ -183,6 +209,7 @@ struct qsv_handle {
   uint64_t ipc_seq = 0;
   std::vector<Shard> shards;     // shards owned by this process
   qsv_stats stats;
+  uint64_t n_realize = 0, n_listed = 0;   // realize() launches, listed-tile launches of the sampler (qsv_state_info)
   bool profiling = false;
   hipEvent_t t0 = nullptr, t1 = nullptr;
   // options
@@ -224,6 +251,7 @@ struct qsv_handle {
   int opt_multi_nt = -1;              // k_multi with non-temporal loads + stores: -1 shards of >= 2^26 amplitudes, 0 never, 1 always
   int opt_init_prod_nt = -1;          // generator with non-temporal stores: -1 by shard size, 0 never, 1 always
   int opt_init_prod_grid = 0;         // workgroups of the persistent generator: 0 = as many as the chip holds, else at most this many
+  int opt_defer_state = -1;           // the generator as a program's last pass leaves tile sums only, the state deferred: -1 from QSV_DEFER_MIN_L local qubits, 0 never, 1 always
   int opt_init_prod_group = -1;       // group bits of the generator (2^B tiles per workgroup step): -1 auto (up to 3), 0 off, 1..4 that many
   int opt_xframe = 1;                 // uncontrolled X gates inside a pass become an XOR on its store addresses
   int opt_trace_passes = 0;           // 1: one stderr line per k_multi pass (R, mode, ops by update shape) -- a diagnostic
@@ -248,8 +276,9 @@ static unsigned grid_for(const qsv_handle* h, const Shard& s, uint64_t work, uin
   return (unsigned)std::min<uint64_t>(std::min(need, cap), (1ull << 24) - 1ull);
 }
 
-// device copy of a small host table, asynchronous on the shard stream
-static int arena_put(Shard& s, const void* src, size_t bytes, void** dptr) {
+// device copy of a small host table, asynchronous on the shard stream: into the arena, or (dst != NULL) staged through
+// the arena's pinned half into a device buffer of the caller's
+static int arena_put(Shard& s, const void* src, size_t bytes, void** dptr, void* dst = nullptr) {
   const size_t slot = (bytes + 255) & ~size_t(255);
   if (slot > s.arena_bytes) return fail(QSV_E_BADARG, "table of %zu bytes exceeds arena", bytes);
   if (s.arena_top + slot > s.arena_bytes) {
@@ -257,9 +286,9 @@ static int arena_put(Shard& s, const void* src, size_t bytes, void** dptr) {
     s.arena_top = 0;
   }
   memcpy(s.h_arena + s.arena_top, src, bytes);
-  HIPCHK(hipMemcpyAsync(s.d_arena + s.arena_top, s.h_arena + s.arena_top, bytes,
-                        hipMemcpyHostToDevice, s.stream));
-  *dptr = s.d_arena + s.arena_top;
+  void* d = dst ? dst : s.d_arena + s.arena_top;
+  HIPCHK(hipMemcpyAsync(d, s.h_arena + s.arena_top, bytes, hipMemcpyHostToDevice, s.stream));
+  *dptr = d;
   s.arena_top += slot;
   return QSV_OK;
 }
@@ -298,7 +327,7 @@ static int launch(qsv_handle* h, Shard& s, int kind, double bytes, F&& f) {
   }
   f();
   HIPCHK(hipGetLastError());
-  if (kind != QSV_K_PROB) { s.sums_valid = false; s.tile_valid = false; s.h_tsums_valid = false; }   // any state change drops cached sums
+  if (kind != QSV_K_PROB) { s.sums_valid = false; s.tile_valid = false; s.h_tsums_valid = false; s.deferred = false; }   // any state change drops cached sums (and whoever changes a deferred state has realised it, or overwrites it)
   if (h->profiling) {
     HIPCHK(hipEventRecord(p.e1, s.stream));
     s.pending.push_back(p);
@@ -308,6 +337,9 @@ static int launch(qsv_handle* h, Shard& s, int kind, double bytes, F&& f) {
   h->stats.per_kind[kind].algorithmic_bytes += bytes;
   return QSV_OK;
 }
+
+// a deferred shard gets its amplitudes written (qsv_multi.inc); a no-op on any other shard
+static int realize(qsv_handle* h, Shard& s);
 
 // ------------------------------------------------------------------------------------------
 // life cycle
@@ -407,6 +439,7 @@ extern "C" int qsv_destroy(qsv_handle* h) {
     if (s.d_tsums) hipFree(s.d_tsums);
     if (s.d_red) hipFree(s.d_red);
     if (s.d_noisy) hipFree(s.d_noisy);
+    if (s.recipe.d_buf) hipFree(s.recipe.d_buf);
     if (s.ev_copied) hipEventDestroy(s.ev_copied);
     if (s.ev_ready) hipEventDestroy(s.ev_ready);
     if (s.h_tsums) hipHostFree(s.h_tsums);
@@ -501,6 +534,7 @@ extern "C" int qsv_ipc_export(qsv_handle* h, uint8_t out[QSV_IPC_HANDLE_BYTES]) 
   if (!h || !out) return fail(QSV_E_BADARG, "NULL argument");
   static_assert(sizeof(hipIpcMemHandle_t) <= QSV_IPC_HANDLE_BYTES, "hipIpcMemHandle_t size");
   CHK(shard_set(h->shards[0]));
+  CHK(realize(h, h->shards[0]));                    // a peer reads this memory behind the engine's bookkeeping
   hipIpcMemHandle_t hd;
   HIPCHK(hipIpcGetMemHandle(&hd, h->shards[0].amp));
   memset(out, 0, QSV_IPC_HANDLE_BYTES);
@@ -688,7 +722,14 @@ extern "C" int qsv_init_zero(qsv_handle* h) { return qsv_init_uniform(h, 0ull); 
 // zero there (zero tracking; the generator as a program's last pass, option implied_zeros).  Every entry point that reads
 // the shard, or writes part of it, either honours zmask or calls this first: it writes those zeros (k_fill_zero).  The
 // state does not change, so the cached block / tile sums stay valid.
+// A deferred shard (Shard::deferred) is realised first: the writing generator runs from the recipe (realize, qsv_multi.inc),
+// after which zmask is what that launch leaves.
+static int realize_all(qsv_handle* h) {
+  for (Shard& s : h->shards) CHK(realize(h, s));
+  return QSV_OK;
+}
 static int materialize(qsv_handle* h, Shard& s) {
+  CHK(realize(h, s));
   if (!s.zmask) return QSV_OK;
   const uint64_t n = amps_local(h);
   const uint64_t zm = s.zmask;

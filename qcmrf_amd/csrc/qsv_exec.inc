@@ -143,7 +143,7 @@ extern "C" int qsv_exec(qsv_handle* h, const qsv_op* ops, int n_ops, const doubl
   h->exec_ops_left = 1 << 30;
   CHK(flush_all(true));
   for (Shard& s : h->shards) {
-    if (!h->opt_implied_zeros) CHK(materialize(h, s));   // else the zero region stays implied (s.zmask, materialize)
+    if (!h->opt_implied_zeros && !s.deferred) CHK(materialize(h, s));   // else the zero region stays implied (s.zmask, materialize); a deferred state has no implied zeros without the option
     s.tile_valid = s.tile_fresh;
     s.tile_fresh = false;
   }
@@ -476,6 +476,15 @@ extern "C" int qsv_get_stats(qsv_handle* h, qsv_stats* out) {
   *out = h->stats;
   return QSV_OK;
 }
+extern "C" int qsv_state_info(qsv_handle* h, int* deferred, uint64_t* realize_calls, uint64_t* listed_launches) {
+  if (!h) return fail(QSV_E_BADARG, "NULL handle");
+  int d = 0;
+  for (const Shard& s : h->shards) d |= s.deferred ? 1 : 0;
+  if (deferred) *deferred = d;
+  if (realize_calls) *realize_calls = h->n_realize;
+  if (listed_launches) *listed_launches = h->n_listed;
+  return QSV_OK;
+}
 extern "C" int qsv_timer_begin(qsv_handle* h) {
   if (!h) return fail(QSV_E_BADARG, "NULL handle");
   Shard& s = h->shards[0];
@@ -519,6 +528,7 @@ extern "C" int qsv_set_option(qsv_handle* h, const char* name, int value) {
   else if (!strcmp(name, "multi_nt")) h->opt_multi_nt = value;
   else if (!strcmp(name, "init_prod_nt")) h->opt_init_prod_nt = value;
   else if (!strcmp(name, "init_prod_grid")) { if (value < 0) return fail(QSV_E_BADARG, "init_prod_grid < 0"); h->opt_init_prod_grid = value; }
+  else if (!strcmp(name, "defer_state")) { if (value < -1 || value > 1) return fail(QSV_E_BADARG, "defer_state must be -1 (auto), 0 or 1"); h->opt_defer_state = value; }
   else if (!strcmp(name, "init_prod_group")) { if (value < -1 || value > QSV_PROD_MAXG) return fail(QSV_E_BADARG, "init_prod_group must be -1 (auto) or 0..4"); h->opt_init_prod_group = value; }
   else if (!strcmp(name, "pass_max_ops")) { if (value < 1 || value > 512) return fail(QSV_E_BADARG, "pass_max_ops out of range"); h->opt_pass_max_ops = value; }
   else if (!strcmp(name, "single_shortcut")) h->opt_single_shortcut = value != 0;

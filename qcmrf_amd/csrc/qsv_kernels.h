@@ -683,6 +683,10 @@ __global__ __launch_bounds__(QSV_TPB) void k_reduce_pairs(const double* __restri
 // A[0] starts from P0 and a[j] = A[j], the product order of the one-tile-per-workgroup generator.  So the order of an
 // amplitude's products depends on its position and the group bits only, never on the grid or the walk; tiles keep
 // their index and their sums their reduction order.  Tile sums: two LDS buffers, one barrier per group.
+// FORM: QSV_GEN_WRITE is the generator as described.  QSV_GEN_SUMS drops the stores and their address arithmetic and
+// keeps everything that feeds the tile sums instruction for instruction: the sums are bit-identical, the shard's
+// memory is untouched (the state is deferred).  QSV_GEN_LISTED stores the tiles of a list (the tiles the sampler's
+// shots fall into) at their real addresses, with the products in group order, and leaves no sums.
 // ZR >= 0: the implied-zero register bits zreg as a compile-time constant (the top register bit as at 34 qubits: the
 // zero half of the register tile costs nothing); ZR < 0: zreg at run time.
 // ---------------------------------------------------------------------------------------
@@ -715,12 +719,17 @@ __device__ __forceinline__ uint32_t prod_gather_wave(uint32_t wi, const uint32_t
   return nl <= 4 ? prod_gather_wave<4>(wi, wb) : prod_gather_wave<QSV_MULTI_MAXLIST>(wi, wb);   // uniform branch
 }
 
-template <int R, bool NT, int ZR>
+// the three forms of the generator: every amplitude stored | no amplitude stored, tile sums only (the
+// state is deferred: the shard keeps the recipe) | the tiles of a sorted list stored, no sums (the sampler)
+enum { QSV_GEN_WRITE = 0, QSV_GEN_SUMS = 1, QSV_GEN_LISTED = 2 };
+
+template <int R, bool NT, int ZR, int FORM>
 __global__ __launch_bounds__(QSV_TPB) void k_init_prod(cplx* __restrict__ amp, uint64_t ntiles, BitIns ins, RegPos rp,
                                                        LanePos lp, const ProdFactor* __restrict__ fac, ProdCounts cnt,
                                                        ProdGroup grp, const cplx* __restrict__ tables, int ntab,
                                                        uint64_t nonmask, double initval, double* __restrict__ tile_sums,
-                                                       uint64_t zskip, unsigned zreg_arg) {
+                                                       uint64_t zskip, unsigned zreg_arg,
+                                                       const uint64_t* __restrict__ list, uint64_t nlist) {
   constexpr int NWB = (QSV_MULTI_MAXLIST + 3) / 4;
   static_assert(NWB == 3, "a factor descriptor holds 12 wave-index bit bytes");
   const unsigned zreg = ZR >= 0 ? (unsigned)ZR : zreg_arg;
@@ -799,10 +808,26 @@ __global__ __launch_bounds__(QSV_TPB) void k_init_prod(cplx* __restrict__ amp, u
   uint64_t base_blk = tile_base_blk(tile0, ins, lp);
   __shared__ double wpart[2][1 << QSV_PROD_MAXG][QSV_TPB / 64];
   int par = 0;
-  for (uint64_t gi = blockIdx.x; gi < ngroups; gi += gridDim.x, tile0 = ((tile0 | tholes) + dtile) & ~tholes,
-                                                                base_blk = ((base_blk | holes) + dblk) & ~holes) {
+  // QSV_GEN_LISTED: the walk is over the list instead, one workgroup per entry, each taking the whole group its tile
+  // belongs to (the product order is the group order) and storing that one tile.  The list is non-decreasing: an entry
+  // equal to its predecessor is skipped (that workgroup stores the tile once for all of them); two different tiles of
+  // one group are two walks over that group, each storing its own tile.
+  constexpr bool LISTED = FORM == QSV_GEN_LISTED;
+  uint32_t bsel = 0;
+  for (uint64_t gi = blockIdx.x; gi < (LISTED ? nlist : ngroups);
+       gi += gridDim.x, tile0 = LISTED ? tile0 : ((tile0 | tholes) + dtile) & ~tholes,
+                        base_blk = LISTED ? base_blk : ((base_blk | holes) + dblk) & ~holes) {
+    if constexpr (LISTED) {
+      const uint64_t t = list[gi];
+      if (t >= ntiles || (gi && list[gi - 1] == t)) continue;
+      tile0 = t & ~tholes;
+      base_blk = tile_base_blk(tile0, ins, lp);
+      bsel = 0;
+#pragma unroll
+      for (int i = 0; i < QSV_PROD_MAXG; ++i) if (t & gt[i]) bsel |= 1u << i;
+    }
     if (base_blk & zskip) {                        // the whole group is implied zero (uniform: no barrier crossed)
-      if (tile_sums && (int)threadIdx.x < nsub) tile_sums[tile0 | sub(gt, threadIdx.x)] = 0.0;
+      if (!LISTED && tile_sums && (int)threadIdx.x < nsub) tile_sums[tile0 | sub(gt, threadIdx.x)] = 0.0;
       continue;
     }
     // wave-uniform parts of the group's first tile: lane k holds factor k's (and k + 64's) table offset, in bytes
@@ -891,22 +916,24 @@ __global__ __launch_bounds__(QSV_TPB) void k_init_prod(cplx* __restrict__ amp, u
               for (int c = 0; c < R; ++c) if ((j >> c) & 1) jr += pf.regw[c];
               a = cmul(a, ldt(entry(gb0, gb1, k) + (uint32_t)jr * sizeof(cplx)));
             }
-          uint64_t off = 0;
+          if constexpr (FORM != QSV_GEN_SUMS) {
+            uint64_t off = 0;
 #pragma unroll
-          for (int c = 0; c < R; ++c) if ((j >> c) & 1) off |= ob[c];
-          if (store) { if (NT) st_nt((pblk + off) + base_thr, a); else (pblk + off)[base_thr] = a; }
+            for (int c = 0; c < R; ++c) if ((j >> c) & 1) off |= ob[c];
+            if (LISTED ? (store && (uint32_t)b == bsel) : store) { if (NT) st_nt((pblk + off) + base_thr, a); else (pblk + off)[base_thr] = a; }
+          }
           psum = fma(a.x, a.x, fma(a.y, a.y, psum));
         }
       };
       if (cnt.nmixed) stores(std::true_type{}, std::true_type{});          // mixed factors exist with group bits only
       else if (grp.nb) stores(std::true_type{}, std::false_type{});
       else stores(std::false_type{}, std::false_type{});
-      if (tile_sums) {
+      if (!LISTED && tile_sums) {
         psum = wave_sum(psum);
         if (lane == 0) wpart[par][b][wave] = psum;
       }
     }
-    if (tile_sums) {                               // two buffers: one barrier per group orders both uses of one
+    if (!LISTED && tile_sums) {                    // two buffers: one barrier per group orders both uses of one
       __syncthreads();
       const int t = threadIdx.x;
       if (t < nsub)

@@ -157,6 +157,15 @@ extern "C" int qsv_sample(qsv_handle* h, uint64_t shots, uint64_t seed, const in
                            sh.d_tsums, sh.tile_nblocks, sh.d_sblk, sh.d_sres, cnt);
         HIPCHK(hipGetLastError());
       }
+      if (bs.super && sh.deferred) {
+        // Deferred state: d_sblk now holds each shot's tile.  One launch of the generator's listed form stores exactly
+        // those tiles at their real addresses (a tile listed several times once: the list is non-decreasing and an entry
+        // equal to its predecessor is skipped); k_locate_tile then reads what the writing form would have stored.  Part
+        // of sampling: like k_locate_*, not booked as a sweep.
+        CHK(launch_recipe(h, sh, QSV_GEN_LISTED, sh.d_sblk, cnt));
+        HIPCHK(hipGetLastError());
+        h->n_listed += 1;
+      }
       if (bs.super) {                     // tile order of the program's last pass
         const dim3 g((unsigned)std::min<uint64_t>(cnt, 65535));
 #define LT(RR) hipLaunchKernelGGL((k_locate_tile<RR>), g, dim3(QSV_TPB), 0, sh.stream, sh.amp, sh.tile_ins, sh.tile_rp, sh.tile_lp, sh.d_sblk, sh.d_sres, sh.d_sout, cnt, sh.tile_xor, sh.zmask)
@@ -316,6 +325,7 @@ static int amp_copy(qsv_handle* h, uint64_t start, uint64_t count, double* out, 
     const uint64_t off = g & (n - 1);
     const uint64_t m = std::min(count - done, n - off);
     CHK(shard_set(*sh));
+    if (out) CHK(realize(h, *sh));        // a deferred state is written before it is read (the write path: materialize below)
     HIPCHK(hipStreamSynchronize(sh->stream));
     if (out) {
       HIPCHK(hipMemcpy(out + 2 * done, sh->amp + off, m * sizeof(cplx), hipMemcpyDeviceToHost));
@@ -353,6 +363,8 @@ extern "C" int qsv_copy_state(qsv_handle* dst, qsv_handle* src) {
     if (a.index != b.index) return fail(QSV_E_BADARG, "qsv_copy_state: shard order differs");
     // destination after source, source after the copy: two events, no host round trip
     CHK(shard_set(a));
+    CHK(realize(src, a));                 // the copy reads the whole source shard; the destination's old state, deferred or not, is gone
+    b.deferred = false;
     if (!a.ev_ready) HIPCHK(hipEventCreateWithFlags(&a.ev_ready, hipEventDisableTiming));
     HIPCHK(hipEventRecord(a.ev_ready, a.stream));
     CHK(shard_set(b));

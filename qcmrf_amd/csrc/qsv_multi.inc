@@ -202,11 +202,12 @@ static bool group_is_init_product(const qsv_handle* h, const PendingGroup& g) {
 }
 
 #define QSV_GEN_NT_MIN_L 30
-template <int R, bool NT, int ZR>
+#define QSV_DEFER_MIN_L 30        // option defer_state = -1: local qubits from which the final generator leaves sums only (DESIGN §5e)
+template <int R, bool NT, int ZR, int FORM>
 static int launch_init_prod_k(const qsv_handle* h, const Shard& s, uint64_t ntiles, const BitIns& ins, const RegPos& rp,
                               const LanePos& lp, const ProdFactor* f, const ProdCounts& cnt, const ProdGroup& grp,
                               const cplx* tab, int ntab, uint64_t nonmask, double initval, double* tsums, uint64_t zskip,
-                              unsigned zreg) {
+                              unsigned zreg, const uint64_t* list, uint64_t nlist) {
   // persistent grid: every workgroup the chip holds at once at this kernel's occupancy (option init_prod_grid: fewer)
   const size_t lds = (size_t)ntab * sizeof(cplx) + (size_t)cnt.nfac * (16 + 64 * sizeof(uint16_t)) +
                      (grp.nb ? ((size_t)cnt.nfac << grp.nb) * sizeof(uint16_t) : 0);
@@ -215,7 +216,7 @@ static int launch_init_prod_k(const qsv_handle* h, const Shard& s, uint64_t ntil
   auto it = occupancy.find(lds);
   if (it == occupancy.end()) {
     int per_cu = 0;
-    HIPCHK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, reinterpret_cast<const void*>(&k_init_prod<R, NT, ZR>),
+    HIPCHK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, reinterpret_cast<const void*>(&k_init_prod<R, NT, ZR, FORM>),
                                                         QSV_TPB, std::max<size_t>(lds, 16)));
     it = occupancy.emplace(lds, per_cu).first;
   }
@@ -223,26 +224,69 @@ static int launch_init_prod_k(const qsv_handle* h, const Shard& s, uint64_t ntil
   if (per_cu < 1) return fail(QSV_E_UNSUPPORTED, "k_init_prod does not fit a CU (%zu B of LDS)", lds);
   uint64_t grid = (uint64_t)per_cu * (uint64_t)s.n_cu;
   if (h->opt_init_prod_grid > 0) grid = std::min<uint64_t>(grid, (uint64_t)h->opt_init_prod_grid);
-  grid = std::min(grid, ntiles >> grp.nb);        // one workgroup per group at most
-  hipLaunchKernelGGL((k_init_prod<R, NT, ZR>), dim3((unsigned)grid), dim3(QSV_TPB), std::max<size_t>(lds, 16), s.stream,
-                     s.amp, ntiles, ins, rp, lp, f, cnt, grp, tab, ntab, nonmask, initval, tsums, zskip, zreg);
+  if (FORM == QSV_GEN_LISTED) grid = std::max<uint64_t>(1, std::min(grid, nlist));   // one workgroup per entry, grid-stride beyond
+  else grid = std::min(grid, ntiles >> grp.nb);   // one workgroup per group at most
+  hipLaunchKernelGGL((k_init_prod<R, NT, ZR, FORM>), dim3((unsigned)grid), dim3(QSV_TPB), std::max<size_t>(lds, 16), s.stream,
+                     s.amp, ntiles, ins, rp, lp, f, cnt, grp, tab, ntab, nonmask, initval, tsums, zskip, zreg, list, nlist);
   return QSV_OK;
 }
 template <int R>
-static int launch_init_prod(const qsv_handle* h, const Shard& s, uint64_t ntiles, const BitIns& ins, const RegPos& rp, const LanePos& lp,
+static int launch_init_prod(const qsv_handle* h, const Shard& s, int form, uint64_t ntiles, const BitIns& ins, const RegPos& rp, const LanePos& lp,
                             const ProdFactor* f, const ProdCounts& cnt, const ProdGroup& grp, const cplx* tab, int ntab,
-                            uint64_t nonmask, double initval, double* tsums, uint64_t zskip, unsigned zreg) {
+                            uint64_t nonmask, double initval, double* tsums, uint64_t zskip, unsigned zreg,
+                            const uint64_t* list = nullptr, uint64_t nlist = 0) {
   // non-temporal stores pay on big shards (34 qubits: 6.86 -> 7.11 TB/s; 28 qubits: -1 %; profiles/r02_nt_variants.log)
   const bool nt = h->opt_nt > 0 || (h->opt_init_prod_nt < 0 && h->L >= QSV_GEN_NT_MIN_L) || h->opt_init_prod_nt > 0;
   // the top register bit as the only implied-zero register bit (the layout at 34 qubits) is a compile-time case; any
   // other zreg, none included, is read at run time (a compile-time zreg = 0 took 127 registers at R = 4 against 109
   // and wrote the full state 8 % slower)
   constexpr int ZTOP = 1 << (R - 1);
-#define QSV_LIP(NT, ZR) return launch_init_prod_k<R, NT, ZR>(h, s, ntiles, ins, rp, lp, f, cnt, grp, tab, ntab, nonmask, initval, tsums, zskip, zreg)
-  if (nt) { if (zreg == ZTOP) QSV_LIP(true, ZTOP); QSV_LIP(true, -1); }
-  if (zreg == ZTOP) QSV_LIP(false, ZTOP);
-  QSV_LIP(false, -1);
+#define QSV_LIP(NT, ZR, FORM) return launch_init_prod_k<R, NT, ZR, FORM>(h, s, ntiles, ins, rp, lp, f, cnt, grp, tab, ntab, nonmask, initval, tsums, zskip, zreg, list, nlist)
+  // the sums-only form stores nothing and the listed form a few tiles that k_locate_tile reads next: one instantiation
+  // per (R, ZR) each, whatever the non-temporal choice of the writing form
+  if (form == QSV_GEN_SUMS) { if (zreg == ZTOP) QSV_LIP(false, ZTOP, QSV_GEN_SUMS); QSV_LIP(false, -1, QSV_GEN_SUMS); }
+  if (form == QSV_GEN_LISTED) { if (zreg == ZTOP) QSV_LIP(false, ZTOP, QSV_GEN_LISTED); QSV_LIP(false, -1, QSV_GEN_LISTED); }
+  if (nt) { if (zreg == ZTOP) QSV_LIP(true, ZTOP, QSV_GEN_WRITE); QSV_LIP(true, -1, QSV_GEN_WRITE); }
+  if (zreg == ZTOP) QSV_LIP(false, ZTOP, QSV_GEN_WRITE);
+  QSV_LIP(false, -1, QSV_GEN_WRITE);
 #undef QSV_LIP
+}
+
+// the generator from a shard's recipe: the writing form (realize) or the listed form (qsv_sample)
+static int launch_recipe(const qsv_handle* h, const Shard& s, int form, const uint64_t* list, uint64_t nlist) {
+  const GenRecipe& rc = s.recipe;
+#define QSV_LR(RR) return launch_init_prod<RR>(h, s, form, rc.ntiles, rc.ins, rc.rp, rc.lp, rc.dfac, rc.cnt, rc.grp, rc.dtab, rc.ntab, rc.nonmask, rc.initval, nullptr, rc.zskip, rc.zreg, list, nlist)
+  switch (rc.R) {
+    case 3: QSV_LR(3);
+    case 4: QSV_LR(4);
+    case 5: QSV_LR(5);
+    case 6: QSV_LR(6);
+    default: return fail(QSV_E_HIP, "deferred state without a recipe");
+  }
+#undef QSV_LR
+}
+
+// A deferred shard gets its amplitudes: the writing generator on the recipe the sums-only launch ran with, the
+// instantiation the engine's options choose for a writing launch.  The state does not change, so -- as in materialize --
+// the cached sums stay valid.  Booked under init_prod with the 16 B of every amplitude stored; afterwards zmask is what
+// a writing final pass leaves (it was set when the state was deferred).
+static int realize(qsv_handle* h, Shard& s) {
+  if (!s.deferred) return QSV_OK;
+  const uint64_t n = amps_local(h);
+  CHK(shard_set(s));
+  const bool sv = s.sums_valid, tv = s.tile_valid, hv = s.h_tsums_valid;
+  int lr = QSV_OK;
+  const int r = launch(h, s, QSV_K_INIT_PROD, 16.0 * (double)(n >> __builtin_popcountll(s.recipe.zskip)), [&] {
+    lr = launch_recipe(h, s, QSV_GEN_WRITE, nullptr, 0);
+  });
+  CHK(lr);
+  CHK(r);
+  s.deferred = false;
+  s.sums_valid = sv;
+  s.tile_valid = tv;
+  s.h_tsums_valid = hv;
+  h->n_realize += 1;
+  return QSV_OK;
 }
 
 template <int R>
@@ -364,10 +408,6 @@ static int flush_init_product_r(qsv_handle* h, Shard& s, PendingGroup& g, bool f
   uni.insert(uni.end(), mixed.begin(), mixed.end());
   cnt.nfac = (int)uni.size();
   cnt.nlmax = nlmax;
-  void* dfac = nullptr;
-  void* dtab = nullptr;
-  CHK(arena_put(s, uni.data(), uni.size() * sizeof(ProdFactor), &dfac));
-  CHK(arena_put(s, tables.data(), tables.size() * sizeof(double), &dtab));
   const int ntab = (int)(tables.size() / 2);
   const uint64_t nthreads = n >> R;
   double* tsums = nullptr;
@@ -394,14 +434,43 @@ static int flush_init_product_r(qsv_handle* h, Shard& s, PendingGroup& g, bool f
   unsigned zreg = 0;
   for (int c = 0; c < R; ++c) if ((zskip >> rp.pos[c]) & 1ull) zreg |= 1u << c;
   s.zmask = zskip;
+  // Deferred state (option defer_state): as the program's last pass, leaving tile sums, the generator stores nothing.
+  // The step's result needs the sums and the tiles its shots fall into (qsv_sample stores those); whoever reads the
+  // state later calls realize().  The descriptors and tables then go to the shard's recipe buffer, not to the arena.
+  const bool defer = tsums != nullptr && (h->opt_defer_state > 0 || (h->opt_defer_state < 0 && h->L >= QSV_DEFER_MIN_L));
+  const size_t fbytes = (uni.size() * sizeof(ProdFactor) + 255) & ~size_t(255);
+  const size_t tbytes = tables.size() * sizeof(double);
+  void* dfac = nullptr;
+  void* dtab = nullptr;
+  if (defer) {
+    GenRecipe& rc = s.recipe;
+    if (rc.cap < fbytes + tbytes) {
+      if (rc.d_buf) { HIPCHK(hipStreamSynchronize(s.stream)); HIPCHK(hipFree(rc.d_buf)); }
+      rc.d_buf = nullptr;
+      rc.cap = 0;
+      const size_t cap = std::max<size_t>(fbytes + tbytes, 64u << 10);
+      HIPCHK(hipMalloc(&rc.d_buf, cap));
+      rc.cap = cap;
+    }
+    CHK(arena_put(s, uni.data(), uni.size() * sizeof(ProdFactor), &dfac, rc.d_buf));
+    CHK(arena_put(s, tables.data(), tbytes, &dtab, rc.d_buf + fbytes));
+    rc.R = R; rc.ntiles = ntiles; rc.ins = ins; rc.rp = rp; rc.lp = lp; rc.cnt = cnt; rc.grp = grp; rc.ntab = ntab;
+    rc.nonmask = nonmask; rc.zskip = zskip; rc.initval = g.initval; rc.zreg = zreg;
+    rc.dfac = reinterpret_cast<const ProdFactor*>(dfac);
+    rc.dtab = reinterpret_cast<const cplx*>(dtab);
+  } else {
+    CHK(arena_put(s, uni.data(), uni.size() * sizeof(ProdFactor), &dfac));
+    CHK(arena_put(s, tables.data(), tbytes, &dtab));
+  }
   h->stats.fused_gates += g.ops.size();
   const double initval = g.initval;
   int lr = QSV_OK;
-  const int r = launch(h, s, QSV_K_INIT_PROD, 16.0 * (double)(n >> __builtin_popcountll(zskip)), [&] {
-    lr = launch_init_prod<R>(h, s, ntiles, ins, rp, lp, reinterpret_cast<const ProdFactor*>(dfac), cnt, grp,
+  const int r = launch(h, s, QSV_K_INIT_PROD, defer ? 0.0 : 16.0 * (double)(n >> __builtin_popcountll(zskip)), [&] {
+    lr = launch_init_prod<R>(h, s, defer ? QSV_GEN_SUMS : QSV_GEN_WRITE, ntiles, ins, rp, lp, reinterpret_cast<const ProdFactor*>(dfac), cnt, grp,
                              reinterpret_cast<const cplx*>(dtab), ntab, nonmask, initval, tsums, zskip, zreg);
   });
   CHK(lr);
+  s.deferred = defer && r == QSV_OK;
   s.tile_fresh = tsums != nullptr;
   g = PendingGroup();
   return r;

@@ -114,7 +114,7 @@ def run(n_cases=300, seed=7, verbose=True, only=None, override=None, widths=(14,
                 "pass_max_ops": int(rs.choice([64, 64, 8, 200])), "swizzle": int(rs.choice([1, 2, 2, 0])),
                 "lane_map_min_l": int(rs.choice([26, 14, 14])),
                 "kq_variant": int(rs.choice([-1, -1, 0, 3, 5, 6, 8])), "kq_order": int(rs.choice([1, 1, 0, 2, 4])),
-                "kq3_tile": int(rs.choice([1, 1, 0, 2]))}
+                "kq3_tile": int(rs.choice([1, 1, 0, 2])), "defer_state": int(rs.choice([-1, 1, 1, 0]))}
         if only is not None and (case != only if only >= 0 else case < -only):
             continue                                       # replay mode (CASE, or -CASE: from that case on): the generator state advances, nothing runs
         if override:
