@@ -218,6 +218,33 @@ int qsv_set_amplitudes(qsv_handle* h, uint64_t start, uint64_t count, const doub
  * trajectory mode: the mid-circuit measure of QCMRF.py:238-239 taken when it occurs. */
 int qsv_copy_state(qsv_handle* dst, qsv_handle* src);
 
+/* ---- slots: the branches of one level of a trajectory run, side by side ------------- */
+
+/* A slot is an aligned block of 2^w amplitudes of a single-shard, single-process handle of W >= w qubits: slot b starts at
+ * amplitude b << w (the branch number rides on the qubits >= w, so one qsv_exec of gates on qubits < w evolves every slot
+ * alike, and an all-zero slot stays zero).  Handles of several shards or ranks return QSV_E_BADARG.  Both entries realise a
+ * deferred state and write implied zeros before they read (qsv_state_info).
+ *
+ * qsv_branch_mass: out[2b] = sum |amp|^2 over slot b with bit `qubit` = 0, out[2b+1] the same with the bit = 1, for
+ * b < n_slots (0 <= qubit < w, 1 <= n_slots <= 2^(W-w); out holds 2 n_slots doubles).  One read pass over n_slots << w
+ * amplitudes, no atomics, one copy and one stream synchronisation; the partial sums live in the shard's reduction scratch,
+ * which is kept between calls up to 2^24 doubles -- a call that needs more (2 n_slots + 2 (n_slots << w) / 1024 doubles for
+ * w > 10, e.g. all 8192 slots of w = 20 in W = 33) allocates and frees its scratch itself.  The two sums of a slot are a pure function of (w, qubit,
+ * the slot's contents): the same bits whatever n_slots, the slot's position, W or the grid (the tree of additions is
+ * spelled out in qsv_branch.hip).  Booked under QSV_K_PROB. */
+int qsv_branch_mass(qsv_handle* h, int w, uint64_t n_slots, int qubit, double* out /* 2 * n_slots */);
+
+/* qsv_branch_split: slot c of dst, c < n_children, becomes slot parent[c] of src projected on bit `qubit` == outcome[c]:
+ * the kept amplitudes bit for bit, the other half zero.  With release != 0 a kept half of outcome 1 is stored at bit
+ * `qubit` = 0 instead (the projection followed by X: the measured qubit handed back in |0>).  Every further slot of dst, up
+ * to 2^(W_dst - w), is written zero.  dst != src, both on one device; W_dst and W_src may differ, each >= w (W_dst = w with
+ * one child extracts a branch into an ordinary state); 1 <= n_children <= 2^(W_dst - w), parent[c] < 2^(W_src - w), a parent
+ * may occur any number of times.  One pass: reads the kept halves, writes all of dst, which afterwards is a plainly stored
+ * state.  Runs on dst's stream, ordered after everything asked of src so far, and src's stream waits for it as in
+ * qsv_copy_state: src may be reused at once.  Booked under QSV_K_SWAP of dst. */
+int qsv_branch_split(qsv_handle* dst, qsv_handle* src, int w, uint64_t n_children, const uint32_t* parent,
+                     const uint8_t* outcome, int qubit, int release);
+
 /* ---- batched execution -------------------------------------------------------------- */
 
 enum {

@@ -86,6 +86,8 @@ SIGNATURES = {
     "qsv_get_amplitudes": (_i, [_vp, _u64, _u64, _dp]),
     "qsv_set_amplitudes": (_i, [_vp, _u64, _u64, _dp]),
     "qsv_copy_state": (_i, [_vp, _vp]),
+    "qsv_branch_mass": (_i, [_vp, _i, _u64, _i, _dp]),
+    "qsv_branch_split": (_i, [_vp, _vp, _i, _u64, _P(C.c_uint32), _P(C.c_uint8), _i, _i]),
     "qsv_exec": (_i, [_vp, _vp, _i, _dp, _u64]),
     "qsv_noisy_sample": (_i, [_vp, _vp, _i, _dp, _u64, _u64, _u64, _ip, _i, _dp, _u64p]),
     "qsv_noisy_sample_hbm": (_i, [_vp, _vp, _i, _dp, _u64, _u64, _u64, _ip, _i, _dp, _u64p]),
@@ -464,6 +466,23 @@ class Engine:
     def copy_from(self, other):
         """device-to-device copy of another engine's state (same shape)"""
         _chk(self._lib.qsv_copy_state(self._h, other._h))
+
+    # -- slots: aligned blocks of 2^w amplitudes, the branches of one level of a trajectory run (qcmrf_amd.trajectory)
+    def branch_mass(self, w, n_slots, qubit):
+        """(n_slots, 2) float64: per slot the sums of |amp|^2 with bit ``qubit`` 0 and 1 (qsv_branch_mass)"""
+        out = np.zeros((int(n_slots), 2), dtype=np.float64)
+        _chk(self._lib.qsv_branch_mass(self._h, int(w), int(n_slots), int(qubit), out.ctypes.data_as(_dp)))
+        return out
+
+    def branch_split(self, src, w, parent, outcome, qubit, release):
+        """slot c of this engine <- slot parent[c] of ``src`` projected on bit ``qubit`` == outcome[c] (release: an outcome 1
+        lands on bit 0); every other slot zero (qsv_branch_split)"""
+        pa = np.ascontiguousarray(parent, dtype=np.uint32)
+        oa = np.ascontiguousarray(outcome, dtype=np.uint8)
+        if pa.ndim != 1 or pa.shape != oa.shape:
+            raise ValueError("branch_split needs one parent and one outcome per child (%d, %d)" % (pa.size, oa.size))
+        _chk(self._lib.qsv_branch_split(self._h, src._h, int(w), pa.size, pa.ctypes.data_as(_P(C.c_uint32)),
+                                        oa.ctypes.data_as(_P(C.c_uint8)), int(qubit), int(bool(release))))
 
     def set_amplitudes(self, start, values):
         v = np.ascontiguousarray(values, dtype=np.complex128)

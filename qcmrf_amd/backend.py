@@ -23,6 +23,7 @@ from . import _lib, ingest as _ingest, noise as _noise, passes, planner, program
 from .comm import SingleProcess
 
 _METHODS = ("statevector", "trajectory", "density_matrix")
+_WALKS = ("depth", "levels")
 _NOISY_STATES = ("lds", "hbm", "auto")
 DENSITY_MAX_CLBITS = 20       # method="density_matrix" returns 2^k probabilities over the k written classical bits
 
@@ -93,8 +94,12 @@ def _format_keys(values, counts, num_clbits, creg_sizes):
     """integer outcomes (bit c = classical bit c) -> Qiskit count keys, vectorised:
     one (keys x width) matrix of '0'/'1' bytes, decoded once and sliced"""
     w = max(num_clbits, 1)
-    values = np.ascontiguousarray(values, dtype=np.uint64)
-    if w <= 64:
+    wide = getattr(values, "dtype", None) == object  # registers past 64 bits: Python ints (trajectory mode)
+    if not wide:
+        values = np.ascontiguousarray(values, dtype=np.uint64)
+    if wide:
+        keys = [format(int(v), "0%db" % w) for v in values]
+    elif w <= 64:
         # big-endian bytes -> bits -> UCS4 code points '0'/'1', VIEWED as fixed-width strings: no
         # per-key conversion at all (an S -> U astype costs more than everything else here together)
         bits = np.unpackbits(values.astype(">u8").view(np.uint8).reshape(-1, 8), axis=1)[:, 64 - w:]
@@ -126,10 +131,20 @@ class QsvBackend:
     devices     HIP device id per shard owned by this process (repeat an id for virtual shards)
     method      'statevector' (default: all measurements deferred, one evolution, W qubits) |
                 'trajectory' (mid-circuit measurements taken when they occur, measured qubits
-                released: n+2 live qubits for a QCMRF circuit, see qcmrf_amd.trajectory) |
+                released: n+2 live qubits for a QCMRF circuit, see qcmrf_amd.trajectory; classical registers of any
+                width) |
                 'density_matrix' (the circuit under ``noise_model``, or ideal, evolved exactly as rho -> sum K rho K^dg in a
                 vector of 2W qubits: ``Result.get_probabilities()`` is the exact distribution over the written classical
                 bits, the counts are drawn from it; W <= 17, one process, <= 20 written classical bits)
+    trajectory_walk   (method 'trajectory') 'depth' (default: one engine per branch of the outcome tree, depth first) |
+                'levels' (the live branches of a level are the slots of one wider state: one program launch, one
+                ``qsv_branch_mass`` and one vectorised binomial draw per batch, one ``qsv_branch_split`` per run of children).
+                The two walks draw in different orders: for one seed their counts agree statistically, not shot by shot
+    trajectory_slots  (walk 'levels') branches of a batch at most, a power of two; None (default): 2^30 bytes worth, halved
+                while segments + 2 engines of that size exceed 80 % of the free device memory; counts are a function of
+                (circuit, shots, seed, fusion, resolved slots); a value that cannot fit is a MemoryError
+    trajectory_trace  (walk 'levels', per run call) a list that receives one record per measuring batch: (level, register bits,
+                shots, mass on 0, mass on 1, shots on 1), each per slot -- for tests that replay the draws
     comm        process group for one-process-per-GPU launches (qcmrf_amd.comm)
     gather_counts  'root' (default: rank 0 returns the merged counts, the other ranks an empty dict) | 'all'
     spmd_ingest    (multi-rank) each rank reads 1/N of the circuit's composite blocks, one all-gather completes the program
@@ -148,7 +163,8 @@ class QsvBackend:
         self._name = name
         self.options = {"fusion": 3, "layout": "auto", "devices": (0,), "comm": None, "device": 0,
                         "profile": False, "engine_options": None, "method": "statevector", "fold_fresh": True,
-                        "gather_counts": "root", "noise_model": None, "noisy_state": "lds"}
+                        "gather_counts": "root", "noise_model": None, "noisy_state": "lds",
+                        "trajectory_walk": None, "trajectory_slots": None, "trajectory_trace": None}
         self.options.update(options)
         self._engine = None
         self._engine_key = None
@@ -237,6 +253,16 @@ class QsvBackend:
         method = opts.get("method", "statevector")
         if method not in _METHODS:
             raise ValueError("unknown method %r; this backend runs %s" % (method, ", ".join(_METHODS)))
+        walk, tslots = opts.get("trajectory_walk"), opts.get("trajectory_slots")
+        if walk is not None and walk not in _WALKS:
+            raise ValueError("unknown trajectory_walk %r; the outcome tree is walked by %s" % (walk, " or ".join(map(repr, _WALKS))))
+        ttrace = opts.get("trajectory_trace")
+        if method != "trajectory" and (walk is not None or tslots is not None or ttrace is not None):
+            raise ValueError("trajectory_walk, trajectory_slots and trajectory_trace belong to method='trajectory', not method=%r" % (method,))
+        if ttrace is not None and walk != "levels":
+            raise ValueError("trajectory_trace records the batches of the walk by 'levels'; the walk by 'depth' has none")
+        if ttrace is not None and not isinstance(ttrace, list):
+            raise TypeError("trajectory_trace must be a list, not %s" % type(ttrace).__name__)
         state = opts.get("noisy_state", "lds")
         if state not in _NOISY_STATES:
             raise ValueError("unknown noisy_state %r; a noisy shot keeps its state in %s" % (state, ", ".join(_NOISY_STATES)))
@@ -491,11 +517,16 @@ class QsvBackend:
         t0 = time.perf_counter()
         vals, cnts, num_clbits, creg_sizes, meta = trajectory.run_trajectories(
             circuit, shots, seed, fusion=opts["fusion"], device=tuple(opts["devices"])[0],
-            engine_factory=self._engine_factory)
+            engine_factory=self._engine_factory, walk=opts.get("trajectory_walk") or "depth",
+            slots=opts.get("trajectory_slots"), trace=opts.get("trajectory_trace"))
         agg = {}
         for v, c in zip(vals.tolist(), cnts.tolist()):
             agg[v] = agg.get(v, 0) + c
-        uv = np.fromiter(agg.keys(), dtype=np.uint64, count=len(agg))
+        if vals.dtype == object:
+            uv = np.empty(len(agg), dtype=object)
+            uv[:] = list(agg.keys())
+        else:
+            uv = np.fromiter(agg.keys(), dtype=np.uint64, count=len(agg))
         uc = np.fromiter(agg.values(), dtype=np.int64, count=len(agg))
         counts = _format_keys(uv, uc, num_clbits, creg_sizes) if len(agg) else {}
         meta.update({"n_qubits": int(circuit.num_qubits), "time_taken": time.perf_counter() - t0,

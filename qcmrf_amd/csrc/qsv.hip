@@ -5,6 +5,7 @@
 #include "qsv_kmulti_inst.h"
 #include "qsv_noise.h"
 #include "qsv_noise_hbm.h"
+#include "qsv_branch.h"
 #include "qsv_density.h"
 QSV_KMULTI_FOR_GENERAL(QSV_KMULTI_DECLARE)
 QSV_KMULTI_FOR_MODE(QSV_KMULTI_DECLARE, 1)
@@ -755,5 +756,6 @@ static int materialize_all(qsv_handle* h) {
 #include "qsv_multi.inc"     // PendingGroup, k_multi pass construction (round schedule, modes), zero tracking
 #include "qsv_layout.inc"    // qsv_apply_kq (VALU + MFMA), qsv_swap_layout: local swap and shard-bit exchange
 #include "qsv_measure.inc"   // qsv_norm / qsv_sample / qsv_probabilities / amplitude copies
+#include "qsv_branch.inc"    // qsv_branch_mass / qsv_branch_split: slots of a wide state (level-wise trajectory walk)
 #include "qsv_exec.inc"      // qsv_exec, stats, timers, options
 #include "qsv_density.inc"   // qsv_density_exec / _diagonal / _sample: the density-matrix method
