@@ -360,18 +360,26 @@ int qsv_reset_stats(qsv_handle* h);
 int qsv_get_stats(qsv_handle* h, qsv_stats* out);
 
 /* Deferred state (option defer_state).  A program whose last pass is the generator and leaves tile sums may store no
- * amplitude at all: the shard keeps the generator's recipe, qsv_sample stores the tiles its shots fall into, qsv_norm
+ * amplitude at all: only the sums kernel runs (it forms the sums from the factors' |.|^2 and touches no amplitude; the
+ * same kernel follows the writing generator when the state is not deferred, so the sums do not depend on the option),
+ * the shard keeps the generator's recipe, qsv_sample stores the tiles its shots fall into, qsv_norm
  * answers from the sums, and every other entry that reads or changes the state first has the generator write it
  * ("realises" it; booked under QSV_K_INIT_PROD with the bytes stored).  Entries that realise: qsv_get_amplitudes,
  * qsv_set_amplitudes, qsv_copy_state (source), qsv_probabilities*, qsv_expect_diag, qsv_apply_*, qsv_swap_layout (and
  * its exchanges), qsv_ipc_export, qsv_density_*, a qsv_exec that does not start with an init, and qsv_norm / qsv_sample
  * when they cannot use the tile sums (cache_sums or fused_sums 0).  Entries that do not: qsv_sample on the tile path,
- * qsv_norm from the cached sums, qsv_noisy_sample* (they keep their own states), stats, timers, options, qsv_sync.
+ * qsv_norm from the cached sums, qsv_tile_sums, qsv_noisy_sample* (they keep their own states), stats, timers, options, qsv_sync.
  * Deferred state ends with realisation or with the next init that writes; a program refused before its init writes
  * leaves the deferred state, recipe included, as it was.
  * deferred: 1 if a shard of this process is deferred; realize_calls / listed_launches: generator launches so far that
  * realised a shard / that stored a sampler's tile list.  Any out pointer may be NULL. */
 int qsv_state_info(qsv_handle* h, int* deferred, uint64_t* realize_calls, uint64_t* listed_launches);
+
+/* The per-tile sums of |amp|^2 the last pass of the last program left on local shard `shard` (fused_sums), in
+ * tile-index order: *n = their number; out (may be NULL: *n only) receives them when cap >= *n.  Read only: a deferred
+ * state stays deferred.  QSV_E_BADARG when that shard holds no valid tile sums (the state changed since, or its last
+ * pass left none). */
+int qsv_tile_sums(qsv_handle* h, int shard, double* out, uint64_t cap, uint64_t* n);
 
 /* HIP-event stopwatch on shard 0's stream: begin records, end records+synchronises */
 int qsv_timer_begin(qsv_handle* h);

@@ -101,6 +101,7 @@ SIGNATURES = {
     "qsv_timer_begin": (_i, [_vp]),
     "qsv_timer_end": (_i, [_vp, _dp]),
     "qsv_state_info": (_i, [_vp, _ip, _u64p, _u64p]),
+    "qsv_tile_sums": (_i, [_vp, _i, _dp, _u64, _u64p]),
     "qsv_set_option": (_i, [_vp, C.c_char_p, _i]),
     "qsv_last_error": (C.c_char_p, []),
     "qsv_version": (C.c_char_p, []),
@@ -513,6 +514,15 @@ class Engine:
         d, r, l = C.c_int(0), C.c_uint64(0), C.c_uint64(0)
         _chk(self._lib.qsv_state_info(self._h, C.byref(d), C.byref(r), C.byref(l)))
         return {"deferred": bool(d.value), "realize_calls": int(r.value), "listed_launches": int(l.value)}
+
+    def tile_sums(self, shard=0):
+        """float64 array: the per-tile |amp|^2 sums the last pass left on local shard ``shard``, in tile-index order
+        (qsv_tile_sums); raises when the shard holds none.  Reads the sums only: a deferred state stays deferred"""
+        n = C.c_uint64(0)
+        _chk(self._lib.qsv_tile_sums(self._h, int(shard), None, 0, C.byref(n)))
+        out = np.empty(int(n.value), dtype=np.float64)
+        _chk(self._lib.qsv_tile_sums(self._h, int(shard), out.ctypes.data_as(_dp), out.size, C.byref(n)))
+        return out
 
     def timer_begin(self):
         _chk(self._lib.qsv_timer_begin(self._h))

@@ -162,7 +162,7 @@ struct Shard {
   hipEvent_t ev_start = nullptr;
   int n_cu = 256;
   uint64_t zmask = 0;            // local bits known |0>: memory at an address with such a bit set is undefined (implied zeros, materialize)
-  // Deferred state (option defer_state): the last program's final pass was the sums-only generator.  amp then holds
+  // Deferred state (option defer_state): the last program's final pass was the generator's sums kernel alone (k_prod_sums).  amp then holds
   // nothing that may be read except the tiles the sampler stored; every other reader calls realize() first, which runs
   // the writing generator from the recipe.  Ends with realize() or the next write of an init.
   bool deferred = false;

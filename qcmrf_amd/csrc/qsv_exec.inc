@@ -485,6 +485,19 @@ extern "C" int qsv_state_info(qsv_handle* h, int* deferred, uint64_t* realize_ca
   if (listed_launches) *listed_launches = h->n_listed;
   return QSV_OK;
 }
+extern "C" int qsv_tile_sums(qsv_handle* h, int shard, double* out, uint64_t cap, uint64_t* n) {
+  if (!h || !n) return fail(QSV_E_BADARG, "NULL argument");
+  if (shard < 0 || shard >= (int)h->shards.size()) return fail(QSV_E_BADARG, "shard %d of %zu", shard, h->shards.size());
+  Shard& s = h->shards[shard];
+  if (!s.tile_valid) return fail(QSV_E_BADARG, "the last pass left no tile sums on shard %d", shard);
+  *n = s.tile_nblocks;
+  if (!out) return QSV_OK;
+  if (cap < s.tile_nblocks) return fail(QSV_E_BADARG, "room for %llu tile sums, %llu needed", (unsigned long long)cap, (unsigned long long)s.tile_nblocks);
+  CHK(shard_set(s));
+  HIPCHK(hipMemcpyAsync(out, s.d_tsums, s.tile_nblocks * sizeof(double), hipMemcpyDeviceToHost, s.stream));
+  HIPCHK(hipStreamSynchronize(s.stream));
+  return QSV_OK;
+}
 extern "C" int qsv_timer_begin(qsv_handle* h) {
   if (!h) return fail(QSV_E_BADARG, "NULL handle");
   Shard& s = h->shards[0];

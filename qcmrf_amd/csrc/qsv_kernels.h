@@ -664,7 +664,7 @@ __global__ __launch_bounds__(QSV_TPB) void k_reduce_pairs(const double* __restri
 // zskip != 0 (the generator is its program's last pass, implied zeros): amplitudes with a zskip bit set -- a subset of
 // the ones nonmask makes zero -- are not stored; the shard's zmask says so.  Such a register bit drops its half of
 // every thread's stores (a uniform branch), a zskip thread bit its threads' stores; a tile whose block bits hit zskip
-// only gets its sum, 0.  Tiles keep their index and their sums stay bit-identical: what is skipped adds exactly +-0.
+// is skipped altogether.  Tiles keep their index.
 // Work per tile scales with what changes from tile to tile.  The host splits every table index bit by
 // class for the tile geometry: register bit, lane bit (address bits the 64 lanes of a wave vary in: fixed per lane
 // for the whole kernel) or wave-uniform bit (a bit of the wave index tile * 4 + wave: the wave bits of the tile and
@@ -682,11 +682,10 @@ __global__ __launch_bounds__(QSV_TPB) void k_reduce_pairs(const double* __restri
 // factors at b in list order, and a[j] = s_b x A[j] x the mixed factors in list order.  B = 0 is the one-tile form:
 // A[0] starts from P0 and a[j] = A[j], the product order of the one-tile-per-workgroup generator.  So the order of an
 // amplitude's products depends on its position and the group bits only, never on the grid or the walk; tiles keep
-// their index and their sums their reduction order.  Tile sums: two LDS buffers, one barrier per group.
-// FORM: QSV_GEN_WRITE is the generator as described.  QSV_GEN_SUMS drops the stores and their address arithmetic and
-// keeps everything that feeds the tile sums instruction for instruction: the sums are bit-identical, the shard's
-// memory is untouched (the state is deferred).  QSV_GEN_LISTED stores the tiles of a list (the tiles the sampler's
-// shots fall into) at their real addresses, with the products in group order, and leaves no sums.
+// their index.  The generator leaves no sums: the tile sums of its state come from k_prod_sums (below), which forms no
+// amplitude, whether this kernel stored the state before it or the state is deferred.
+// FORM: QSV_GEN_WRITE is the generator as described.  QSV_GEN_LISTED stores the tiles of a list (the tiles the sampler's
+// shots fall into) at their real addresses, with the products in group order.
 // ZR >= 0: the implied-zero register bits zreg as a compile-time constant (the top register bit as at 34 qubits: the
 // zero half of the register tile costs nothing); ZR < 0: zreg at run time.
 // ---------------------------------------------------------------------------------------
@@ -719,15 +718,14 @@ __device__ __forceinline__ uint32_t prod_gather_wave(uint32_t wi, const uint32_t
   return nl <= 4 ? prod_gather_wave<4>(wi, wb) : prod_gather_wave<QSV_MULTI_MAXLIST>(wi, wb);   // uniform branch
 }
 
-// the three forms of the generator: every amplitude stored | no amplitude stored, tile sums only (the
-// state is deferred: the shard keeps the recipe) | the tiles of a sorted list stored, no sums (the sampler)
-enum { QSV_GEN_WRITE = 0, QSV_GEN_SUMS = 1, QSV_GEN_LISTED = 2 };
+// the two forms of the generator: every amplitude stored | the tiles of a sorted list stored (the sampler)
+enum { QSV_GEN_WRITE = 0, QSV_GEN_LISTED = 2 };
 
 template <int R, bool NT, int ZR, int FORM>
 __global__ __launch_bounds__(QSV_TPB) void k_init_prod(cplx* __restrict__ amp, uint64_t ntiles, BitIns ins, RegPos rp,
                                                        LanePos lp, const ProdFactor* __restrict__ fac, ProdCounts cnt,
                                                        ProdGroup grp, const cplx* __restrict__ tables, int ntab,
-                                                       uint64_t nonmask, double initval, double* __restrict__ tile_sums,
+                                                       uint64_t nonmask, double initval,
                                                        uint64_t zskip, unsigned zreg_arg,
                                                        const uint64_t* __restrict__ list, uint64_t nlist) {
   constexpr int NWB = (QSV_MULTI_MAXLIST + 3) / 4;
@@ -806,8 +804,6 @@ __global__ __launch_bounds__(QSV_TPB) void k_init_prod(cplx* __restrict__ amp, u
   const uint64_t dblk = tile_base_blk(dtile, ins, lp);
   uint64_t tile0 = spread(blockIdx.x);
   uint64_t base_blk = tile_base_blk(tile0, ins, lp);
-  __shared__ double wpart[2][1 << QSV_PROD_MAXG][QSV_TPB / 64];
-  int par = 0;
   // QSV_GEN_LISTED: the walk is over the list instead, one workgroup per entry, each taking the whole group its tile
   // belongs to (the product order is the group order) and storing that one tile.  The list is non-decreasing: an entry
   // equal to its predecessor is skipped (that workgroup stores the tile once for all of them); two different tiles of
@@ -826,10 +822,7 @@ __global__ __launch_bounds__(QSV_TPB) void k_init_prod(cplx* __restrict__ amp, u
 #pragma unroll
       for (int i = 0; i < QSV_PROD_MAXG; ++i) if (t & gt[i]) bsel |= 1u << i;
     }
-    if (base_blk & zskip) {                        // the whole group is implied zero (uniform: no barrier crossed)
-      if (!LISTED && tile_sums && (int)threadIdx.x < nsub) tile_sums[tile0 | sub(gt, threadIdx.x)] = 0.0;
-      continue;
-    }
+    if (base_blk & zskip) continue;                // the whole group is implied zero: nothing to store
     // wave-uniform parts of the group's first tile: lane k holds factor k's (and k + 64's) table offset, in bytes
     uint32_t jb0 = 0, jb1 = 0, rw0 = 0, rw1 = 0;
     const uint32_t wi = (uint32_t)tile0 * (QSV_TPB / 64) + wave;
@@ -900,7 +893,6 @@ __global__ __launch_bounds__(QSV_TPB) void k_init_prod(cplx* __restrict__ amp, u
       cplx s = p0;                                 // s_b
       for (int k = kg; k < kg + cnt.ngrp; ++k) s = cmul(s, ldt(entry(gb0, gb1, k)));
       cplx* __restrict__ pblk = amp + (base_blk | sub(ga, (uint32_t)b));
-      double psum = 0.0;
       // the tile's stores; the multiply by s_b only with group bits, the loop over the mixed factors only where there
       // are any (uniform branches around the whole tile)
       auto stores = [&](auto grouped, auto mixed) {
@@ -916,30 +908,317 @@ __global__ __launch_bounds__(QSV_TPB) void k_init_prod(cplx* __restrict__ amp, u
               for (int c = 0; c < R; ++c) if ((j >> c) & 1) jr += pf.regw[c];
               a = cmul(a, ldt(entry(gb0, gb1, k) + (uint32_t)jr * sizeof(cplx)));
             }
-          if constexpr (FORM != QSV_GEN_SUMS) {
-            uint64_t off = 0;
+          uint64_t off = 0;
 #pragma unroll
-            for (int c = 0; c < R; ++c) if ((j >> c) & 1) off |= ob[c];
-            if (LISTED ? (store && (uint32_t)b == bsel) : store) { if (NT) st_nt((pblk + off) + base_thr, a); else (pblk + off)[base_thr] = a; }
-          }
-          psum = fma(a.x, a.x, fma(a.y, a.y, psum));
+          for (int c = 0; c < R; ++c) if ((j >> c) & 1) off |= ob[c];
+          if (LISTED ? (store && (uint32_t)b == bsel) : store) { if (NT) st_nt((pblk + off) + base_thr, a); else (pblk + off)[base_thr] = a; }
         }
       };
       if (cnt.nmixed) stores(std::true_type{}, std::true_type{});          // mixed factors exist with group bits only
       else if (grp.nb) stores(std::true_type{}, std::false_type{});
       else stores(std::false_type{}, std::false_type{});
-      if (!LISTED && tile_sums) {
-        psum = wave_sum(psum);
-        if (lane == 0) wpart[par][b][wave] = psum;
+    }
+  }
+}
+
+// ---------------------------------------------------------------------------------------
+// k_prod_sums<R, REGSUM>: the per-tile sums of |amp|^2 of the state k_init_prod generates, without forming an amplitude.
+// |amp|^2 of a product is the product of the factors' |.|^2, so with w_k = |table_k entry|^2 a tile's sum is, per
+// thread, (init value^2 x outer weights) x (group weights at tile b) x N, N = sum over the register combinations j of
+// the register factors' weights.  Same tile geometry, tile index, group bits and factor descriptors as k_init_prod (the
+// host's classification is shared); amp is never touched.  Once per workgroup every table entry goes to LDS as ONE
+// double, w = fma(re, re, im * im), with the descriptors and offsets of k_init_prod in 8-byte units.
+// Order of the arithmetic (all of it real, nothing contracted: what the source says is what runs):
+//   per group and thread   w0 = init value^2 x the outer weights in list order; 0 where the thread hits nonmask
+//                          register bit c: t0_c, t1_c = products of its single-register factors' weights at bit value
+//                          0 / 1 in list order (t1_c = 0 on a nonmask bit)
+//                          REGSUM = false (no multi, no mixed factor): N = (..((t0_0 + t1_0) x (t0_1 + t1_1)) x ..)
+//                          REGSUM = true: A[j] by the register expansion c = 0..R-1 from 1 (k_init_prod's, in reals), x
+//                          the multi factors in list order; N = pairwise tree over j (neighbours first)
+//   per tile b             s_b = w0 x the group weights at b in list order; with mixed factors N_b = the same tree over
+//                          A[j] x the mixed weights at (b, j) in list order; v_b = s_b x N (or N_b)
+//   over the 256 threads   a fixed tree for eight tiles of the group at once.  Within a wave the values are transposed as
+//                          they are added: lane l + lane l ^ 32 (v_permlane32_swap: eight values become four, each half
+//                          of the wave keeping four tiles), + lane l ^ 16 (v_permlane16_swap: two values, each row of 16
+//                          lanes one tile), then l ^ 1, l ^ 2, the mirrored half row and the mirrored row (DPP).  Then
+//                          the four waves through LDS, (w0 + w1) + (w2 + w3): two buffers, one barrier per group.
+// So a tile's sum is a fixed function of its position, the factor list and the group bits, never of the grid or the
+// walk.  A group whose block bits hit nonmask gets 0.0 without arithmetic; nonmask, not the implied-zero mask, decides,
+// so implied_zeros 0 and 1 run the same code.  Exact zeros stay exact: a zero weight makes its products 0.
+// Rounding against the exact sum of the stored |amp|^2: a weight is within 2 ulp of |entry|^2 and every multiply adds
+// one, 3 ulp per factor; every addition of non-negative terms one ulp along a chain of R (REGSUM: R levels) + 6 + 2.
+// ---------------------------------------------------------------------------------------
+template <int CTRL>
+__device__ __forceinline__ double dpp_f64(double v) {
+  const int lo = __builtin_amdgcn_update_dpp(0, __double2loint(v), CTRL, 0xf, 0xf, false);
+  const int hi = __builtin_amdgcn_update_dpp(0, __double2hiint(v), CTRL, 0xf, 0xf, false);
+  return __hiloint2double(hi, lo);
+}
+// sum over each row of 16 lanes, every lane of the row ending with the same bits (the partners of a step add the same
+// two numbers): quad_perm [1,0,3,2], quad_perm [2,3,0,1], row_half_mirror, row_mirror
+__device__ __forceinline__ double row16_sum(double v) {
+  v += dpp_f64<0xB1>(v);
+  v += dpp_f64<0x4E>(v);
+  v += dpp_f64<0x141>(v);
+  v += dpp_f64<0x140>(v);
+  return v;
+}
+// x <- x(l) + x(l ^ 32) in lanes 0..31 and y(l) + y(l ^ 32) in lanes 32..63 (SWAP16: l ^ 16, even / odd rows of 16)
+template <bool SWAP16>
+__device__ __forceinline__ double lanes_fold(double x, double y) {
+  const int xl = __double2loint(x), xh = __double2hiint(x), yl = __double2loint(y), yh = __double2hiint(y);
+  if constexpr (SWAP16) {
+    auto a = __builtin_amdgcn_permlane16_swap(xl, yl, false, false);
+    auto b = __builtin_amdgcn_permlane16_swap(xh, yh, false, false);
+    return __hiloint2double(b[0], a[0]) + __hiloint2double(b[1], a[1]);
+  } else {
+    auto a = __builtin_amdgcn_permlane32_swap(xl, yl, false, false);
+    auto b = __builtin_amdgcn_permlane32_swap(xh, yh, false, false);
+    return __hiloint2double(b[0], a[0]) + __hiloint2double(b[1], a[1]);
+  }
+}
+
+template <int R, bool REGSUM>
+__global__ __launch_bounds__(QSV_TPB) void k_prod_sums(uint64_t ntiles, BitIns ins, RegPos rp, LanePos lp,
+                                                       const ProdFactor* __restrict__ fac, ProdCounts cnt, ProdGroup grp,
+                                                       const cplx* __restrict__ tables, int ntab, uint64_t nonmask,
+                                                       double initval, double* __restrict__ tile_sums) {
+#pragma clang fp contract(off)
+  constexpr int NWB = (QSV_MULTI_MAXLIST + 3) / 4;
+  constexpr int NV = 8;                           // tiles of a group reduced together
+  const int nsub = 1 << grp.nb;                   // tiles per group
+  extern __shared__ double4 lds_raw[];
+  double* lw = reinterpret_cast<double*>(lds_raw);
+  const char* ltb = reinterpret_cast<const char*>(lds_raw);
+  // LDS: weights (an even number of slots) | per factor {wave-index bit of element e (bytes 0..11), table offset |
+  // single-register weight << 16} (bytes) | per factor and lane the lane part of the table index (bytes) | group bits
+  // only: per factor and tile of a group the group part of the table index (bytes)
+  uint4* desc = reinterpret_cast<uint4*>(lw + ((ntab + 1) & ~1));
+  uint16_t* lane_off = reinterpret_cast<uint16_t*>(desc + cnt.nfac);
+  uint16_t* grp_off = lane_off + cnt.nfac * 64;
+  const int lane = threadIdx.x & 63;
+  const uint32_t wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  // once per workgroup
+  for (int i = threadIdx.x; i < ntab; i += QSV_TPB) { const cplx t = tables[i]; lw[i] = fma(t.x, t.x, t.y * t.y); }
+  for (int i = threadIdx.x; i < cnt.nfac; i += QSV_TPB) {
+    uint32_t rw = 0;
+    for (int c = 0; c < R; ++c) rw += (uint32_t)fac[i].regw[c];
+    desc[i] = make_uint4(fac[i].wbit[0], fac[i].wbit[1], fac[i].wbit[2], (uint32_t)(fac[i].tab * sizeof(double)) | (uint32_t)(rw * sizeof(double)) << 16);
+  }
+  for (int i = threadIdx.x; i < cnt.nfac * 64; i += QSV_TPB) {
+    const ProdFactor& pf = fac[i >> 6];
+    const uint32_t lb = tile_base_thr((uint32_t)(i & 63), ins, lp);
+    uint32_t j = 0;
+    for (int e = 0; e < pf.nlist; ++e) if (pf.pos[e] >= 0) j |= ((lb >> pf.pos[e]) & 1u) << e;
+    lane_off[i] = (uint16_t)(j * sizeof(double));
+  }
+  if (grp.nb)
+    for (int i = threadIdx.x; i < cnt.nfac << grp.nb; i += QSV_TPB) {
+      const ProdFactor& pf = fac[i >> grp.nb];
+      uint32_t j = 0;
+      for (int g = 0; g < grp.nb; ++g) if ((i >> g) & 1) j += (uint32_t)pf.grpw[g];
+      grp_off[i] = (uint16_t)(j * sizeof(double));
+    }
+  const bool two = cnt.nfac > 64;
+  const int d0 = cnt.nfac ? (lane < cnt.nfac ? lane : 0) : -1;          // this lane's factors: lane and lane + 64
+  const int d1 = two ? (lane + 64 < cnt.nfac ? lane + 64 : 0) : -1;
+  __syncthreads();
+  const double w_thr = (tile_base_thr(threadIdx.x, ins, lp) & nonmask) == 0 ? initval * initval : 0.0;
+  unsigned nreg = 0;                              // register bits that nonmask makes zero
+#pragma unroll
+  for (int c = 0; c < R; ++c) if ((nonmask >> rp.pos[c]) & 1ull) nreg |= 1u << c;
+  // the walk over groups in tile index, as in k_init_prod; tnon: the tile-index bits whose block address bit is in nonmask
+  uint64_t gt[QSV_PROD_MAXG];
+  uint64_t tholes = 0, tnon = 0;
+#pragma unroll
+  for (int i = 0; i < QSV_PROD_MAXG; ++i) {
+    gt[i] = i < grp.nb ? 1ull << grp.tpos[i] : 0ull;
+    tholes |= gt[i];
+  }
+  for (uint64_t t = 1; t < ntiles; t <<= 1) if (tile_base_blk(t, ins, lp) & nonmask) tnon |= t;
+  auto spread = [&](uint64_t x) -> uint64_t {     // group index -> tile index of its first tile
+    for (int i = 0; i < grp.nb; ++i) {
+      const int p = grp.tpos[i];
+      x = ((x >> p) << (p + 1)) | (x & ((1ull << p) - 1ull));
+    }
+    return x;
+  };
+  auto sub = [&](uint32_t b) -> uint64_t {        // tile b of a group: its group bits
+    uint64_t o = 0;
+#pragma unroll
+    for (int i = 0; i < QSV_PROD_MAXG; ++i) if ((b >> i) & 1u) o |= gt[i];
+    return o;
+  };
+  auto ldw = [&](uint32_t o) -> double { return *reinterpret_cast<const double*>(ltb + o); };
+  const uint64_t ngroups = ntiles >> grp.nb;
+  const uint64_t dtile = spread(gridDim.x);
+  uint64_t tile0 = spread(blockIdx.x);
+  __shared__ double wpart[2][1 << QSV_PROD_MAXG][QSV_TPB / 64];
+  int par = 0;
+  for (uint64_t gi = blockIdx.x; gi < ngroups; gi += gridDim.x, tile0 = ((tile0 | tholes) + dtile) & ~tholes) {
+    if (tile0 & tnon) {                            // the whole group is zero (uniform: no barrier crossed)
+      if ((int)threadIdx.x < nsub) tile_sums[tile0 | sub(threadIdx.x)] = 0.0;
+      continue;
+    }
+    // wave-uniform parts of the group's first tile: lane k holds factor k's (and k + 64's) table offset, in bytes
+    uint32_t jb0 = 0, jb1 = 0, rw0 = 0, rw1 = 0;
+    const uint32_t wi = (uint32_t)tile0 * (QSV_TPB / 64) + wave;
+    if (d0 >= 0) {
+      const uint4 d = desc[d0];
+      const uint32_t wb[NWB] = {d.x, d.y, d.z};
+      jb0 = (d.w & 0xffffu) + (prod_gather_wave(wi, wb, cnt.nlmax) << 3);
+      rw0 = d.w >> 16;
+    }
+    if (d1 >= 0) {
+      const uint4 d = desc[d1];
+      const uint32_t wb[NWB] = {d.x, d.y, d.z};
+      jb1 = (d.w & 0xffffu) + (prod_gather_wave(wi, wb, cnt.nlmax) << 3);
+      rw1 = d.w >> 16;
+    }
+    // byte offset in LDS of this thread's entry of factor k, lane k of j0 (k - 64 of j1) holding its wave-uniform part
+    auto entry = [&](uint32_t j0, uint32_t j1, int k) -> uint32_t {
+      const uint32_t u = (uint32_t)__builtin_amdgcn_readlane((int)(k < 64 ? j0 : j1), k & 63);
+      return u + lane_off[k * 64 + lane];
+    };
+    // the outer factors, four at a time while they last: their offsets, then their weights, then the products in
+    // list order (the loads of a batch are in flight together)
+    double w0 = w_thr;
+    int ko = 0;
+    for (; ko + 4 <= cnt.nouter; ko += 4) {
+      uint32_t o[4];
+      double w[4];
+#pragma unroll
+      for (int i = 0; i < 4; ++i) o[i] = entry(jb0, jb1, ko + i);
+#pragma unroll
+      for (int i = 0; i < 4; ++i) w[i] = ldw(o[i]);
+#pragma unroll
+      for (int i = 0; i < 4; ++i) w0 *= w[i];
+    }
+    for (; ko < cnt.nouter; ++ko) w0 *= ldw(entry(jb0, jb1, ko));
+    const int kg = cnt.nouter;                     // the group factors
+    int k0 = kg + cnt.ngrp;
+    double N = 1.0;
+    double A[REGSUM ? 1 << R : 1];
+    A[0] = 1.0;
+#pragma unroll
+    for (int c = 0; c < R; ++c) {
+      const bool zc = (nreg >> c) & 1u;
+      double t0 = 1.0, t1 = zc ? 0.0 : 1.0;
+      for (int k = k0; k < k0 + cnt.nsingle[c]; ++k) {
+        const uint32_t o = entry(jb0, jb1, k);
+        t0 *= ldw(o);
+        if (!zc) t1 *= ldw(o + (uint32_t)__builtin_amdgcn_readlane((int)(k < 64 ? rw0 : rw1), k & 63));
+      }
+      k0 += cnt.nsingle[c];
+      if constexpr (REGSUM) {
+#pragma unroll
+        for (int j = 0; j < (1 << c); ++j) { A[j | (1 << c)] = A[j] * t1; A[j] *= t0; }
+      } else {
+        N *= t0 + t1;
       }
     }
-    if (!LISTED && tile_sums) {                    // two buffers: one barrier per group orders both uses of one
-      __syncthreads();
-      const int t = threadIdx.x;
-      if (t < nsub)
-        tile_sums[tile0 | sub(gt, (uint32_t)t)] = (wpart[par][t][0] + wpart[par][t][1]) + (wpart[par][t][2] + wpart[par][t][3]);
-      par ^= 1;
+    const int km = k0 + cnt.nmulti;                // the mixed factors
+    if constexpr (REGSUM) {
+      for (int k = k0; k < km; ++k) {
+        const uint32_t o = entry(jb0, jb1, k);
+        const ProdFactor& pf = fac[k];
+#pragma unroll
+        for (int j = 0; j < (1 << R); ++j) {
+          int jr = 0;
+#pragma unroll
+          for (int c = 0; c < R; ++c) if ((j >> c) & 1) jr += pf.regw[c];
+          A[j] *= ldw(o + (uint32_t)jr * sizeof(double));
+        }
+      }
+      if (!cnt.nmixed) {
+        double T[1 << R];
+#pragma unroll
+        for (int j = 0; j < (1 << R); ++j) T[j] = A[j];
+#pragma unroll
+        for (int s = 1; s < (1 << R); s <<= 1)
+#pragma unroll
+          for (int j = 0; j < (1 << R); j += 2 * s) T[j] += T[j + s];
+        N = T[0];
+      }
     }
+    for (int cb = 0; cb < nsub; cb += NV) {
+      // tiles cb .. cb + 7 of the group: the group part of lane k's table offsets, then s_b, factor by factor
+      // (slots past the group's last tile repeat it; their values are never written)
+      uint32_t gb0[NV], gb1[NV];
+      double v[NV];
+#pragma unroll
+      for (int i = 0; i < NV; ++i) {
+        const int b = min(cb + i, nsub - 1);
+        gb0[i] = jb0 + (grp.nb && cnt.nfac ? grp_off[(max(d0, 0) << grp.nb) + b] : 0);
+        gb1[i] = jb1;
+        v[i] = w0;
+      }
+      if (two && grp.nb) {
+#pragma unroll
+        for (int i = 0; i < NV; ++i) gb1[i] += grp_off[(d1 << grp.nb) + min(cb + i, nsub - 1)];
+      }
+      auto group_factors = [&](const uint32_t (&gb)[NV], int ka, int kb, int lane_base) {   // factors ka .. kb - 1, their offsets in gb
+        for (int k = ka; k < kb; ++k) {
+          const uint32_t lo = lane_off[k * 64 + lane];
+          double w[NV];
+#pragma unroll
+          for (int i = 0; i < NV; ++i) w[i] = ldw(lo + (uint32_t)__builtin_amdgcn_readlane((int)gb[i], k - lane_base));
+#pragma unroll
+          for (int i = 0; i < NV; ++i) v[i] *= w[i];
+        }
+      };
+      group_factors(gb0, kg, min(kg + cnt.ngrp, 64), 0);
+      group_factors(gb1, max(kg, 64), kg + cnt.ngrp, 64);
+      if constexpr (REGSUM) {
+        if (cnt.nmixed) {
+#pragma unroll
+          for (int i = 0; i < NV; ++i) {
+            if (cb + i >= nsub) continue;
+            double T[1 << R];
+#pragma unroll
+            for (int j = 0; j < (1 << R); ++j) T[j] = A[j];
+            for (int k = km; k < km + cnt.nmixed; ++k) {
+              const uint32_t o = entry(gb0[i], gb1[i], k);
+              const ProdFactor& pf = fac[k];
+#pragma unroll
+              for (int j = 0; j < (1 << R); ++j) {
+                int jr = 0;
+#pragma unroll
+                for (int c = 0; c < R; ++c) if ((j >> c) & 1) jr += pf.regw[c];
+                T[j] *= ldw(o + (uint32_t)jr * sizeof(double));
+              }
+            }
+#pragma unroll
+            for (int s = 1; s < (1 << R); s <<= 1)
+#pragma unroll
+              for (int j = 0; j < (1 << R); j += 2 * s) T[j] += T[j + s];
+            v[i] *= T[0];
+          }
+        } else {
+#pragma unroll
+          for (int i = 0; i < NV; ++i) v[i] *= N;
+        }
+      } else {
+#pragma unroll
+        for (int i = 0; i < NV; ++i) v[i] *= N;
+      }
+      // the wave's sums of the eight tiles: x0 holds tile cb + 2 * row, x1 tile cb + 1 + 2 * row (row = lane >> 4)
+      double u[4];
+#pragma unroll
+      for (int i = 0; i < 4; ++i) u[i] = lanes_fold<false>(v[i], v[i + 4]);
+      const double x0 = row16_sum(lanes_fold<true>(u[0], u[2]));
+      const double x1 = row16_sum(lanes_fold<true>(u[1], u[3]));
+      if ((lane & 15) == 0) {
+        const int t = cb + 2 * (lane >> 4);
+        if (t < nsub) wpart[par][t][wave] = x0;
+        if (t + 1 < nsub) wpart[par][t + 1][wave] = x1;
+      }
+    }
+    __syncthreads();                               // two buffers: one barrier per group orders both uses of one
+    const int t = threadIdx.x;
+    if (t < nsub)
+      tile_sums[tile0 | sub((uint32_t)t)] = (wpart[par][t][0] + wpart[par][t][1]) + (wpart[par][t][2] + wpart[par][t][3]);
+    par ^= 1;
   }
 }
 

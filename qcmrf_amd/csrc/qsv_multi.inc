@@ -206,7 +206,7 @@ static bool group_is_init_product(const qsv_handle* h, const PendingGroup& g) {
 template <int R, bool NT, int ZR, int FORM>
 static int launch_init_prod_k(const qsv_handle* h, const Shard& s, uint64_t ntiles, const BitIns& ins, const RegPos& rp,
                               const LanePos& lp, const ProdFactor* f, const ProdCounts& cnt, const ProdGroup& grp,
-                              const cplx* tab, int ntab, uint64_t nonmask, double initval, double* tsums, uint64_t zskip,
+                              const cplx* tab, int ntab, uint64_t nonmask, double initval, uint64_t zskip,
                               unsigned zreg, const uint64_t* list, uint64_t nlist) {
   // persistent grid: every workgroup the chip holds at once at this kernel's occupancy (option init_prod_grid: fewer)
   const size_t lds = (size_t)ntab * sizeof(cplx) + (size_t)cnt.nfac * (16 + 64 * sizeof(uint16_t)) +
@@ -227,13 +227,13 @@ static int launch_init_prod_k(const qsv_handle* h, const Shard& s, uint64_t ntil
   if (FORM == QSV_GEN_LISTED) grid = std::max<uint64_t>(1, std::min(grid, nlist));   // one workgroup per entry, grid-stride beyond
   else grid = std::min(grid, ntiles >> grp.nb);   // one workgroup per group at most
   hipLaunchKernelGGL((k_init_prod<R, NT, ZR, FORM>), dim3((unsigned)grid), dim3(QSV_TPB), std::max<size_t>(lds, 16), s.stream,
-                     s.amp, ntiles, ins, rp, lp, f, cnt, grp, tab, ntab, nonmask, initval, tsums, zskip, zreg, list, nlist);
+                     s.amp, ntiles, ins, rp, lp, f, cnt, grp, tab, ntab, nonmask, initval, zskip, zreg, list, nlist);
   return QSV_OK;
 }
 template <int R>
 static int launch_init_prod(const qsv_handle* h, const Shard& s, int form, uint64_t ntiles, const BitIns& ins, const RegPos& rp, const LanePos& lp,
                             const ProdFactor* f, const ProdCounts& cnt, const ProdGroup& grp, const cplx* tab, int ntab,
-                            uint64_t nonmask, double initval, double* tsums, uint64_t zskip, unsigned zreg,
+                            uint64_t nonmask, double initval, uint64_t zskip, unsigned zreg,
                             const uint64_t* list = nullptr, uint64_t nlist = 0) {
   // non-temporal stores pay on big shards (34 qubits: 6.86 -> 7.11 TB/s; 28 qubits: -1 %; profiles/r02_nt_variants.log)
   const bool nt = h->opt_nt > 0 || (h->opt_init_prod_nt < 0 && h->L >= QSV_GEN_NT_MIN_L) || h->opt_init_prod_nt > 0;
@@ -241,10 +241,9 @@ static int launch_init_prod(const qsv_handle* h, const Shard& s, int form, uint6
   // other zreg, none included, is read at run time (a compile-time zreg = 0 took 127 registers at R = 4 against 109
   // and wrote the full state 8 % slower)
   constexpr int ZTOP = 1 << (R - 1);
-#define QSV_LIP(NT, ZR, FORM) return launch_init_prod_k<R, NT, ZR, FORM>(h, s, ntiles, ins, rp, lp, f, cnt, grp, tab, ntab, nonmask, initval, tsums, zskip, zreg, list, nlist)
-  // the sums-only form stores nothing and the listed form a few tiles that k_locate_tile reads next: one instantiation
-  // per (R, ZR) each, whatever the non-temporal choice of the writing form
-  if (form == QSV_GEN_SUMS) { if (zreg == ZTOP) QSV_LIP(false, ZTOP, QSV_GEN_SUMS); QSV_LIP(false, -1, QSV_GEN_SUMS); }
+#define QSV_LIP(NT, ZR, FORM) return launch_init_prod_k<R, NT, ZR, FORM>(h, s, ntiles, ins, rp, lp, f, cnt, grp, tab, ntab, nonmask, initval, zskip, zreg, list, nlist)
+  // the listed form stores a few tiles that k_locate_tile reads next: one instantiation per (R, ZR), whatever the
+  // non-temporal choice of the writing form
   if (form == QSV_GEN_LISTED) { if (zreg == ZTOP) QSV_LIP(false, ZTOP, QSV_GEN_LISTED); QSV_LIP(false, -1, QSV_GEN_LISTED); }
   if (nt) { if (zreg == ZTOP) QSV_LIP(true, ZTOP, QSV_GEN_WRITE); QSV_LIP(true, -1, QSV_GEN_WRITE); }
   if (zreg == ZTOP) QSV_LIP(false, ZTOP, QSV_GEN_WRITE);
@@ -252,10 +251,45 @@ static int launch_init_prod(const qsv_handle* h, const Shard& s, int form, uint6
 #undef QSV_LIP
 }
 
+// The tile sums of the state the generator produces (k_prod_sums): the one producer of a generator pass's sums, whether
+// the amplitudes are stored by the launch before it or deferred.  Persistent grid like the generator's.
+template <int R, bool REGSUM>
+static int launch_prod_sums_k(const qsv_handle* h, const Shard& s, uint64_t ntiles, const BitIns& ins, const RegPos& rp,
+                              const LanePos& lp, const ProdFactor* f, const ProdCounts& cnt, const ProdGroup& grp,
+                              const cplx* tab, int ntab, uint64_t nonmask, double initval, double* tsums) {
+  const size_t lds = (size_t)((ntab + 1) & ~1) * sizeof(double) + (size_t)cnt.nfac * (16 + 64 * sizeof(uint16_t)) +
+                     (grp.nb ? ((size_t)cnt.nfac << grp.nb) * sizeof(uint16_t) : 0);
+  static thread_local std::unordered_map<size_t, int> occupancy;
+  auto it = occupancy.find(lds);
+  if (it == occupancy.end()) {
+    int per_cu = 0;
+    HIPCHK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, reinterpret_cast<const void*>(&k_prod_sums<R, REGSUM>),
+                                                        QSV_TPB, std::max<size_t>(lds, 16)));
+    it = occupancy.emplace(lds, per_cu).first;
+  }
+  const int per_cu = it->second;
+  if (per_cu < 1) return fail(QSV_E_UNSUPPORTED, "k_prod_sums does not fit a CU (%zu B of LDS)", lds);
+  uint64_t grid = (uint64_t)per_cu * (uint64_t)s.n_cu;
+  if (h->opt_init_prod_grid > 0) grid = std::min<uint64_t>(grid, (uint64_t)h->opt_init_prod_grid);
+  grid = std::min(grid, ntiles >> grp.nb);        // one workgroup per group at most
+  hipLaunchKernelGGL((k_prod_sums<R, REGSUM>), dim3((unsigned)grid), dim3(QSV_TPB), std::max<size_t>(lds, 16), s.stream,
+                     ntiles, ins, rp, lp, f, cnt, grp, tab, ntab, nonmask, initval, tsums);
+  return QSV_OK;
+}
+template <int R>
+static int launch_prod_sums(const qsv_handle* h, const Shard& s, uint64_t ntiles, const BitIns& ins, const RegPos& rp, const LanePos& lp,
+                            const ProdFactor* f, const ProdCounts& cnt, const ProdGroup& grp, const cplx* tab, int ntab,
+                            uint64_t nonmask, double initval, double* tsums) {
+  // only single-register factors on the register bits: the register sum is a product of R two-term sums
+  if (cnt.nmulti == 0 && cnt.nmixed == 0)
+    return launch_prod_sums_k<R, false>(h, s, ntiles, ins, rp, lp, f, cnt, grp, tab, ntab, nonmask, initval, tsums);
+  return launch_prod_sums_k<R, true>(h, s, ntiles, ins, rp, lp, f, cnt, grp, tab, ntab, nonmask, initval, tsums);
+}
+
 // the generator from a shard's recipe: the writing form (realize) or the listed form (qsv_sample)
 static int launch_recipe(const qsv_handle* h, const Shard& s, int form, const uint64_t* list, uint64_t nlist) {
   const GenRecipe& rc = s.recipe;
-#define QSV_LR(RR) return launch_init_prod<RR>(h, s, form, rc.ntiles, rc.ins, rc.rp, rc.lp, rc.dfac, rc.cnt, rc.grp, rc.dtab, rc.ntab, rc.nonmask, rc.initval, nullptr, rc.zskip, rc.zreg, list, nlist)
+#define QSV_LR(RR) return launch_init_prod<RR>(h, s, form, rc.ntiles, rc.ins, rc.rp, rc.lp, rc.dfac, rc.cnt, rc.grp, rc.dtab, rc.ntab, rc.nonmask, rc.initval, rc.zskip, rc.zreg, list, nlist)
   switch (rc.R) {
     case 3: QSV_LR(3);
     case 4: QSV_LR(4);
@@ -266,7 +300,7 @@ static int launch_recipe(const qsv_handle* h, const Shard& s, int form, const ui
 #undef QSV_LR
 }
 
-// A deferred shard gets its amplitudes: the writing generator on the recipe the sums-only launch ran with, the
+// A deferred shard gets its amplitudes: the writing generator on the recipe the sums launch ran with, the
 // instantiation the engine's options choose for a writing launch.  The state does not change, so -- as in materialize --
 // the cached sums stay valid.  Booked under init_prod with the 16 B of every amplitude stored; afterwards zmask is what
 // a writing final pass leaves (it was set when the state was deferred).
@@ -434,7 +468,8 @@ static int flush_init_product_r(qsv_handle* h, Shard& s, PendingGroup& g, bool f
   unsigned zreg = 0;
   for (int c = 0; c < R; ++c) if ((zskip >> rp.pos[c]) & 1ull) zreg |= 1u << c;
   s.zmask = zskip;
-  // Deferred state (option defer_state): as the program's last pass, leaving tile sums, the generator stores nothing.
+  // Deferred state (option defer_state): as the program's last pass, leaving tile sums, the generator stores nothing:
+  // k_prod_sums alone runs.  Not deferred, the writing generator runs and then k_prod_sums, one bracket, one launch booked.
   // The step's result needs the sums and the tiles its shots fall into (qsv_sample stores those); whoever reads the
   // state later calls realize().  The descriptors and tables then go to the shard's recipe buffer, not to the arena.
   const bool defer = tsums != nullptr && (h->opt_defer_state > 0 || (h->opt_defer_state < 0 && h->L >= QSV_DEFER_MIN_L));
@@ -466,8 +501,10 @@ static int flush_init_product_r(qsv_handle* h, Shard& s, PendingGroup& g, bool f
   const double initval = g.initval;
   int lr = QSV_OK;
   const int r = launch(h, s, QSV_K_INIT_PROD, defer ? 0.0 : 16.0 * (double)(n >> __builtin_popcountll(zskip)), [&] {
-    lr = launch_init_prod<R>(h, s, defer ? QSV_GEN_SUMS : QSV_GEN_WRITE, ntiles, ins, rp, lp, reinterpret_cast<const ProdFactor*>(dfac), cnt, grp,
-                             reinterpret_cast<const cplx*>(dtab), ntab, nonmask, initval, tsums, zskip, zreg);
+    const ProdFactor* df = reinterpret_cast<const ProdFactor*>(dfac);
+    const cplx* dt = reinterpret_cast<const cplx*>(dtab);
+    if (!defer) lr = launch_init_prod<R>(h, s, QSV_GEN_WRITE, ntiles, ins, rp, lp, df, cnt, grp, dt, ntab, nonmask, initval, zskip, zreg);
+    if (lr == QSV_OK && tsums) lr = launch_prod_sums<R>(h, s, ntiles, ins, rp, lp, df, cnt, grp, dt, ntab, nonmask, initval, tsums);
   });
   CHK(lr);
   s.deferred = defer && r == QSV_OK;
