@@ -273,7 +273,8 @@ static unsigned grid_for(const qsv_handle* h, const Shard& s, uint64_t work, uin
   uint64_t cap = (uint64_t)s.n_cu * (uint64_t)h->opt_blocks_per_cu;
   if (need < 1) need = 1;
   // HIP rejects a launch whose gridDim.x * blockDim.x reaches 2^32 (hit by a 256 GiB shard:
-  // 2^34 amplitudes / 4 per thread); every kernel sized through here has a grid-stride loop
+  // 2^34 amplitudes / 4 per thread); every kernel sized through here has a grid-stride loop.  No state a test can hold
+  // reaches either cap by itself: tests/test_gpu_kernel_forms.py runs the loops' later iterations with blocks_per_cu = 1
   return (unsigned)std::min<uint64_t>(std::min(need, cap), (1ull << 24) - 1ull);
 }
 
