@@ -153,20 +153,22 @@ extern "C" int qsv_exec(qsv_handle* h, const qsv_op* ops, int n_ops, const doubl
 // ------------------------------------------------------------------------------------------
 // noisy shots: one trajectory per shot, in LDS (kernel: qsv_noise.hip) or in a slot of device memory (qsv_noise_hbm.hip)
 // ------------------------------------------------------------------------------------------
-// The qsv_op records are re-encoded once per call into 32-byte records (NzOp, or NzWideOp for the slot path) and a pool in
-// which equal tables are stored once (a lowered circuit repeats a handful of matrices thousands of times): every
-// trajectory streams the whole list.  One validator (nz_encode) fills both record formats; what differs between them
-// is how a control bit and a listed qubit are stored, which the two pairs of overloads below say.
+// The qsv_op records are re-encoded once per call into 32-byte records (NzOp, qsv_noise.h: one format for both paths) and
+// a pool in which equal tables are stored once (a lowered circuit repeats a handful of matrices thousands of times): every
+// trajectory streams the whole list.  Both entry points are nz_run: the checks, the re-encoding (nz_encode), the staging of
+// the device copies (nz_stage), the launch fields the kernels share (NzCall) and the copy back.  An entry point says its
+// width limit and how it launches: qsv_noisy_sample picks a k_noisy instantiation and lets the launcher size the grid by LDS
+// occupancy; qsv_noisy_sample_hbm sizes the grid by the memory its slots need, allocates them and launches k_noisy_hbm.
+// What a record does on the device is written once as well (qsv_noise_ops.h).
 static inline void nz_put_ctrl(NzOp& c, int q, bool one) {
-  c.cmask |= (uint16_t)(1u << q);
-  if (one) c.cval |= (uint16_t)(1u << q);
-}
-static inline void nz_put_ctrl(NzWideOp& c, int q, bool one) {
   c.cmask |= 1u << q;
   if (one) c.cval |= 1u << q;
 }
-static inline void nz_put_qubit(NzOp& c, int b, int q) { c.qlist |= (uint64_t)q << (4 * b); }
-static inline void nz_put_qubit(NzWideOp& c, int b, int q) { c.ql[b >> 3] |= (uint64_t)q << (8 * (b & 7)); }
+static inline void nz_put_qubit(NzOp& c, int b, int q) {            // read back by nz_qubit
+  if (b < 4) c.cmask |= (uint32_t)q << (8 * b);
+  else if (b < 8) c.cval |= (uint32_t)q << (8 * (b - 4));
+  else c.ql8 |= (uint64_t)q << (8 * (b - 8));
+}
 
 struct NzPool {                                                   // each table once, at an even offset (16-byte aligned)
   std::vector<double> pool;
@@ -199,9 +201,8 @@ static int nz_check_meas(qsv_handle* h, const int* meas_qubits, int n_meas, cons
   return QSV_OK;
 }
 
-// validates every record and appends its compact form (Rec = NzOp or NzWideOp) to cops, its tables to pool
-template <class Rec>
-static int nz_encode(qsv_handle* h, const qsv_op* ops, int n_ops, const double* data, uint64_t n_data, std::vector<Rec>& cops,
+// validates every record and appends its compact form to cops, its tables to pool
+static int nz_encode(qsv_handle* h, const qsv_op* ops, int n_ops, const double* data, uint64_t n_data, std::vector<NzOp>& cops,
                      NzPool& pool, bool* has_kraus) {
   cops.reserve(n_ops);
   *has_kraus = false;
@@ -214,10 +215,10 @@ static int nz_encode(qsv_handle* h, const qsv_op* ops, int n_ops, const double* 
                                                           (unsigned long long)o.data_off, (unsigned long long)cnt, (unsigned long long)n_data);
       return QSV_OK;
     };
-    auto ctrl_mask = [&](Rec& c) {
+    auto ctrl_mask = [&](NzOp& c) {
       for (int b = 0; b < o.n; ++b) nz_put_ctrl(c, o.qubits[b], o.vals[b] != 0);
     };
-    Rec c;
+    NzOp c;
     memset(&c, 0, sizeof c);
     switch (o.kind) {
       case QSV_OP_INIT_ZERO:
@@ -226,7 +227,7 @@ static int nz_encode(qsv_handle* h, const qsv_op* ops, int n_ops, const double* 
         if (mask >> h->W) return fail(QSV_E_BADARG, "op %d: mask has bits beyond qubit %d", i, h->W - 1);
         const double val = std::pow(2.0, -0.5 * __builtin_popcountll(mask));
         c.kind = NZ_INIT;
-        c.cmask = (decltype(c.cmask))mask;
+        c.cmask = (uint32_t)mask;
         c.off = pool.put(&val, 1);
         break;
       }
@@ -235,7 +236,7 @@ static int nz_encode(qsv_handle* h, const qsv_op* ops, int n_ops, const double* 
         CHK(check_qubit(h, o.target, "target"));
         CHK(check_distinct(h, o.n, o.qubits, o.target));
         c.kind = o.kind == QSV_OP_1Q ? NZ_1Q : NZ_MCX;
-        c.target = (decltype(c.target))o.target;
+        c.target = (uint8_t)o.target;
         ctrl_mask(c);
         if (o.kind == QSV_OP_1Q) { CHK(need(8)); c.off = pool.put(d, 8); }
         break;
@@ -243,7 +244,7 @@ static int nz_encode(qsv_handle* h, const qsv_op* ops, int n_ops, const double* 
         CHK(check_distinct(h, o.n, o.qubits, -1));
         CHK(need(2ull << o.n));
         c.kind = NZ_DIAG;
-        c.n = (decltype(c.n))o.n;
+        c.n = (uint8_t)o.n;
         for (int b = 0; b < o.n; ++b) nz_put_qubit(c, b, o.qubits[b]);
         c.off = pool.put(d, 2ull << o.n);
         break;
@@ -267,7 +268,7 @@ static int nz_encode(qsv_handle* h, const qsv_op* ops, int n_ops, const double* 
                         (unsigned long long)p, d[p]);
         if (d[np - 1] != 1.0) return fail(QSV_E_BADARG, "op %d: cumulative Pauli probabilities end at %.17g, not 1", i, d[np - 1]);
         c.kind = NZ_PAULI;
-        c.n = (decltype(c.n))o.n;
+        c.n = (uint8_t)o.n;
         for (int b = 0; b < o.n; ++b) nz_put_qubit(c, b, o.qubits[b]);
         c.off = pool.put(d, np);
         break;
@@ -289,8 +290,8 @@ static int nz_encode(qsv_handle* h, const qsv_op* ops, int n_ops, const double* 
         if (std::fabs(e00 - 1.0) > 1e-9 || std::fabs(e11 - 1.0) > 1e-9 || std::fabs(e01r) > 1e-9 || std::fabs(e01i) > 1e-9)
           return fail(QSV_E_BADARG, "op %d: the K^dg K of a Kraus channel must sum to the identity (diagonal %.17g, %.17g)", i, e00, e11);
         c.kind = NZ_KRAUS;
-        c.target = (decltype(c.target))o.qubits[0];
-        c.n = (decltype(c.n))m;
+        c.target = (uint8_t)o.qubits[0];
+        c.n = (uint8_t)m;
         c.off = pool.put(d, 12 * (size_t)m);
         *has_kraus = true;
         break;
@@ -305,19 +306,17 @@ static int nz_encode(qsv_handle* h, const qsv_op* ops, int n_ops, const double* 
 
 // the device copies of one call in the shard's noisy buffer: [ops | pool | pos | out], each part 256-byte aligned
 struct NzStaged {
-  char* ops;
+  const NzOp* ops;
   const double* pool;
   const int* pos;
   uint64_t* out;
 };
-template <class Rec>
-static int nz_stage(Shard& s, const std::vector<Rec>& cops, const std::vector<double>& pool, const int* meas_qubits, int n_meas,
+static int nz_stage(Shard& s, const std::vector<NzOp>& cops, const std::vector<double>& pool, const int* meas_qubits, int n_meas,
                     uint64_t shots, NzStaged* st) {
-  static_assert(sizeof(Rec) == 32, "compact records are 32 bytes");
   std::vector<int> pos(64, -1);
   for (int j = 0; meas_qubits && j < n_meas; ++j) pos[j] = meas_qubits[j];
   auto up = [](size_t b) { return (b + 255) & ~size_t(255); };
-  const size_t b_ops = up(cops.size() * sizeof(Rec) + 1), b_pool = up(pool.size() * sizeof(double)), b_pos = up(64 * sizeof(int));
+  const size_t b_ops = up(cops.size() * sizeof(NzOp) + 1), b_pool = up(pool.size() * sizeof(double)), b_pos = up(64 * sizeof(int));
   const size_t bytes = b_ops + b_pool + b_pos + up(shots * sizeof(uint64_t));
   if (s.noisy_cap < bytes) {
     if (s.d_noisy) { HIPCHK(hipStreamSynchronize(s.stream)); HIPCHK(hipFree(s.d_noisy)); }
@@ -327,20 +326,19 @@ static int nz_stage(Shard& s, const std::vector<Rec>& cops, const std::vector<do
     s.noisy_cap = bytes;
   }
   char* base = s.d_noisy;
-  st->ops = base;
+  st->ops = reinterpret_cast<const NzOp*>(base);
   st->pool = reinterpret_cast<const double*>(base + b_ops);
   st->pos = reinterpret_cast<const int*>(base + b_ops + b_pool);
   st->out = reinterpret_cast<uint64_t*>(base + b_ops + b_pool + b_pos);
-  if (!cops.empty()) HIPCHK(hipMemcpyAsync(base, cops.data(), cops.size() * sizeof(Rec), hipMemcpyHostToDevice, s.stream));
+  if (!cops.empty()) HIPCHK(hipMemcpyAsync(base, cops.data(), cops.size() * sizeof(NzOp), hipMemcpyHostToDevice, s.stream));
   HIPCHK(hipMemcpyAsync(base + b_ops, pool.data(), pool.size() * sizeof(double), hipMemcpyHostToDevice, s.stream));
   HIPCHK(hipMemcpyAsync(base + b_ops + b_pool, pos.data(), 64 * sizeof(int), hipMemcpyHostToDevice, s.stream));
   return QSV_OK;
 }
 
 // records -> compact records, pool and measurement map of one call
-template <class Rec>
 static int nz_prepare(qsv_handle* h, const qsv_op* ops, int n_ops, const double* data, uint64_t n_data, const int* meas_qubits,
-                      int n_meas, const double* readout, std::vector<Rec>& cops, NzPool& pool, bool* has_kraus, NzMeas* meas) {
+                      int n_meas, const double* readout, std::vector<NzOp>& cops, NzPool& pool, bool* has_kraus, NzMeas* meas) {
   CHK(nz_check_meas(h, meas_qubits, n_meas, readout));
   CHK(nz_encode(h, ops, n_ops, data, n_data, cops, pool, has_kraus));
   meas->n = meas_qubits ? n_meas : -1;
@@ -352,46 +350,65 @@ static int nz_prepare(qsv_handle* h, const qsv_op* ops, int n_ops, const double*
   return QSV_OK;
 }
 
-extern "C" int qsv_noisy_sample(qsv_handle* h, const qsv_op* ops, int n_ops, const double* data, uint64_t n_data,
-                                uint64_t shots, uint64_t seed, const int* meas_qubits, int n_meas,
-                                const double* readout, uint64_t* out_bits) {
+// One call of either path: everything but the width limit (max_w qubits, kept in `where`) and the launch.  launch(s, c, kraus)
+// gets the shard, the fields both kernels take and whether the stream holds a Kraus record; it chooses its grid and starts
+// its kernel on s.stream.
+template <class Launch>
+static int nz_run(qsv_handle* h, const qsv_op* ops, int n_ops, const double* data, uint64_t n_data, uint64_t shots, uint64_t seed,
+                  const int* meas_qubits, int n_meas, const double* readout, uint64_t* out_bits, int max_w, const char* where,
+                  Launch launch) {
   CHK(nz_check_args(h, ops, n_ops, shots, out_bits));
-  if (h->W > QSV_NOISY_MAX_QUBITS)
-    return fail(QSV_E_BADARG, "noisy shots keep one %d-qubit state per trajectory in LDS: at most %d qubits", h->W, QSV_NOISY_MAX_QUBITS);
+  if (h->W > max_w) return fail(QSV_E_BADARG, "noisy shots keep one %d-qubit state per trajectory in %s: at most %d qubits", h->W, where, max_w);
   std::vector<NzOp> cops;
   NzPool pool;
   bool has_kraus = false;
-  NzMeas meas;
-  CHK(nz_prepare(h, ops, n_ops, data, n_data, meas_qubits, n_meas, readout, cops, pool, &has_kraus, &meas));
+  NzCall c;
+  CHK(nz_prepare(h, ops, n_ops, data, n_data, meas_qubits, n_meas, readout, cops, pool, &has_kraus, &c.meas));
   if (shots == 0) return QSV_OK;
   Shard& s = h->shards[0];
   CHK(shard_set(s));
   NzStaged st;
   CHK(nz_stage(s, cops, pool.pool, meas_qubits, n_meas, shots, &st));
-  NzLaunch l;
-  l.stream = s.stream;
-  l.W = h->W;
-  l.n_cu = s.n_cu;
-  l.max_grid = h->opt_noisy_grid;
-  l.d_ops = reinterpret_cast<const NzOp*>(st.ops);
-  l.n_ops = (int)cops.size();
-  l.kraus = has_kraus;
-  l.d_pool = st.pool;
-  l.shots = shots;
-  l.seed = seed;
-  meas.pos = st.pos;
-  l.meas = meas;
-  l.d_out = st.out;
-  unsigned grid = 0;
-  HIPCHK(qsv_noise_launch(l, &grid));
-  HIPCHK(hipMemcpyAsync(out_bits, l.d_out, shots * sizeof(uint64_t), hipMemcpyDeviceToHost, s.stream));
-  HIPCHK(hipStreamSynchronize(s.stream));
+  c.stream = s.stream;
+  c.W = h->W;
+  c.d_ops = st.ops;
+  c.n_ops = (int)cops.size();
+  c.d_pool = st.pool;
+  c.shots = shots;
+  c.seed = seed;
+  c.meas.pos = st.pos;
+  c.d_out = st.out;
+  const int rc = launch(s, c, has_kraus);
+  hipError_t e = hipSuccess;
+  if (rc == QSV_OK) e = hipMemcpyAsync(out_bits, c.d_out, shots * sizeof(uint64_t), hipMemcpyDeviceToHost, s.stream);
+  // Synchronised on every way out, a failed launch included, so that the stream is idle before a caller frees its slots.
+  // (For the LDS path the synchronisation after a failed launch is new: nothing runs then, and the error returned is the same.)
+  const hipError_t e2 = hipStreamSynchronize(s.stream);
+  CHK(rc);
+  HIPCHK(e);
+  HIPCHK(e2);
   return QSV_OK;
 }
 
-// The slot path: as qsv_noisy_sample up to the launch.  The slots are one allocation per call, sized for the grid and
-// freed on every way out (NzSlots); nothing of them stays on the handle, so a handle that ran 64 GiB of trajectories
-// holds no more memory afterwards than one that did not.
+extern "C" int qsv_noisy_sample(qsv_handle* h, const qsv_op* ops, int n_ops, const double* data, uint64_t n_data,
+                                uint64_t shots, uint64_t seed, const int* meas_qubits, int n_meas,
+                                const double* readout, uint64_t* out_bits) {
+  return nz_run(h, ops, n_ops, data, n_data, shots, seed, meas_qubits, n_meas, readout, out_bits, QSV_NOISY_MAX_QUBITS, "LDS",
+                [&](Shard& s, const NzCall& c, bool kraus) -> int {
+                  NzLaunch l;
+                  static_cast<NzCall&>(l) = c;
+                  l.n_cu = s.n_cu;
+                  l.max_grid = h->opt_noisy_grid;
+                  l.kraus = kraus;
+                  unsigned grid = 0;
+                  HIPCHK(qsv_noise_launch(l, &grid));
+                  return QSV_OK;
+                });
+}
+
+// The slot path.  The slots are one allocation per call, sized for the grid and freed on every way out (NzSlots), after
+// nz_run has synchronised; nothing of them stays on the handle, so a handle that ran 64 GiB of trajectories holds no more
+// memory afterwards than one that did not.
 struct NzSlots {
   char* p = nullptr;
   ~NzSlots() { if (p) hipFree(p); }
@@ -399,59 +416,35 @@ struct NzSlots {
 extern "C" int qsv_noisy_sample_hbm(qsv_handle* h, const qsv_op* ops, int n_ops, const double* data, uint64_t n_data,
                                     uint64_t shots, uint64_t seed, const int* meas_qubits, int n_meas,
                                     const double* readout, uint64_t* out_bits) {
-  CHK(nz_check_args(h, ops, n_ops, shots, out_bits));
-  if (h->W > QSV_NOISY_HBM_MAX_QUBITS)
-    return fail(QSV_E_BADARG, "noisy shots keep one %d-qubit state per trajectory in a slot of device memory: at most %d qubits",
-                h->W, QSV_NOISY_HBM_MAX_QUBITS);
-  std::vector<NzWideOp> cops;
-  NzPool pool;
-  bool has_kraus = false;
-  NzMeas meas;
-  CHK(nz_prepare(h, ops, n_ops, data, n_data, meas_qubits, n_meas, readout, cops, pool, &has_kraus, &meas));
-  if (shots == 0) return QSV_OK;
-  Shard& s = h->shards[0];
-  CHK(shard_set(s));
-  NzStaged st;
-  CHK(nz_stage(s, cops, pool.pool, meas_qubits, n_meas, shots, &st));
-  // grid = min(shots, noisy_grid if set, workgroups resident at once, slots that fit into 90 % of the free memory)
-  const uint64_t slot = (uint64_t)16 << h->W;
-  uint64_t grid = 0;
-  HIPCHK(qsv_noise_hbm_resident(s.n_cu, &grid));
-  if (h->opt_noisy_grid > 0 && (uint64_t)h->opt_noisy_grid < grid) grid = (uint64_t)h->opt_noisy_grid;
-  if (shots < grid) grid = shots;
-  size_t free_b = 0, total_b = 0;
-  HIPCHK(hipMemGetInfo(&free_b, &total_b));
-  const uint64_t fit = (uint64_t)((double)free_b * 0.9) / slot;
-  if (fit < 1)
-    return fail(QSV_E_NOMEM, "noisy shots in device memory: one %d-qubit trajectory needs %llu bytes, %llu bytes are free (qsv_device_memory)",
-                h->W, (unsigned long long)slot, (unsigned long long)free_b);
-  if (fit < grid) grid = fit;
   NzSlots slots;
-  if (hipMalloc(&slots.p, grid * slot) != hipSuccess) {
-    slots.p = nullptr;
-    (void)hipGetLastError();
-    return fail(QSV_E_NOMEM, "noisy shots in device memory: %llu slots of %llu bytes need %llu bytes, %llu bytes are free (qsv_device_memory)",
-                (unsigned long long)grid, (unsigned long long)slot, (unsigned long long)(grid * slot), (unsigned long long)free_b);
-  }
-  NzHbmLaunch l;
-  l.stream = s.stream;
-  l.W = h->W;
-  l.grid = (unsigned)grid;
-  l.d_ops = reinterpret_cast<const NzWideOp*>(st.ops);
-  l.n_ops = (int)cops.size();
-  l.d_pool = st.pool;
-  l.shots = shots;
-  l.seed = seed;
-  meas.pos = st.pos;
-  l.meas = meas;
-  l.d_slots = slots.p;
-  l.d_out = st.out;
-  hipError_t e = qsv_noise_hbm_launch(l);
-  if (e == hipSuccess) e = hipMemcpyAsync(out_bits, l.d_out, shots * sizeof(uint64_t), hipMemcpyDeviceToHost, s.stream);
-  const hipError_t e2 = hipStreamSynchronize(s.stream);             // the kernel is done with the slots before they are freed
-  HIPCHK(e);
-  HIPCHK(e2);
-  return QSV_OK;
+  return nz_run(h, ops, n_ops, data, n_data, shots, seed, meas_qubits, n_meas, readout, out_bits, QSV_NOISY_HBM_MAX_QUBITS,
+                "a slot of device memory", [&](Shard& s, const NzCall& c, bool) -> int {
+    // grid = min(shots, noisy_grid if set, workgroups resident at once, slots that fit into 90 % of the free memory)
+    const uint64_t slot = (uint64_t)16 << h->W;
+    uint64_t grid = 0;
+    HIPCHK(qsv_noise_hbm_resident(s.n_cu, &grid));
+    if (h->opt_noisy_grid > 0 && (uint64_t)h->opt_noisy_grid < grid) grid = (uint64_t)h->opt_noisy_grid;
+    if (shots < grid) grid = shots;
+    size_t free_b = 0, total_b = 0;
+    HIPCHK(hipMemGetInfo(&free_b, &total_b));
+    const uint64_t fit = (uint64_t)((double)free_b * 0.9) / slot;
+    if (fit < 1)
+      return fail(QSV_E_NOMEM, "noisy shots in device memory: one %d-qubit trajectory needs %llu bytes, %llu bytes are free (qsv_device_memory)",
+                  h->W, (unsigned long long)slot, (unsigned long long)free_b);
+    if (fit < grid) grid = fit;
+    if (hipMalloc(&slots.p, grid * slot) != hipSuccess) {
+      slots.p = nullptr;
+      (void)hipGetLastError();
+      return fail(QSV_E_NOMEM, "noisy shots in device memory: %llu slots of %llu bytes need %llu bytes, %llu bytes are free (qsv_device_memory)",
+                  (unsigned long long)grid, (unsigned long long)slot, (unsigned long long)(grid * slot), (unsigned long long)free_b);
+    }
+    NzHbmLaunch l;
+    static_cast<NzCall&>(l) = c;
+    l.grid = (unsigned)grid;
+    l.d_slots = slots.p;
+    HIPCHK(qsv_noise_hbm_launch(l));
+    return QSV_OK;
+  });
 }
 
 // ------------------------------------------------------------------------------------------

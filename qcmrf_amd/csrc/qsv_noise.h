@@ -1,5 +1,6 @@
 // qsv_noise.h -- noisy shots as per-shot trajectories (qsv_noisy_sample): the compact op stream the kernel walks
-// and its launcher.  Shared by qsv_noise.hip (kernel) and qsv.hip (entry point, re-encoding of qsv_op records).
+// and its launcher.  Shared by qsv_noise.hip and qsv_noise_hbm.hip (kernels; what a record does is in qsv_noise_ops.h) and
+// qsv.hip (entry points, re-encoding of qsv_op records).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -11,20 +12,29 @@
 enum { NZ_INIT = 0, NZ_1Q, NZ_MCX, NZ_DIAG, NZ_MCPHASE, NZ_PAULI, NZ_KRAUS };
 
 // One op of the compact stream, 32 bytes: every trajectory reads the whole list, so a record is a quarter of an
-// L2 line instead of the 168 bytes of a qsv_op.  Qubits < 16, so masks are 16 bits.
+// L2 line instead of the 168 bytes of a qsv_op.  Both paths read this record: qubits < 256, masks of 32 bits (the slot path
+// goes to 24 qubits; the 13 of the LDS path fit as well).  What a trajectory waits for at every op is the scalar fetch of
+// the record, so everything but a diagonal over more than 8 qubits sits in the first 16 bytes, one s_load_dwordx4
+// (nz_fetch): DIAG and PAULI have no controls, and their first 8 listed qubits take the place of cmask and cval.
 struct NzOp {
-  uint16_t kind;       // NZ_*
-  uint16_t target;     // 1Q, MCX, KRAUS
-  uint16_t cmask;      // control qubits (1Q, MCX, MCPHASE: all its qubits); NZ_INIT: the uniform mask
-  uint16_t cval;       // values the control bits must have
+  uint32_t kind : 8;   // NZ_*.  Bit fields of one word: the record's first 16 bytes have no hole and load as one piece
+  uint32_t target : 8; // 1Q, MCX, KRAUS
+  uint32_t n : 16;     // DIAG, PAULI: number of listed qubits; KRAUS: number of operators (1..4)
+  uint32_t cmask;      // control qubits (1Q, MCX, MCPHASE: all its qubits); NZ_INIT: the uniform mask.  DIAG, PAULI: listed
+  uint32_t cval;       // qubits 0..3 / values the control bits must have.  DIAG, PAULI: listed qubits 4..7, 8 bits each
   uint32_t off;        // into the pool (doubles): 1Q 8 = m00 m01 m10 m11; DIAG 2^n complex; MCPHASE (cos, sin);
                        // INIT the amplitude value; PAULI 4^n cumulative probabilities; KRAUS n x 8 = the K_k as 1Q, then
                        // n x 4 = (E00, E11, Re E01, Im E01) of E_k = K_k^dg K_k
-  uint32_t n;          // DIAG, PAULI: number of qubits in qlist; KRAUS: number of operators (1..4)
-  uint64_t qlist;      // DIAG, PAULI: qubit b in bits [4b, 4b + 4)
-  uint64_t pad;
+  uint64_t ql8;        // DIAG: listed qubit b = 8..15 in bits [8 (b - 8), 8 (b - 8) + 8)
+  uint64_t pad2;
 };
 static_assert(sizeof(NzOp) == 32, "NzOp is 32 bytes");
+
+// listed qubit b of a DIAG or PAULI record
+__host__ __device__ __forceinline__ uint32_t nz_qubit(const NzOp& o, uint32_t b) {
+  const uint32_t w = b < 4u ? o.cmask : b < 8u ? o.cval : (uint32_t)(o.ql8 >> (b < 12u ? 0 : 32));
+  return (w >> (8u * (b & 3u))) & 255u;
+}
 
 // Philox-4x32-10 streams (counter word 1): every random number is a pure function of (seed, shot, stream, draw)
 enum { NZ_STREAM_PAULI = 0, NZ_STREAM_SAMPLE = 1, NZ_STREAM_READOUT = 2 };
@@ -52,18 +62,22 @@ struct NzMeas {
   const int* pos;           // device: bit j <- qubit pos[j] (< 0: stays 0), n entries
 };
 
-struct NzLaunch {
+// what every launch of a trajectory kernel takes
+struct NzCall {
   hipStream_t stream;
   int W;
-  int n_cu;
-  int max_grid;             // 0: as many workgroups as the chip holds at once
   const NzOp* d_ops;        // device copies
   int n_ops;
-  bool kraus;               // the stream holds an NZ_KRAUS op: a kernel instantiation that knows the kind is launched
   const double* d_pool;
   uint64_t shots, seed;
   NzMeas meas;
   uint64_t* d_out;
+};
+
+struct NzLaunch : NzCall {
+  int n_cu;
+  int max_grid;             // 0: as many workgroups as the chip holds at once
+  bool kraus;               // the stream holds an NZ_KRAUS op: a kernel instantiation that knows the kind is launched
 };
 
 // launches the trajectory kernel on l.stream (asynchronous); the workgroup count used goes to *grid

@@ -128,6 +128,31 @@ def test_wide_cases_every_word(name):
             assert sample(eng, c).max() < 2 ** c["W"]
 
 
+# ---- a diagonal over more than 8 qubits: list positions 8..15 sit in the record's second word ----------------------------------
+
+def long_diag_program(W, k, b):
+    """H on every qubit, DIAG over a seeded permutation of k qubits with table[j] = (-1)^(bit b of j), H on every qubit:
+    the state ends in 1 << qubits[b], whatever is drawn"""
+    qubits = [int(q) for q in np.random.default_rng(5).permutation(W)[:k]]
+    table = 1.0 - 2.0 * ((np.arange(2 ** k) >> b) & 1)
+    hs = [ir.op_u(q, kc._H) for q in range(W)]
+    return program.encode(hs + [ir.op_diag(qubits, table.astype(complex))] + hs), 1 << qubits[b]
+
+
+@pytest.mark.parametrize("W,k,b", [(13, 13, 0), (13, 13, 7), (13, 13, 8), (13, 13, 12), (16, 16, 8), (16, 16, 15)])
+def test_diag_over_more_than_8_qubits_reads_the_second_word(W, k, b):
+    (rec, data), want = long_diag_program(W, k, b)
+    assert int(rec["n"][W]) == k > 8
+    with _lib.Engine(W) as eng:
+        paths = [("hbm", eng.noisy_sample_hbm)] + ([("lds", eng.noisy_sample)] if W <= 13 else [])
+        for name, fn in paths:
+            for grid in (1, 0):
+                eng.set_option("noisy_grid", grid)
+                got = fn(rec, data, 8, 23)
+                assert (got == want).all(), "%s noisy_grid=%d: expected %#x, states seen %s" % (
+                    name, grid, want, sorted(set(int(g) for g in got))[:4])
+
+
 # ---- forced Paulis at W = 20: plain equality ------------------------------------------------------------------------------------
 
 @pytest.mark.parametrize("qubits", [(0,), (16,), (19,), (19, 0), (0, 19), (16, 15), (15, 16)])
