@@ -253,10 +253,14 @@ enum {
   QSV_OP_PAULI,     /* random Pauli on qubits[0..n) (n <= 2), qsv_noisy_sample only: data_off points to the 4^n
                        CUMULATIVE probabilities; Pauli index p holds for error qubit j the x bit (p >> 2j) & 1 and
                        the z bit (p >> 2j+1) & 1 -- (x,z) = (0,0) I, (1,0) X, (0,1) Z, (1,1) Y               */
-  QSV_OP_KRAUS = 10 /* one-qubit Kraus channel of m = vals[0] operators (1 <= m <= 4) on qubits[0] (n = 1),
+  QSV_OP_KRAUS = 10,/* one-qubit Kraus channel of m = vals[0] operators (1 <= m <= 4) on qubits[0] (n = 1),
                        qsv_noisy_sample only: data_off points to m x 8 doubles, each K_k row-major with (re, im) pairs as
                        for QSV_OP_1Q, followed by m x 4 doubles, E_k = K_k^dg K_k as (E00, E11, Re E01, Im E01).  Per
                        shot one k is drawn with weight <psi|E_k|psi> and K_k applied, the state keeping its mass. */
+  QSV_OP_MEASURE = 11 /* measurement of qubits[0] (n = 1) taken when it occurs, qsv_noisy_sample only: vals[0] = the classical
+                       bit c it writes (0 <= c < 64), vals[1] = release (0 or 1: hand the qubit back in |0>), data_off points
+                       to 2 doubles, P(flip | 0) and P(flip | 1) (always present; zeros: no readout error).  The contract
+                       is below, next to the one of QSV_OP_KRAUS. */
 };
 
 /* scheduling hint from the planner: close the current multi-gate pass before this gate (the
@@ -275,7 +279,7 @@ typedef struct {
   double   angle;                  /* MCPHASE                                              */
 } qsv_op;
 
-/* run a whole program in one call (one ctypes crossing per circuit); QSV_OP_PAULI and QSV_OP_KRAUS are refused */
+/* run a whole program in one call (one ctypes crossing per circuit); QSV_OP_PAULI, QSV_OP_KRAUS and QSV_OP_MEASURE are refused */
 int qsv_exec(qsv_handle* h, const qsv_op* ops, int n_ops, const double* data, uint64_t n_data);
 
 /* ---- noisy shots: one trajectory per shot ------------------------------------------------ */
@@ -288,12 +292,24 @@ int qsv_exec(qsv_handle* h, const qsv_op* ops, int n_ops, const double* data, ui
  * state from |amp|^2, and records it as qsv_sample does:
  * out_bits[s] bit j = the value of qubit meas_qubits[j] (-1: bit j stays 0; NULL: the full basis index), each
  * measured bit flipped with probability readout[2j + value] (NULL: no readout error).
- * Kinds: INIT_ZERO, INIT_UNIFORM, 1Q, MCX, DIAG, MCPHASE, PAULI, KRAUS; anything else returns QSV_E_UNSUPPORTED.
+ * Kinds: INIT_ZERO, INIT_UNIFORM, 1Q, MCX, DIAG, MCPHASE, PAULI, KRAUS, MEASURE; anything else returns QSV_E_UNSUPPORTED.
  * A KRAUS record on qubit t: u = the next draw of stream 0 (PAULI and KRAUS records share one draw counter, which
  * advances at every such record, m = 1 included); r00 = sum |a_i0|^2, r11 = sum |a_i1|^2, r10 = sum a_i1 conj(a_i0) over
  * the pairs (a_i0, a_i1) of t, total = r00 + r11; w_k = E00_k r00 + E11_k r11 + 2 Re(E01_k r10); the first k with w_k > 0
  * whose inclusive cumulative sum of the positive w exceeds u total is taken (none: the last k with w_k > 0), and every
  * pair is multiplied by K_k sqrt(total / w_k).
+ * A MEASURE record on qubit t with classical bit c: the channel K_0 = |0><0|, K_1 = |1><1| (release: |0><1|) plus one recorded
+ * bit.  u = the draw (seed, shot, stream 3, d), d = the ordinal of the record among the MEASURE records of the program; the
+ * draw counter of stream 0 does NOT advance, so a shot meets the same Pauli and Kraus draws whether its measurements are
+ * deferred or taken in place.  r00, r11 and total as for KRAUS.  The outcome b = 0 if r00 > 0 and r00 > u total, otherwise
+ * b = 1 if r11 > 0, else b = 0 (the KRAUS rule with w_0 = r00, w_1 = r11); a state without mass stays as it is, with b = 0.
+ * The other half of every pair is set to zero and the kept half multiplied by sqrt(total / w_b); with release = 1 and
+ * b = 1 the kept half moves to the 0 half, so that the qubit is back in |0>.  Bit c of the shot's word is cleared, then
+ * set to b, flipped iff the draw (seed, shot, stream 2, c) -- the draw the final readout takes for bit c, so the readout draw
+ * of a bit does not depend on when it was measured -- is below flip[b].  A later MEASURE record may write the same bit
+ * again.  The final word is the word of the final draw ORed with these bits.  QSV_E_BADARG, with a message that names the
+ * op: meas_qubits == NULL (full-index words) together with a MEASURE record, c >= n_meas, meas_qubits[c] >= 0 for a bit a
+ * MEASURE record writes, a flip outside [0, 1], a release flag other than 0 or 1.
  * Random numbers are Philox-4x32-10 draws keyed by the seed and counted by (shot, stream, draw): shot s of a call
  * is the same whatever the number of shots or the grid.  Runs on the handle's stream (qsv_timer_* bracket it).
  * Replaces: simulator.run(T, shots=SHOTS, noise_model=...) of an Aer noise model of Pauli and one-qubit Kraus errors. */
@@ -328,7 +344,7 @@ int qsv_noisy_sample_hbm(qsv_handle* h, const qsv_op* ops, int n_ops, const doub
  * U rho U^dg (the record on the ket bits and its mirror on the bra bits -- qubits + W, matrix and table conjugated, angle
  * negated -- through the sweeps of qsv_exec), QSV_OP_PAULI as sum_p P(p) P rho P^dg with P(p) the differences of the
  * record's cumulative table, QSV_OP_KRAUS as sum_k K_k rho K_k^dg (its E tables are not read).
- * Kinds: INIT_ZERO, INIT_UNIFORM, 1Q, MCX, DIAG, MCPHASE, PAULI (n = 1, 2), KRAUS (n = 1, 1..4 operators); MUX, KQ, SWAP and
+ * Kinds: INIT_ZERO, INIT_UNIFORM, 1Q, MCX, DIAG, MCPHASE, PAULI (n = 1, 2), KRAUS (n = 1, 1..4 operators); MUX, KQ, SWAP, MEASURE and
  * handles of several shards or ranks return QSV_E_UNSUPPORTED; an odd n_qubits or a record qubit >= W QSV_E_BADARG.  Every
  * record is checked before the first one runs.
  * Replaces: simulator.run(T, noise_model=..., method="density_matrix") of Qiskit Aer. */

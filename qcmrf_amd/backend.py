@@ -25,6 +25,7 @@ from .comm import SingleProcess
 _METHODS = ("statevector", "trajectory", "density_matrix")
 _WALKS = ("depth", "levels")
 _NOISY_STATES = ("lds", "hbm", "auto")
+_NOISY_MEASURES = ("deferred", "in_place", "auto")
 DENSITY_MAX_CLBITS = 20       # method="density_matrix" returns 2^k probabilities over the k written classical bits
 
 _NAMES = ("qasm_simulator", "aer_simulator", "aer_simulator_statevector", "statevector_simulator",
@@ -156,14 +157,20 @@ class QsvBackend:
                 runs the ideal path
     noisy_state where a noisy shot keeps its state: 'lds' (default: on-chip memory, W <= 13) | 'hbm' (a slot of device
                 memory per resident shot, ``qsv_noisy_sample_hbm``, W <= 24; the same draws and words) | 'auto' ('lds' up to
-                13 qubits, 'hbm' above)
+                13 qubits, 'hbm' above); resolved on the live width when the measurements are taken in place
+    noisy_measure  when a noisy shot measures: 'deferred' (default: every measurement at the end, one qubit per clique ancilla,
+                W = n + m + 1 for a QCMRF circuit) | 'in_place' (a mid-circuit measurement is taken when it occurs, as one
+                QSV_OP_MEASURE record, and its qubit recycled: n + 2 live qubits for any number of cliques; the trailing
+                measurements stay one joint final draw; same limits: <= 64 classical bits, no reset, no gate after a
+                measure, no classical conditions) | 'auto' (in place iff that makes the state narrower).  A shot's Pauli,
+                Kraus and readout draws are the same in both; 'density_matrix' stays deferred
     """
 
     def __init__(self, name="qasm_simulator", **options):
         self._name = name
         self.options = {"fusion": 3, "layout": "auto", "devices": (0,), "comm": None, "device": 0,
                         "profile": False, "engine_options": None, "method": "statevector", "fold_fresh": True,
-                        "gather_counts": "root", "noise_model": None, "noisy_state": "lds",
+                        "gather_counts": "root", "noise_model": None, "noisy_state": "lds", "noisy_measure": "deferred",
                         "trajectory_walk": None, "trajectory_slots": None, "trajectory_trace": None}
         self.options.update(options)
         self._engine = None
@@ -266,7 +273,12 @@ class QsvBackend:
         state = opts.get("noisy_state", "lds")
         if state not in _NOISY_STATES:
             raise ValueError("unknown noisy_state %r; a noisy shot keeps its state in %s" % (state, ", ".join(_NOISY_STATES)))
+        nmeasure = opts.get("noisy_measure", "deferred")
+        if nmeasure not in _NOISY_MEASURES:
+            raise ValueError("unknown noisy_measure %r; a noisy shot takes its measurements %s" % (nmeasure, ", ".join(_NOISY_MEASURES)))
         if method == "density_matrix":
+            if nmeasure == "in_place":
+                raise ValueError("method='density_matrix' defers every measurement; noisy_measure='in_place' belongs to noisy shots")
             model = self._density_model_of(opts)
             from concurrent.futures import ThreadPoolExecutor
             with ThreadPoolExecutor(max_workers=1) as pool:     # host compile of circuit i+1 while the device evolves circuit i
@@ -282,11 +294,11 @@ class QsvBackend:
             # host compile of circuit i+1 on a helper thread while the device runs the shots of circuit i
             from concurrent.futures import ThreadPoolExecutor
             with ThreadPoolExecutor(max_workers=1) as pool:
-                nxt = pool.submit(self._prepare_noisy, circs[0], model, state)
+                nxt = pool.submit(self._prepare_noisy, circs[0], model, state, nmeasure)
                 for i in range(len(circs)):
                     prepared = nxt.result()
                     if i + 1 < len(circs):
-                        nxt = pool.submit(self._prepare_noisy, circs[i + 1], model, state)
+                        nxt = pool.submit(self._prepare_noisy, circs[i + 1], model, state, nmeasure)
                     exps.append(self._run_noisy(circs[i], int(shots), int(seed_simulator) + i, opts, prepared))
             return Job(Result(exps, self._name))
         if len(circs) > 1 and opts.get("method", "statevector") == "statevector":
@@ -326,20 +338,31 @@ class QsvBackend:
         return model
 
     @staticmethod
-    def _prepare_noisy(circuit, model, state="lds"):
-        """host half of a noisy run: ingest with the model's Pauli and Kraus ops (identity layout) + encode; ``state`` is
-        the run option noisy_state, returned resolved ('lds' or 'hbm')"""
-        t0 = time.perf_counter()
-        ing = _ingest.ingest(circuit, noise=model)
+    def _resolve_noisy_state(state, width, what):
+        """the run option noisy_state resolved ('lds' or 'hbm') for a per-shot state of ``width`` qubits"""
         if state == "auto":
-            state = "lds" if ing.num_qubits <= _lib.NOISY_MAX_QUBITS else "hbm"
-        if state == "lds" and ing.num_qubits > _lib.NOISY_MAX_QUBITS:
-            raise ValueError("noisy runs keep one state per shot in on-chip memory: at most %d qubits, the circuit has %d "
+            state = "lds" if width <= _lib.NOISY_MAX_QUBITS else "hbm"
+        if state == "lds" and width > _lib.NOISY_MAX_QUBITS:
+            raise ValueError("noisy runs keep one state per shot in on-chip memory: at most %d qubits, the circuit has %d%s "
                              "(noisy_state='hbm' or 'auto' keeps it in device memory: at most %d qubits)"
-                             % (_lib.NOISY_MAX_QUBITS, ing.num_qubits, _lib.NOISY_HBM_MAX_QUBITS))
-        if state == "hbm" and ing.num_qubits > _lib.NOISY_HBM_MAX_QUBITS:
+                             % (_lib.NOISY_MAX_QUBITS, width, what, _lib.NOISY_HBM_MAX_QUBITS))
+        if state == "hbm" and width > _lib.NOISY_HBM_MAX_QUBITS:
             raise ValueError("noisy runs with noisy_state='hbm' keep one state per shot in device memory: at most %d qubits, "
-                             "the circuit has %d" % (_lib.NOISY_HBM_MAX_QUBITS, ing.num_qubits))
+                             "the circuit has %d%s" % (_lib.NOISY_HBM_MAX_QUBITS, width, what))
+        return state
+
+    @staticmethod
+    def _prepare_noisy(circuit, model, state="lds", measure="deferred"):
+        """host half of a noisy run: ingest with the model's Pauli and Kraus ops (identity layout) + encode; ``state`` and
+        ``measure`` are the run options noisy_state and noisy_measure, returned resolved ('lds' or 'hbm'; 'deferred' or
+        'in_place')"""
+        t0 = time.perf_counter()
+        if measure != "deferred":
+            prepared = QsvBackend._prepare_noisy_in_place(circuit, model, state, measure == "auto", t0)
+            if prepared is not None:
+                return prepared
+        ing = _ingest.ingest(circuit, noise=model)
+        state = QsvBackend._resolve_noisy_state(state, ing.num_qubits, "")
         if ing.num_clbits > 64:
             raise ValueError("noisy runs record at most 64 classical bits, the circuit has %d" % ing.num_clbits)
         rec, data = program.encode(ing.ops)
@@ -349,17 +372,57 @@ class QsvBackend:
         for c in clist:
             meas[c] = ing.measure[c]
             readout[c] = ing.readout.get(c, (0.0, 0.0))
-        return ing, rec, data, clist, meas, readout, time.perf_counter() - t0, state
+        return ing, rec, data, clist, meas, readout, time.perf_counter() - t0, state, ("deferred", ing.num_qubits, 0)
+
+    @staticmethod
+    def _prepare_noisy_in_place(circuit, model, state, only_if_narrower, t0):
+        """``_prepare_noisy`` with the mid-circuit measurements taken when they occur: the ops of the deferred ingest, Pauli
+        and Kraus ops included, in their order and remapped to live slots (``trajectory.plan_slots``), every mid-circuit
+        measure a "measure" op (one QSV_OP_MEASURE record, its flips those of the measured logical qubit), the trailing
+        ones one joint final draw through ``meas`` (-1 for the bits written earlier).  None: ``only_if_narrower`` and the
+        live width is the circuit's"""
+        from . import ir, trajectory
+        ing = _ingest.ingest(circuit, noise=model, keep_measures=True)
+        if ing.num_clbits > 64:
+            raise ValueError("noisy runs record at most 64 classical bits, the circuit has %d" % ing.num_clbits)
+        staged, width, finals = trajectory.plan_slots(ing.ops)
+        width = max(width, 1)
+        if only_if_narrower and width >= ing.num_qubits:
+            return None
+        state = QsvBackend._resolve_noisy_state(state, width, " live at once with its measurements taken in place")
+        early = {item[2] for item in staged if item[0] == "measure"}
+        late = [(s, c) for s, c in finals if c in early]    # a bit written earlier and again at the end: a record as well, so
+        finals = [(s, c) for s, c in finals if c not in early]   # that the last write wins
+        ops, n_measure = [], 0
+        for item in staged:
+            if item[0] == "ops":
+                ops += item[1]
+            else:
+                _, s, c, release, q = item
+                ops.append(ir.Op("measure", target=s, mask=c, vals=(int(release),), table=model.readout_flips(q)))
+                n_measure += 1
+        for s, c in late:
+            ops.append(ir.Op("measure", target=s, mask=c, vals=(0,), table=ing.readout.get(c)))
+            n_measure += 1
+        ing.ops = ops
+        rec, data = program.encode(ops)
+        clist = sorted(ing.measure)
+        meas = [-1] * (clist[-1] + 1) if clist else []
+        readout = np.zeros((len(meas), 2))
+        for s, c in finals:
+            meas[c] = s
+            readout[c] = ing.readout.get(c, (0.0, 0.0))
+        return ing, rec, data, clist, meas, readout, time.perf_counter() - t0, state, ("in_place", width, n_measure)
 
     def _run_noisy(self, circuit, shots, seed, opts, prepared):
         """one qsv_noisy_sample (or qsv_noisy_sample_hbm) call: shots trajectories, sampled and read out on the device"""
-        ing, rec, data, clist, meas, readout, t_compile, state = prepared
+        ing, rec, data, clist, meas, readout, t_compile, state, (nmeasure, width, n_measure) = prepared
         t1 = time.perf_counter()
         t0 = t1 - t_compile
         counts = {}
         t2 = t1
         if clist and shots > 0:
-            eng = self._get_engine(ing.num_qubits, dict(opts, comm=None, devices=tuple(opts["devices"])[:1]))
+            eng = self._get_engine(width, dict(opts, comm=None, devices=tuple(opts["devices"])[:1]))
             self._apply_engine_options(eng, opts)
             sample = eng.noisy_sample_hbm if state == "hbm" else eng.noisy_sample
             bits = sample(rec, data, shots, seed, meas, readout if ing.readout else None)
@@ -367,7 +430,8 @@ class QsvBackend:
             uv, uc = np.unique(bits, return_counts=True)
             counts = _format_keys(uv, uc, ing.num_clbits, ing.creg_sizes)
         t3 = time.perf_counter()
-        meta = {"method": "noisy", "noisy_state": state, "n_qubits": ing.num_qubits, "n_source_ops": ing.n_source_ops, "n_device_ops": len(rec),
+        meta = {"method": "noisy", "noisy_state": state, "noisy_measure": nmeasure, "n_qubits": width,
+                "n_circuit_qubits": ing.num_qubits, "n_measure_ops": n_measure, "n_source_ops": ing.n_source_ops, "n_device_ops": len(rec),
                 "n_pauli_ops": ing.n_pauli, "n_kraus_ops": ing.n_kraus, "readout_errors": len(ing.readout), "time_compile": t1 - t0,
                 "time_evolve": t2 - t1, "time_sample": t3 - t2, "time_taken": t3 - t0, "seed_simulator": seed}
         self.last_engine = None          # no resident state: every shot had its own

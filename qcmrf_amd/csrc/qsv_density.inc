@@ -114,6 +114,8 @@ extern "C" int qsv_density_exec(qsv_handle* h, const qsv_op* ops, int n_ops, con
           if (!std::isfinite(data[o.data_off + j])) return fail(QSV_E_BADARG, "op %d: Kraus entry %d is not finite", i, j);
         break;
       }
+      case QSV_OP_MEASURE:
+        return fail(QSV_E_UNSUPPORTED, "op %d: QSV_OP_MEASURE (a measurement taken in place) runs in qsv_noisy_sample only; the density-matrix method defers every measurement", i);
       case QSV_OP_MUX: case QSV_OP_KQ: case QSV_OP_SWAP:
         return fail(QSV_E_UNSUPPORTED, "op %d: kind %d is not supported by the density-matrix method (INIT, 1Q, MCX, DIAG, MCPHASE, PAULI, KRAUS only)", i, o.kind);
       default:

@@ -136,6 +136,8 @@ extern "C" int qsv_exec(qsv_handle* h, const qsv_op* ops, int n_ops, const doubl
         return fail(QSV_E_BADARG, "op %d: QSV_OP_PAULI (a random Pauli) runs in qsv_noisy_sample only, not in qsv_exec", i);
       case QSV_OP_KRAUS:
         return fail(QSV_E_BADARG, "op %d: QSV_OP_KRAUS (a Kraus channel) runs in qsv_noisy_sample only, not in qsv_exec", i);
+      case QSV_OP_MEASURE:
+        return fail(QSV_E_BADARG, "op %d: QSV_OP_MEASURE (a measurement taken in place) runs in qsv_noisy_sample only, not in qsv_exec", i);
       default:
         return fail(QSV_E_BADARG, "op %d: unknown kind %d", i, o.kind);
     }
@@ -201,11 +203,14 @@ static int nz_check_meas(qsv_handle* h, const int* meas_qubits, int n_meas, cons
   return QSV_OK;
 }
 
-// validates every record and appends its compact form to cops, its tables to pool
-static int nz_encode(qsv_handle* h, const qsv_op* ops, int n_ops, const double* data, uint64_t n_data, std::vector<NzOp>& cops,
-                     NzPool& pool, bool* has_kraus) {
+// validates every record and appends its compact form to cops, its tables to pool; a MEASURE record is checked against the
+// measurement map it writes beside (meas_qubits, n_meas)
+static int nz_encode(qsv_handle* h, const qsv_op* ops, int n_ops, const double* data, uint64_t n_data, const int* meas_qubits,
+                     int n_meas, std::vector<NzOp>& cops, NzPool& pool, bool* has_kraus, bool* has_measure) {
   cops.reserve(n_ops);
   *has_kraus = false;
+  *has_measure = false;
+  uint32_t n_measure = 0;
   for (int i = 0; i < n_ops; ++i) {
     const qsv_op& o = ops[i];
     if (o.n < 0 || o.n > QSV_MAX_CTRL) return fail(QSV_E_BADARG, "op %d: n=%d out of range", i, o.n);
@@ -296,8 +301,29 @@ static int nz_encode(qsv_handle* h, const qsv_op* ops, int n_ops, const double* 
         *has_kraus = true;
         break;
       }
+      case QSV_OP_MEASURE: {
+        if (o.n != 1) return fail(QSV_E_BADARG, "op %d: QSV_OP_MEASURE measures 1 qubit, not %d", i, o.n);
+        CHK(check_qubit(h, o.qubits[0], "QSV_OP_MEASURE"));
+        if (!meas_qubits) return fail(QSV_E_BADARG, "op %d: QSV_OP_MEASURE writes a classical bit and needs meas_qubits (full-index words have none)", i);
+        const int cb = o.vals[0], release = o.vals[1];
+        if (cb < 0 || cb >= 64 || cb >= n_meas)
+          return fail(QSV_E_BADARG, "op %d: QSV_OP_MEASURE writes classical bit %d, outside the %d bits of the call", i, cb, n_meas < 64 ? n_meas : 64);
+        if (meas_qubits[cb] >= 0)
+          return fail(QSV_E_BADARG, "op %d: QSV_OP_MEASURE writes classical bit %d, which the final draw writes too (meas_qubits[%d] = %d, not -1)", i, cb, cb, meas_qubits[cb]);
+        if (release != 0 && release != 1) return fail(QSV_E_BADARG, "op %d: QSV_OP_MEASURE release flag %d is not 0 or 1", i, release);
+        CHK(need(2));
+        for (int j = 0; j < 2; ++j)
+          if (!(d[j] >= 0.0 && d[j] <= 1.0)) return fail(QSV_E_BADARG, "op %d: QSV_OP_MEASURE flip probability %d = %g not in [0, 1]", i, j, d[j]);
+        c.kind = NZ_MEASURE;
+        c.target = (uint8_t)o.qubits[0];
+        c.cmask = (uint32_t)cb | ((uint32_t)release << 8);
+        c.cval = n_measure++;                              // the draw number of stream NZ_STREAM_MEASURE
+        c.off = pool.put(d, 2);
+        *has_measure = true;
+        break;
+      }
       default:
-        return fail(QSV_E_UNSUPPORTED, "op %d: kind %d is not supported by noisy shots (INIT, 1Q, MCX, DIAG, MCPHASE, PAULI, KRAUS only)", i, o.kind);
+        return fail(QSV_E_UNSUPPORTED, "op %d: kind %d is not supported by noisy shots (INIT, 1Q, MCX, DIAG, MCPHASE, PAULI, KRAUS, MEASURE only)", i, o.kind);
     }
     cops.push_back(c);
   }
@@ -338,9 +364,10 @@ static int nz_stage(Shard& s, const std::vector<NzOp>& cops, const std::vector<d
 
 // records -> compact records, pool and measurement map of one call
 static int nz_prepare(qsv_handle* h, const qsv_op* ops, int n_ops, const double* data, uint64_t n_data, const int* meas_qubits,
-                      int n_meas, const double* readout, std::vector<NzOp>& cops, NzPool& pool, bool* has_kraus, NzMeas* meas) {
+                      int n_meas, const double* readout, std::vector<NzOp>& cops, NzPool& pool, bool* has_kraus, bool* has_measure,
+                      NzMeas* meas) {
   CHK(nz_check_meas(h, meas_qubits, n_meas, readout));
-  CHK(nz_encode(h, ops, n_ops, data, n_data, cops, pool, has_kraus));
+  CHK(nz_encode(h, ops, n_ops, data, n_data, meas_qubits, n_meas, cops, pool, has_kraus, has_measure));
   meas->n = meas_qubits ? n_meas : -1;
   meas->readout = -1;
   meas->pos = nullptr;
@@ -361,9 +388,9 @@ static int nz_run(qsv_handle* h, const qsv_op* ops, int n_ops, const double* dat
   if (h->W > max_w) return fail(QSV_E_BADARG, "noisy shots keep one %d-qubit state per trajectory in %s: at most %d qubits", h->W, where, max_w);
   std::vector<NzOp> cops;
   NzPool pool;
-  bool has_kraus = false;
+  bool has_kraus = false, has_measure = false;
   NzCall c;
-  CHK(nz_prepare(h, ops, n_ops, data, n_data, meas_qubits, n_meas, readout, cops, pool, &has_kraus, &c.meas));
+  CHK(nz_prepare(h, ops, n_ops, data, n_data, meas_qubits, n_meas, readout, cops, pool, &has_kraus, &has_measure, &c.meas));
   if (shots == 0) return QSV_OK;
   Shard& s = h->shards[0];
   CHK(shard_set(s));
@@ -378,6 +405,7 @@ static int nz_run(qsv_handle* h, const qsv_op* ops, int n_ops, const double* dat
   c.seed = seed;
   c.meas.pos = st.pos;
   c.d_out = st.out;
+  c.measure = has_measure;
   const int rc = launch(s, c, has_kraus);
   hipError_t e = hipSuccess;
   if (rc == QSV_OK) e = hipMemcpyAsync(out_bits, c.d_out, shots * sizeof(uint64_t), hipMemcpyDeviceToHost, s.stream);

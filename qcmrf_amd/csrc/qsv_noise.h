@@ -9,7 +9,7 @@
 #define QSV_NZ_WAVE_MAXW 10       // up to here one wavefront per trajectory (no workgroup barriers)
 #define QSV_NZ_KRAUS_1PAIR_MAXW 7 // up to here a lane owns at most one pair of a Kraus op's target (2^6 pairs, 64 lanes)
 
-enum { NZ_INIT = 0, NZ_1Q, NZ_MCX, NZ_DIAG, NZ_MCPHASE, NZ_PAULI, NZ_KRAUS };
+enum { NZ_INIT = 0, NZ_1Q, NZ_MCX, NZ_DIAG, NZ_MCPHASE, NZ_PAULI, NZ_KRAUS, NZ_MEASURE };
 
 // One op of the compact stream, 32 bytes: every trajectory reads the whole list, so a record is a quarter of an
 // L2 line instead of the 168 bytes of a qsv_op.  Both paths read this record: qubits < 256, masks of 32 bits (the slot path
@@ -18,13 +18,14 @@ enum { NZ_INIT = 0, NZ_1Q, NZ_MCX, NZ_DIAG, NZ_MCPHASE, NZ_PAULI, NZ_KRAUS };
 // (nz_fetch): DIAG and PAULI have no controls, and their first 8 listed qubits take the place of cmask and cval.
 struct NzOp {
   uint32_t kind : 8;   // NZ_*.  Bit fields of one word: the record's first 16 bytes have no hole and load as one piece
-  uint32_t target : 8; // 1Q, MCX, KRAUS
+  uint32_t target : 8; // 1Q, MCX, KRAUS, MEASURE
   uint32_t n : 16;     // DIAG, PAULI: number of listed qubits; KRAUS: number of operators (1..4)
   uint32_t cmask;      // control qubits (1Q, MCX, MCPHASE: all its qubits); NZ_INIT: the uniform mask.  DIAG, PAULI: listed
   uint32_t cval;       // qubits 0..3 / values the control bits must have.  DIAG, PAULI: listed qubits 4..7, 8 bits each
+                       // MEASURE: cmask = classical bit | release << 8, cval = the record's ordinal among the MEASURE records
   uint32_t off;        // into the pool (doubles): 1Q 8 = m00 m01 m10 m11; DIAG 2^n complex; MCPHASE (cos, sin);
                        // INIT the amplitude value; PAULI 4^n cumulative probabilities; KRAUS n x 8 = the K_k as 1Q, then
-                       // n x 4 = (E00, E11, Re E01, Im E01) of E_k = K_k^dg K_k
+                       // n x 4 = (E00, E11, Re E01, Im E01) of E_k = K_k^dg K_k; MEASURE 2 = P(flip | 0), P(flip | 1)
   uint64_t ql8;        // DIAG: listed qubit b = 8..15 in bits [8 (b - 8), 8 (b - 8) + 8)
   uint64_t pad2;
 };
@@ -37,7 +38,7 @@ __host__ __device__ __forceinline__ uint32_t nz_qubit(const NzOp& o, uint32_t b)
 }
 
 // Philox-4x32-10 streams (counter word 1): every random number is a pure function of (seed, shot, stream, draw)
-enum { NZ_STREAM_PAULI = 0, NZ_STREAM_SAMPLE = 1, NZ_STREAM_READOUT = 2 };
+enum { NZ_STREAM_PAULI = 0, NZ_STREAM_SAMPLE = 1, NZ_STREAM_READOUT = 2, NZ_STREAM_MEASURE = 3 };
 
 // the draw itself, in [0, 1): 53 bits of counter (draw, stream, shot lo, shot hi) under the 64-bit seed
 __device__ __forceinline__ double philox_u01(uint64_t seed, uint64_t shot, uint32_t stream, uint32_t draw) {
@@ -72,6 +73,7 @@ struct NzCall {
   uint64_t shots, seed;
   NzMeas meas;
   uint64_t* d_out;
+  bool measure;             // the stream holds an NZ_MEASURE op: a kernel instantiation that knows the kind is launched
 };
 
 struct NzLaunch : NzCall {
@@ -82,3 +84,5 @@ struct NzLaunch : NzCall {
 
 // launches the trajectory kernel on l.stream (asynchronous); the workgroup count used goes to *grid
 hipError_t qsv_noise_launch(const NzLaunch& l, unsigned* grid);
+// the same for a stream that holds an NZ_MEASURE op (qsv_noise_measure.hip); qsv_noise_launch comes here by itself
+hipError_t qsv_noise_launch_measure(const NzLaunch& l, unsigned* grid);

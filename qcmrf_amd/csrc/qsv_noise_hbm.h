@@ -16,3 +16,5 @@ struct NzHbmLaunch : NzCall {
 hipError_t qsv_noise_hbm_resident(int n_cu, uint64_t* workgroups);
 // launches the trajectory kernel on l.stream (asynchronous)
 hipError_t qsv_noise_hbm_launch(const NzHbmLaunch& l);
+// the same for a stream that holds an NZ_MEASURE op (qsv_noise_measure.hip); qsv_noise_hbm_launch comes here by itself
+hipError_t qsv_noise_hbm_launch_measure(const NzHbmLaunch& l);

@@ -156,6 +156,24 @@ __device__ __forceinline__ bool kraus_pick(double r00, double r11, double rre, d
   return true;
 }
 
+// The operator of a MEASURE record (the contract is in include/qsv.h, QSV_OP_MEASURE) for the draw u: the Kraus rule with
+// K_0 = |0><0|, K_1 = |1><1| (release: |0><1|), so w_0 = r00 and w_1 = r11.  Returns the outcome b and m = K_b sqrt(total / w_b);
+// -1: the state has no mass and stays as it is (the recorded outcome is then 0).  Every lane holds the same r00, r11 and u.
+__device__ __forceinline__ int measure_pick(double r00, double r11, double u, bool release, cplx& m00, cplx& m01, cplx& m10,
+                                            cplx& m11) {
+  const double total = r00 + r11, r = u * total;
+  int b = (r00 > 0.0 && r00 > r) ? 0 : (r11 > 0.0 ? 1 : 0);
+  const double w = b ? r11 : r00;
+  if (!(w > 0.0)) return -1;
+  b = __builtin_amdgcn_readfirstlane(b);                           // uniform: the selects below are scalar
+  const double s = sqrt(total / w);
+  m00 = m01 = m10 = m11 = make_double2(0.0, 0.0);
+  if (b == 0) m00.x = s;
+  else if (release) m01.x = s;                                     // the kept half moves to the 0 half: the slot is back in |0>
+  else m11.x = s;
+  return b;
+}
+
 // One Kraus channel on one trajectory (the contract is in include/qsv.h, QSV_OP_KRAUS): r = the reduced density matrix
 // of the target summed over all pairs, then every pair times the operator kraus_pick draws.  TPB 64 (W <= 10): a lane owns
 // at most R pairs and keeps them in registers between the reduction and the apply, so the op reads and writes the state
@@ -164,9 +182,11 @@ __device__ __forceinline__ bool kraus_pick(double r00, double r11, double rre, d
 // unused): 16 pairs per thread at W = 13 would take 128 registers, so the pairs are read again, B loads in flight; a thread
 // sums its pairs in index order (a batch's pairs past the end are zeros), the waves' sums cross through static LDS and every
 // thread adds them in wave order.  The caller's barrier after the op also fences that scratch.
-template <int TPB, int B, int R>
-__device__ __forceinline__ void kraus_op(cplx* st, const NzOp& o, const double* __restrict__ pool, uint32_t half, uint32_t tid,
-                                         double u) {
+// MEAS: the record may also be a MEASURE record, which shares everything but the pick (measure_pick).  Returns the outcome of
+// a MEASURE record (0 for a KRAUS record), -1 for a state without mass.
+template <int TPB, int B, int R, bool MEAS = false>
+__device__ __forceinline__ int kraus_op(cplx* st, const NzOp& o, const double* __restrict__ pool, uint32_t half, uint32_t tid,
+                                        double u) {
   const uint32_t tb = 1u << o.target, lo = tb - 1u;
   cplx a0[R], a1[R];
   double r00 = 0.0, r11 = 0.0, rre = 0.0, rim = 0.0;               // r10 = sum a1 conj(a0) = rre + i rim
@@ -221,7 +241,11 @@ __device__ __forceinline__ void kraus_op(cplx* st, const NzOp& o, const double* 
     for (int w = 1; w < NW; ++w) { r00 += part[w][0]; r11 += part[w][1]; rre += part[w][2]; rim += part[w][3]; }
   }
   cplx m00, m01, m10, m11;
-  if (!kraus_pick(r00, r11, rre, rim, u, o, pool, m00, m01, m10, m11)) return;
+  int b = 0;
+  if (MEAS && o.kind == NZ_MEASURE) {
+    b = measure_pick(r00, r11, u, (o.cmask >> 8) & 1u, m00, m01, m10, m11);
+    if (b < 0) return -1;
+  } else if (!kraus_pick(r00, r11, rre, rim, u, o, pool, m00, m01, m10, m11)) return -1;
   if constexpr (TPB == 64) {
 #pragma unroll
     for (int j = 0; j < R; ++j) {
@@ -239,16 +263,37 @@ __device__ __forceinline__ void kraus_op(cplx* st, const NzOp& o, const double* 
                     n1 = cmad(m10, b0, cmul(m11, b1));
                   });
   }
+  return b;
 }
 
 // One record on one trajectory of N amplitudes, by the TPB threads of its workgroup, and the workgroup barrier that has to
 // follow before the state is read again.  PAULI and KRAUS records take the next draw of the shot's stream NZ_STREAM_PAULI
 // (draw advances at every one of them, whatever is drawn); an identity Pauli leaves the state as it is and skips the barrier.
 // KRAUS > 0: the kind is known, and at TPB 64 a lane holds KRAUS pairs (kraus_op).
-template <int TPB, int B, int KRAUS>
+// MEAS: MEASURE records are known too (KRAUS > 0 with it: the op is built on kraus_op, and one copy of it serves both kinds).
+// A MEASURE record draws from its own stream NZ_STREAM_MEASURE, numbered by the record's ordinal, so `draw` does not advance;
+// it writes its bit, flipped by the readout draw nz_word would take for it, into `word`, which every thread holds alike.
+template <int TPB, int B, int KRAUS, bool MEAS = false>
 __device__ __forceinline__ void nz_apply(cplx* st, uint32_t N, const NzOp& o, const double* __restrict__ pool, uint32_t tid,
-                                         uint64_t seed, uint64_t shot, uint32_t& draw) {
+                                         uint64_t seed, uint64_t shot, uint32_t& draw, uint64_t& word) {
   const uint32_t half = N >> 1;
+  if constexpr (MEAS) {
+    static_assert(KRAUS > 0, "a kernel that knows MEASURE records knows KRAUS records");
+    if (o.kind == NZ_MEASURE || o.kind == NZ_KRAUS) {
+      const bool meas = o.kind == NZ_MEASURE;
+      const double u = philox_u01(seed, shot, meas ? NZ_STREAM_MEASURE : NZ_STREAM_PAULI, meas ? o.cval : draw);
+      if (!meas) ++draw;
+      const int k = kraus_op<TPB, B, KRAUS, true>(st, o, pool, half, tid, u);
+      if (meas) {
+        const uint32_t c = o.cmask & 63u;
+        uint32_t bit = k > 0 ? 1u : 0u;
+        if (philox_u01(seed, shot, NZ_STREAM_READOUT, c) < pool[o.off + bit]) bit ^= 1u;
+        word = (word & ~(1ull << c)) | ((uint64_t)bit << c);
+      }
+      __syncthreads();
+      return;
+    }
+  }
   const auto all = [](uint32_t) { return true; };
   const uint32_t cmask = o.cmask, cval = o.cval;
   const auto ctrl = [=](uint32_t i) { return (i & cmask) == cval; };
@@ -314,7 +359,7 @@ __device__ __forceinline__ void nz_apply(cplx* st, uint32_t N, const NzOp& o, co
       break;
     }
     case NZ_KRAUS:
-      if constexpr (KRAUS > 0) kraus_op<TPB, B, KRAUS>(st, o, pool, half, tid, philox_u01(seed, shot, NZ_STREAM_PAULI, draw++));
+      if constexpr (KRAUS > 0 && !MEAS) kraus_op<TPB, B, KRAUS>(st, o, pool, half, tid, philox_u01(seed, shot, NZ_STREAM_PAULI, draw++));
       break;
     default: break;
   }

@@ -17,6 +17,9 @@ pauli    qubits, table              random Pauli (noise models, trajectory runs 
                                     index p, error qubit j = qubits[j] (x bit p >> 2j & 1, z bit p >> 2j+1 & 1; qcmrf_amd.noise)
 kraus    qubits, table              one-qubit Kraus channel on qubits[0] (noise models, trajectory runs only): table is the stack
                                     of its m <= 4 operators, shape (m, 2, 2); one is drawn per shot with weight <psi|K^dg K|psi>
+measure  target, mask, vals, table  measurement of ``target`` into classical bit ``mask`` when it occurs (ingest with keep_measures).
+                                    For noisy runs that measure in place: vals = (release,), the slot handed back in |0>, and
+                                    table = (P(flip | 0), P(flip | 1)) of the measured logical qubit (None: no readout error)
 """
 from __future__ import annotations
 

@@ -93,6 +93,14 @@ def encode(ops):
             if flat is None:
                 flat = kraus_seen[id(op.table)] = kraus_tables(ks)
             r["data_off"] = put_real(flat)
+        elif k == "measure":
+            c, release = int(op.mask), int(bool(op.vals[0])) if len(op.vals) else 0
+            if not 0 <= c < 64:
+                raise ValueError("a measure op records into classical bit %d; noisy runs hold bits 0..63" % c)
+            r["kind"] = _lib.OP_MEASURE
+            fill(r, [op.target], [c])
+            r["vals"][1] = release
+            r["data_off"] = put_real(measure_flips(op.table))
         else:
             raise ValueError("cannot encode op kind %r" % k)
     data = np.concatenate(pool) if pool else np.zeros(0, dtype=np.float64)
@@ -108,6 +116,14 @@ def pauli_cumulative(probs, n):
     cum = np.cumsum(p)
     cum[int(np.flatnonzero(p > 0)[-1]):] = 1.0
     return cum
+
+
+def measure_flips(flips):
+    """QSV_OP_MEASURE data: (P(flip | 0), P(flip | 1)) of the measured (logical) qubit's readout error, zeros for none"""
+    f = np.zeros(2) if flips is None else np.asarray(flips, dtype=np.float64).ravel()
+    if f.size != 2 or not ((f >= 0.0) & (f <= 1.0)).all():
+        raise ValueError("a measure op carries two flip probabilities in [0, 1], got %r" % (flips,))
+    return f
 
 
 def kraus_tables(ks):

@@ -17,7 +17,8 @@ P1 after every ``sx``, ``x`` and ``id``, P2 after every ``cx``, a symmetric read
 ``--t1 US --t2 US --gate-time NS1,NS2`` adds thermal relaxation (T1 and T2 in microseconds): over NS1 nanoseconds after
 every ``sx``, ``x`` and ``id``, over NS2 on both qubits of every ``cx``, each composed with the depolarizing error of
 the gate when that is given too.  The circuits are then always lowered to {cx,id,rz,sx,x} (by ``qcmrf_amd.transpile`` when Qiskit is absent) so that those gates exist,
-and the counts go to ``result_simulation_noisy_<SCALE>.json``.
+and the counts go to ``result_simulation_noisy_<SCALE>.json``.  ``--noisy-measure in_place`` (or ``auto``) takes the clique
+ancillas' measurements when they occur and recycles their qubits: n + 2 live qubits per shot instead of n + m + 1.
 
 ``--method density_matrix`` evolves every circuit exactly as a density matrix (noisy or not): the counts are drawn from the
 exact distributions, and those are written as well, one ``{bitstring: p}`` per circuit, to ``probs_simulation_<SCALE>.json``
@@ -49,6 +50,9 @@ def main(argv=None):
     ap.add_argument("--gate-time", default=None, metavar="NS1,NS2", help="duration of sx/x/id and of cx in nanoseconds")
     ap.add_argument("--method", default=None, choices=["density_matrix"],
                     help="density_matrix: exact distributions (probs_simulation_*.json) next to the counts drawn from them")
+    ap.add_argument("--noisy-measure", default=None, choices=["deferred", "in_place", "auto"],
+                    help="noisy run: take every measurement at the end (deferred, the default) or mid-circuit ones when they occur, "
+                         "their qubits recycled (in_place; auto: in place iff that makes the per-shot state narrower)")
     args = ap.parse_args(argv)
     model = ibm_like_model(args.depolarizing, args.readout, args.t1, args.t2, args.gate_time)
 
@@ -79,6 +83,8 @@ def main(argv=None):
     extra = {} if model is None else {"noise_model": model}
     if args.method is not None:
         extra["method"] = args.method
+    if args.noisy_measure is not None:
+        extra["noisy_measure"] = args.noisy_measure
     result = simulator.run(CIRCS, shots=args.shots, seed_simulator=args.seed_simulator, **extra).result()
     counts = result.get_counts()
     dt = time.perf_counter() - t0

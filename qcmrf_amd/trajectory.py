@@ -42,16 +42,19 @@ def _live_plan(ops, n_qubits):
     return first, last
 
 
-def compile_trajectory(circuit, fusion=3):
-    """-> (segments, width, final_measures [(slot, clbit)], num_clbits, creg_sizes, n_source_ops)"""
-    ing = _ingest.ingest(circuit, peephole=fusion >= 1, keep_measures=True)
-    ops = ing.ops
-    first, last = _live_plan(ops, ing.num_qubits)
+def plan_slots(ops):
+    """The slot plan of a gate list with "measure" ops, shared by trajectory mode and by noisy runs that measure in place.
+
+    Every logical qubit gets a slot at its first use; a measure releases its slot iff it is the last thing that happens to
+    its qubit, and the lowest freed slot is handed out again first.  Returns (staged, width, final_measures): ``staged``
+    alternates ("ops", [ops remapped to slots]) and ("measure", slot, clbit, release, logical qubit) and ends with an "ops"
+    entry; the trailing measures (nothing but measures after them) are taken out of it and listed as ``final_measures``
+    [(slot, clbit)], to be sampled jointly from the final state; ``width`` is the number of slots in use at once."""
+    first, last = _live_plan(ops, None)
     # a measure is a release point iff it is the last thing that happens to its qubit
     slot_of, free, next_slot = {}, [], 0
     width = 0
-    segments, cur = [], []
-    pending_release = []                       # slots freed by the measure that closed the previous segment
+    cur = []
     final_measures = []
 
     def slot(q):
@@ -72,13 +75,13 @@ def compile_trajectory(circuit, fusion=3):
                   angle=op.angle, label=op.label)
         return o
 
-    staged = []                                # (kind, payload) in order: ("ops", [...]) / ("measure", slot, clbit, release)
+    staged = []                                # in order: ("ops", [...]) / ("measure", slot, clbit, release, logical qubit)
     for k, op in enumerate(ops):
         if op.kind == "measure":
             s = slot(op.target)
             release = last[op.target] == k
             staged.append(("ops", cur))
-            staged.append(("measure", s, op.mask, release))
+            staged.append(("measure", s, op.mask, release, op.target))
             cur = []
             if release:
                 del slot_of[op.target]
@@ -90,8 +93,15 @@ def compile_trajectory(circuit, fusion=3):
     # trailing measures (nothing but measures after them) are sampled jointly from the final state
     while len(staged) >= 2 and staged[-1][0] == "ops" and not staged[-1][1] and staged[-2][0] == "measure":
         staged.pop()
-        _, s, c, _ = staged.pop()
+        _, s, c, _, _ = staged.pop()
         final_measures.insert(0, (s, c))
+    return staged, width, final_measures
+
+
+def compile_trajectory(circuit, fusion=3):
+    """-> (segments, width, final_measures [(slot, clbit)], num_clbits, creg_sizes, n_source_ops)"""
+    ing = _ingest.ingest(circuit, peephole=fusion >= 1, keep_measures=True)
+    staged, width, final_measures = plan_slots(ing.ops)
     # fuse every segment with the ordinary exact passes (no init folding after the first one)
     segs = []
     first_seg = True
@@ -122,7 +132,7 @@ def compile_trajectory(circuit, fusion=3):
                     pre.append(ir.op_x(prev.measure_slot))
                 sg.prog[outcome] = program.encode(pre + list(fused))
         if i + 1 < len(staged):
-            _, s, c, rel = staged[i + 1]
+            _, s, c, rel, _ = staged[i + 1]
             sg.measure_slot, sg.measure_clbit, sg.release = s, c, rel
         segs.append(sg)
         i += 2
