@@ -406,11 +406,16 @@ int qsv_timer_end(qsv_handle* h, double* ms);
  *   passes      multi_r [5]        register targets of a k_multi pass at most (0: one kernel per gate)
  *               general_r [4]      ... of a GENERAL pass (masked X / 2x2 / phase, register selects); its tile width
  *               general_light_r [5] tile width a general pass with little arithmetic is padded to
- *               pass_max_ops [64]  ops per pass at most        pass_budget [0]   arithmetic cap of a general pass, % of one sweep
+ *               pass_max_ops [56]  ops per pass at most        pass_budget [0]   arithmetic cap of a general pass, % of one sweep
  *               lane_targets [1]   targets < 6 ride on lane bits (wave shuffles)   dyn_lanes [3]  lane bits 3..5 lent per pass
  *               lane_map [1]       lane bit 5 on address bit 11 when the tile allows (2: only a tile on bits 6..10; 0: never)    pass_hints [1]  honour QSV_OPF_NEW_PASS
  *               xframe [1]         uncontrolled X = XOR on store addresses / pending across passes (never a data move)
  *               single_shortcut [1] a one-op pass runs as its dedicated kernel     trace_passes [0]  one stderr line per pass
+ *               general_combos [1] general pass: controls on workgroup-uniform bits resolved per workgroup on the host (combo table)
+ *               fold_init_h [1]    H on a still-|0> qubit right after an init is part of the init write.  The one knob that can
+ *                                  decide WHETHER a program runs: folded, an H on a shard-bit qubit needs no data movement; with 0
+ *                                  the same record is a dense gate on a shard bit and qsv_exec returns QSV_E_UNSUPPORTED (swap the
+ *                                  qubit to a local position first).  Where both run, the results agree.
  *   generator   init_prod [1]      init x diagonal factors in one write-only pass   init_prod_r [0 = by shard size], init_prod_bit0 [0 = by size]
  *                                  init_prod_grid [0 = every workgroup the chip holds at once; else at most this many]
  *                                  init_prod_group [-1 = up to 3 group bits; 0 = one tile per group; 1..4 = that many]

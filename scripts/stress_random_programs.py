@@ -35,8 +35,9 @@ def sample_violations(eng, got, shots, seed, exact):
 
 
 
-def run(n_cases=300, seed=7, verbose=True, only=None, override=None, widths=(14, 15, 16, 17), poison=False, sample_shots=0):
-    """returns the number of mismatching programs.  sample_shots: words drawn from every program (seed from the case number)
+def run(n_cases=300, seed=7, verbose=True, only=None, override=None, widths=(14, 15, 16, 17), poison=False, sample_shots=0,
+        n_ops=(3, 26)):
+    """returns the number of mismatching programs.  n_ops: (low, high) of the number of ops drawn per program, high excluded.  sample_shots: words drawn from every program (seed from the case number)
     and checked shot by shot; a violated rule counts as a mismatch.  widths: state sizes drawn from; at >= 21 qubits the
     workgroups of a pass no longer run all at once (in-place permutations that cross workgroups show)"""
     rs = np.random.RandomState(seed)
@@ -63,7 +64,7 @@ def run(n_cases=300, seed=7, verbose=True, only=None, override=None, widths=(14,
                 mask |= 1 << q
         if rs.rand() < 0.7 or style == 3:
             ops.append(ir.op_init(mask))
-        for _ in range(int(rs.randint(3, 26))):
+        for _ in range(int(rs.randint(n_ops[0], n_ops[1]))):
             k = rs.randint(0, 10)
             qs = [int(x) for x in rs.permutation(W)[:4]]
             L = W - (P.bit_length() - 1)
@@ -115,6 +116,11 @@ def run(n_cases=300, seed=7, verbose=True, only=None, override=None, widths=(14,
                 "lane_map_min_l": int(rs.choice([26, 14, 14])),
                 "kq_variant": int(rs.choice([-1, -1, 0, 3, 5, 6, 8])), "kq_order": int(rs.choice([1, 1, 0, 2, 4])),
                 "kq3_tile": int(rs.choice([1, 1, 0, 2])), "defer_state": int(rs.choice([-1, 1, 1, 0]))}
+        # options added later come from a generator of their own, keyed by (seed, case): the programs and the options above
+        # of every logged (seed, case) stay what they were
+        rs2 = np.random.RandomState([int(seed) & 0xffffffff, case])
+        opts.update({"general_combos": int(rs2.choice([1, 1, 0])), "fold_init_h": int(rs2.choice([1, 1, 0])),
+                     "lowctl_mask": int(rs2.choice([1, 1, 0])), "single_shortcut": int(rs2.choice([1, 1, 1, 0]))})
         if only is not None and (case != only if only >= 0 else case < -only):
             continue                                       # replay mode (CASE, or -CASE: from that case on): the generator state advances, nothing runs
         if override:

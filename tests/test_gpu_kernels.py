@@ -662,6 +662,19 @@ def test_random_programs_differential_wide_states():
     assert mod.run(40, 3, verbose=False, widths=(21, 22, 23)) == 0
 
 
+def test_random_programs_long_passes():
+    """30 random programs of 60 to 126 ops with pass_max_ops = 200: general passes of up to 112 ops and the ops that ride
+    along at a program's end, i.e. the second mask word of the combo table, with the random options (general_combos,
+    fold_init_h, lowctl_mask and single_shortcut among them)"""
+    import importlib.util
+    import os
+    from conftest import ROOT
+    spec = importlib.util.spec_from_file_location("stress_random_programs", os.path.join(ROOT, "scripts", "stress_random_programs.py"))
+    mod = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(mod)
+    assert mod.run(30, 11, verbose=False, override={"pass_max_ops": 200}, n_ops=(60, 127)) == 0
+
+
 @pytest.mark.parametrize("P", [1, 2])
 def test_x_frame_on_block_bits_of_a_state_wider_than_one_wave_of_workgroups(lib, P):
     """An uncontrolled X rides in a pass as an XOR on the STORE addresses -- race-free only for bits inside
