@@ -397,6 +397,14 @@ int qsv_state_info(qsv_handle* h, int* deferred, uint64_t* realize_calls, uint64
  * pass left none). */
 int qsv_tile_sums(qsv_handle* h, int shard, double* out, uint64_t cap, uint64_t* n);
 
+/* How the generator formed the tile sums local shard `shard` holds (option sums_factored).  A factor that touches block
+ * bits only is tile-uniform: one weight for a whole tile.  The other factors (inner) read the tile index through the
+ * block bits they touch, the set D.  Factored, the 256-thread sums ran over the 2^|D| tiles that differ in D, and every
+ * tile's sum is that sum times its tile-uniform weights.  *factored: 1 if the last sums launch ran that way; *d_bits:
+ * |D|; *inner_factors, *uniform_factors: the split of the factor list (reported whichever path ran).  Read only; any
+ * out pointer may be NULL.  QSV_E_BADARG when the shard's tile sums are not valid or were not left by the generator. */
+int qsv_tile_sums_info(qsv_handle* h, int shard, int* factored, int* d_bits, int* inner_factors, int* uniform_factors);
+
 /* HIP-event stopwatch on shard 0's stream: begin records, end records+synchronises */
 int qsv_timer_begin(qsv_handle* h);
 int qsv_timer_end(qsv_handle* h, double* ms);
@@ -421,6 +429,9 @@ int qsv_timer_end(qsv_handle* h, double* ms);
  *                                  init_prod_group [-1 = up to 3 group bits; 0 = one tile per group; 1..4 = that many]
  *                                  defer_state [-1]  the generator as a program's last pass, leaving tile sums, stores nothing (qsv_state_info):
  *                                  -1 from 30 local qubits, 0 never, 1 always
+ *                                  sums_factored [-1]  the generator's tile sums from the 2^|D| tiles its inner factors tell apart,
+ *                                  times the tile-uniform factors' weights (qsv_tile_sums_info): -1 where that removes at least 3
+ *                                  tile-index bits, 1 at least one, 0 never (the sums differ by rounding only, within the same bound)
  *   memory      nontemporal [-1], multi_nt [-1], init_prod_nt [-1]   non-temporal loads/stores: -1 by shard size, 0 never, 1 always
  *   measurement cache_sums [1], fused_sums [1]   keep / produce per-tile |amp|^2 sums in the last pass of a program
  *   kernels     unroll [4], lowt_shuffle [1], pair_variant [0], kq_mfma [1], blocks_per_cu [65536]

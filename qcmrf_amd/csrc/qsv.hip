@@ -172,6 +172,10 @@ struct Shard {
   // sums left behind by the last k_multi pass of a program, one per workgroup tile (no read pass)
   double* d_tsums = nullptr;
   size_t tsums_cap = 0;
+  double* d_inner = nullptr;     // the 2^|D| sums of a factored generator sums launch (option sums_factored): grown on demand, kept
+  size_t inner_cap = 0;          // ... in doubles
+  bool sums_from_gen = false;    // d_tsums was last written by the generator's sums launch; sums_info describes it:
+  int sums_info[4] = {0, 0, 0, 0};   // factored, |D|, inner factors, tile-uniform factors (qsv_tile_sums_info)
   double* d_super = nullptr;     // one sum per QSV_SUPER tiles (device) ...
   double* h_tsums = nullptr;     // ... and their pinned host copy, valid until the state changes
   size_t h_tsums_cap = 0;
@@ -253,6 +257,7 @@ struct qsv_handle {
   int opt_init_prod_nt = -1;          // generator with non-temporal stores: -1 by shard size, 0 never, 1 always
   int opt_init_prod_grid = 0;         // workgroups of the persistent generator: 0 = as many as the chip holds, else at most this many
   int opt_defer_state = -1;           // the generator as a program's last pass leaves tile sums only, the state deferred: -1 from QSV_DEFER_MIN_L local qubits, 0 never, 1 always
+  int opt_sums_factored = -1;         // the generator's sums launch over the tiles that differ in an inner factor only, expanded by the tile-uniform factors: -1 where that removes at least QSV_FACTORED_MIN_BITS (3) tile-index bits, 0 never, 1 where it removes at least one
   int opt_init_prod_group = -1;       // group bits of the generator (2^B tiles per workgroup step): -1 auto (up to 3), 0 off, 1..4 that many
   int opt_xframe = 1;                 // uncontrolled X gates inside a pass become an XOR on its store addresses
   int opt_trace_passes = 0;           // 1: one stderr line per k_multi pass (R, mode, ops by update shape) -- a diagnostic
@@ -291,6 +296,21 @@ static int arena_put(Shard& s, const void* src, size_t bytes, void** dptr, void*
   void* d = dst ? dst : s.d_arena + s.arena_top;
   HIPCHK(hipMemcpyAsync(d, s.h_arena + s.arena_top, bytes, hipMemcpyHostToDevice, s.stream));
   *dptr = d;
+  s.arena_top += slot;
+  return QSV_OK;
+}
+
+// a slot of the arena's pinned half alone, filled from src: for a kernel that reads it in place (the pinned half is
+// device-visible); valid until the arena wraps, which waits for the stream first
+static int arena_stage(Shard& s, const void* src, size_t bytes, void** hptr) {
+  const size_t slot = (bytes + 255) & ~size_t(255);
+  if (slot > s.arena_bytes) return fail(QSV_E_BADARG, "table of %zu bytes exceeds arena", bytes);
+  if (s.arena_top + slot > s.arena_bytes) {
+    HIPCHK(hipStreamSynchronize(s.stream));
+    s.arena_top = 0;
+  }
+  memcpy(s.h_arena + s.arena_top, src, bytes);
+  *hptr = s.h_arena + s.arena_top;
   s.arena_top += slot;
   return QSV_OK;
 }
@@ -439,6 +459,7 @@ extern "C" int qsv_destroy(qsv_handle* h) {
     if (s.xstream) { hipStreamSynchronize(s.xstream); hipStreamDestroy(s.xstream); }
     if (s.d_sblk) { hipFree(s.d_sblk); hipFree(s.d_sres); hipFree(s.d_sout); }
     if (s.d_tsums) hipFree(s.d_tsums);
+    if (s.d_inner) hipFree(s.d_inner);
     if (s.d_red) hipFree(s.d_red);
     if (s.d_noisy) hipFree(s.d_noisy);
     if (s.recipe.d_buf) hipFree(s.recipe.d_buf);

@@ -519,6 +519,17 @@ extern "C" int qsv_tile_sums(qsv_handle* h, int shard, double* out, uint64_t cap
   HIPCHK(hipStreamSynchronize(s.stream));
   return QSV_OK;
 }
+extern "C" int qsv_tile_sums_info(qsv_handle* h, int shard, int* factored, int* d_bits, int* inner_factors, int* uniform_factors) {
+  if (!h) return fail(QSV_E_BADARG, "NULL handle");
+  if (shard < 0 || shard >= (int)h->shards.size()) return fail(QSV_E_BADARG, "shard %d of %zu", shard, h->shards.size());
+  const Shard& s = h->shards[shard];
+  if (!s.tile_valid || !s.sums_from_gen) return fail(QSV_E_BADARG, "the last pass on shard %d was no generator leaving tile sums", shard);
+  if (factored) *factored = s.sums_info[0];
+  if (d_bits) *d_bits = s.sums_info[1];
+  if (inner_factors) *inner_factors = s.sums_info[2];
+  if (uniform_factors) *uniform_factors = s.sums_info[3];
+  return QSV_OK;
+}
 extern "C" int qsv_timer_begin(qsv_handle* h) {
   if (!h) return fail(QSV_E_BADARG, "NULL handle");
   Shard& s = h->shards[0];
@@ -562,6 +573,7 @@ extern "C" int qsv_set_option(qsv_handle* h, const char* name, int value) {
   else if (!strcmp(name, "multi_nt")) h->opt_multi_nt = value;
   else if (!strcmp(name, "init_prod_nt")) h->opt_init_prod_nt = value;
   else if (!strcmp(name, "init_prod_grid")) { if (value < 0) return fail(QSV_E_BADARG, "init_prod_grid < 0"); h->opt_init_prod_grid = value; }
+  else if (!strcmp(name, "sums_factored")) { if (value < -1 || value > 1) return fail(QSV_E_BADARG, "sums_factored must be -1 (auto), 0 or 1"); h->opt_sums_factored = value; }
   else if (!strcmp(name, "defer_state")) { if (value < -1 || value > 1) return fail(QSV_E_BADARG, "defer_state must be -1 (auto), 0 or 1"); h->opt_defer_state = value; }
   else if (!strcmp(name, "init_prod_group")) { if (value < -1 || value > QSV_PROD_MAXG) return fail(QSV_E_BADARG, "init_prod_group must be -1 (auto) or 0..4"); h->opt_init_prod_group = value; }
   else if (!strcmp(name, "pass_max_ops")) { if (value < 1 || value > 512) return fail(QSV_E_BADARG, "pass_max_ops out of range"); h->opt_pass_max_ops = value; }

@@ -705,6 +705,9 @@ struct ProdFactor {
 struct ProdCounts { int nouter; int ngrp; int nsingle[QSV_MULTI_MAXR]; int nmulti; int nmixed; int nfac; int nlmax; };
 // the group bits: nb tile-index bits, positions ascending (nb = 0: one tile per group)
 struct ProdGroup { int nb; int tpos[QSV_PROD_MAXG]; };
+// k_prod_sums' walk and output: nsum sums are written (the tile count, or 2^|D| of a factored launch); the
+// tile-index bits tfix are held at 0 (none, or the bits outside D); cpos = the group bits' positions in the output index
+struct ProdWalk { uint64_t nsum; uint64_t tfix; int cpos[QSV_PROD_MAXG]; };
 
 // wave-uniform part of one factor's table index: bit e <- bit wbit[e] of the wave index (NE >= the longest list)
 template <int NE>
@@ -981,8 +984,8 @@ __device__ __forceinline__ double lanes_fold(double x, double y) {
 template <int R, bool REGSUM>
 __global__ __launch_bounds__(QSV_TPB) void k_prod_sums(uint64_t ntiles, BitIns ins, RegPos rp, LanePos lp,
                                                        const ProdFactor* __restrict__ fac, ProdCounts cnt, ProdGroup grp,
-                                                       const cplx* __restrict__ tables, int ntab, uint64_t nonmask,
-                                                       double initval, double* __restrict__ tile_sums) {
+                                                       ProdWalk wk, const cplx* __restrict__ tables, int ntab,
+                                                       uint64_t nonmask, double initval, double* __restrict__ tile_sums) {
 #pragma clang fp contract(off)
   constexpr int NWB = (QSV_MULTI_MAXLIST + 3) / 4;
   constexpr int NV = 8;                           // tiles of a group reduced together
@@ -1027,37 +1030,40 @@ __global__ __launch_bounds__(QSV_TPB) void k_prod_sums(uint64_t ntiles, BitIns i
   unsigned nreg = 0;                              // register bits that nonmask makes zero
 #pragma unroll
   for (int c = 0; c < R; ++c) if ((nonmask >> rp.pos[c]) & 1ull) nreg |= 1u << c;
-  // the walk over groups in tile index, as in k_init_prod; tnon: the tile-index bits whose block address bit is in nonmask
-  uint64_t gt[QSV_PROD_MAXG];
-  uint64_t tholes = 0, tnon = 0;
+  // the walk over groups, as in k_init_prod, twice: in tile index (tile0: the group bits and the bits wk.tfix are holes
+  // held at 0) and in the index of the sums written (out0: the group bits at wk.cpos are its only holes).  Without
+  // wk.tfix the two are the same number.  tnon: the tile-index bits whose block address bit is in nonmask
+  uint64_t gc[QSV_PROD_MAXG];
+  uint64_t tholes = wk.tfix, choles = 0, tnon = 0;
 #pragma unroll
   for (int i = 0; i < QSV_PROD_MAXG; ++i) {
-    gt[i] = i < grp.nb ? 1ull << grp.tpos[i] : 0ull;
-    tholes |= gt[i];
+    gc[i] = i < grp.nb ? 1ull << wk.cpos[i] : 0ull;
+    choles |= gc[i];
+    tholes |= i < grp.nb ? 1ull << grp.tpos[i] : 0ull;
   }
   for (uint64_t t = 1; t < ntiles; t <<= 1) if (tile_base_blk(t, ins, lp) & nonmask) tnon |= t;
-  auto spread = [&](uint64_t x) -> uint64_t {     // group index -> tile index of its first tile
-    for (int i = 0; i < grp.nb; ++i) {
-      const int p = grp.tpos[i];
-      x = ((x >> p) << (p + 1)) | (x & ((1ull << p) - 1ull));
-    }
-    return x;
+  auto spread = [](uint64_t x, uint64_t holes) -> uint64_t {   // group index -> index of its first tile: x's bits fill the positions outside holes
+    uint64_t o = 0;
+    for (int p = 0; x && p < 64; ++p)
+      if (!((holes >> p) & 1ull)) { o |= (x & 1ull) << p; x >>= 1; }
+    return o;
   };
-  auto sub = [&](uint32_t b) -> uint64_t {        // tile b of a group: its group bits
+  auto sub = [&](uint32_t b) -> uint64_t {        // tile b of a group: its group bits in the output index
     uint64_t o = 0;
 #pragma unroll
-    for (int i = 0; i < QSV_PROD_MAXG; ++i) if ((b >> i) & 1u) o |= gt[i];
+    for (int i = 0; i < QSV_PROD_MAXG; ++i) if ((b >> i) & 1u) o |= gc[i];
     return o;
   };
   auto ldw = [&](uint32_t o) -> double { return *reinterpret_cast<const double*>(ltb + o); };
-  const uint64_t ngroups = ntiles >> grp.nb;
-  const uint64_t dtile = spread(gridDim.x);
-  uint64_t tile0 = spread(blockIdx.x);
+  const uint64_t ngroups = wk.nsum >> grp.nb;
+  const uint64_t dtile = spread(gridDim.x, tholes), dout = spread(gridDim.x, choles);
+  uint64_t tile0 = spread(blockIdx.x, tholes), out0 = spread(blockIdx.x, choles);
   __shared__ double wpart[2][1 << QSV_PROD_MAXG][QSV_TPB / 64];
   int par = 0;
-  for (uint64_t gi = blockIdx.x; gi < ngroups; gi += gridDim.x, tile0 = ((tile0 | tholes) + dtile) & ~tholes) {
+  for (uint64_t gi = blockIdx.x; gi < ngroups; gi += gridDim.x, tile0 = ((tile0 | tholes) + dtile) & ~tholes,
+                                                out0 = ((out0 | choles) + dout) & ~choles) {
     if (tile0 & tnon) {                            // the whole group is zero (uniform: no barrier crossed)
-      if ((int)threadIdx.x < nsub) tile_sums[tile0 | sub(threadIdx.x)] = 0.0;
+      if ((int)threadIdx.x < nsub) tile_sums[out0 | sub(threadIdx.x)] = 0.0;
       continue;
     }
     // wave-uniform parts of the group's first tile: lane k holds factor k's (and k + 64's) table offset, in bytes
@@ -1217,9 +1223,65 @@ __global__ __launch_bounds__(QSV_TPB) void k_prod_sums(uint64_t ntiles, BitIns i
     __syncthreads();                               // two buffers: one barrier per group orders both uses of one
     const int t = threadIdx.x;
     if (t < nsub)
-      tile_sums[tile0 | sub((uint32_t)t)] = (wpart[par][t][0] + wpart[par][t][1]) + (wpart[par][t][2] + wpart[par][t][3]);
+      tile_sums[out0 | sub((uint32_t)t)] = (wpart[par][t][0] + wpart[par][t][1]) + (wpart[par][t][2] + wpart[par][t][3]);
     par ^= 1;
   }
+}
+
+// ---------------------------------------------------------------------------------------
+// k_tile_sums_expand: every tile's sum from the sums of a factored k_prod_sums launch.  A factor that
+// touches block bits only has one weight for all 256 threads of a tile, so it leaves the tile's sum:
+//     tile_sums[t] = inner[t compacted over D] x the tile-uniform factors' weights at t, in list order
+// with D (dmask) the tile-index bits the other factors read; 0.0 where t hits tnon (the tile-index bits of nonmask).
+// One thread per tile, coalesced stores.  Once per workgroup the tile-uniform factors' weights go to LDS as
+// w = fma(re, re, im * im), the expression of k_prod_sums, nothing contracted.  A tile's sum is a function of its index
+// and the factor list only, never of the grid.  Exact zeros stay exact.
+// ---------------------------------------------------------------------------------------
+struct ExpandFactor {
+  int nlist;                        // table index bit e <- tile-index bit tbit[e]
+  int tab;                          // its table in the launch's tables, complex128 units
+  int lds;                          // its weights in LDS, doubles
+  unsigned char tbit[QSV_MULTI_MAXLIST];
+};
+__global__ __launch_bounds__(QSV_TPB) void k_tile_sums_expand(uint64_t ntiles, uint64_t dmask, uint64_t tnon,
+                                                              const ExpandFactor* __restrict__ fac, int nuni, int nw,
+                                                              const cplx* __restrict__ tables,
+                                                              const double* __restrict__ inner,
+                                                              double* __restrict__ tile_sums) {
+#pragma clang fp contract(off)
+  extern __shared__ double4 lds_raw[];
+  double* lw = reinterpret_cast<double*>(lds_raw);
+  ExpandFactor* lf = reinterpret_cast<ExpandFactor*>(lw + nw);
+  for (int u = 0; u < nuni; ++u) {
+    const ExpandFactor f = fac[u];
+    for (int i = threadIdx.x; i < (1 << f.nlist); i += QSV_TPB) { const cplx t = tables[f.tab + i]; lw[f.lds + i] = fma(t.x, t.x, t.y * t.y); }
+    if (threadIdx.x == 0) lf[u] = f;
+  }
+  __syncthreads();
+  const uint64_t stride = (uint64_t)gridDim.x * QSV_TPB;
+  for (uint64_t t = (uint64_t)blockIdx.x * QSV_TPB + threadIdx.x; t < ntiles; t += stride) {
+    double v = 0.0;
+    if (!(t & tnon)) {
+      uint64_t c = 0;
+      int k = 0;
+      for (uint64_t m = dmask; m; m &= m - 1) { c |= ((t >> __builtin_ctzll(m)) & 1ull) << k; ++k; }   // uniform: scalar
+      v = inner[c];
+      for (int u = 0; u < nuni; ++u) {
+        uint32_t j = 0;
+        for (int e = 0; e < lf[u].nlist; ++e) j |= (uint32_t)((t >> lf[u].tbit[e]) & 1ull) << e;
+        v *= lw[lf[u].lds + j];
+      }
+    }
+    tile_sums[t] = v;
+  }
+}
+
+// qsv_sample: the shots' (block, residual) pairs from the shard's pinned staging arena to the device, read by the
+// compute queue itself (no copy engine: see qsv_sample)
+__global__ __launch_bounds__(QSV_TPB) void k_stage_shots(const uint64_t* __restrict__ hblk, const double* __restrict__ hres,
+                                                         uint64_t* __restrict__ dblk, double* __restrict__ dres, uint64_t n) {
+  const uint64_t stride = (uint64_t)gridDim.x * QSV_TPB;
+  for (uint64_t i = (uint64_t)blockIdx.x * QSV_TPB + threadIdx.x; i < n; i += stride) { dblk[i] = hblk[i]; dres[i] = hres[i]; }
 }
 
 // zero tracking epilogue: amplitudes with any bit of zmask set were never written; make them 0

@@ -150,8 +150,22 @@ extern "C" int qsv_sample(qsv_handle* h, uint64_t shots, uint64_t seed, const in
         HIPCHK(hipMalloc(&sh.d_sres, sh.sample_cap * sizeof(double)));
         HIPCHK(hipMalloc(&sh.d_sout, sh.sample_cap * sizeof(uint64_t)));
       }
-      HIPCHK(hipMemcpyAsync(sh.d_sblk, blk.data(), cnt * sizeof(uint64_t), hipMemcpyHostToDevice, sh.stream));
-      HIPCHK(hipMemcpyAsync(sh.d_sres, res.data(), cnt * sizeof(double), hipMemcpyHostToDevice, sh.stream));
+      // The shots' (block, residual) pairs go to the device through the pinned arena and a kernel that reads it, not as
+      // two copies from pageable memory: those are staged copies on a copy engine, each with a host wait, and the first
+      // one after event timing has been switched on stalls for 8-20 ms inside the runtime (profiles/r09_factored_sums.log)
+      // -- once per process, but a step is 2.5 ms.  Lists beyond a quarter of the arena take the copies as before.
+      if (2 * cnt * sizeof(uint64_t) <= sh.arena_bytes / 4) {
+        void* hb = nullptr;
+        void* hr = nullptr;
+        CHK(arena_stage(sh, blk.data(), cnt * sizeof(uint64_t), &hb));
+        CHK(arena_stage(sh, res.data(), cnt * sizeof(double), &hr));
+        hipLaunchKernelGGL(k_stage_shots, dim3((unsigned)std::min<uint64_t>((cnt + QSV_TPB - 1) / QSV_TPB, 1024)), dim3(QSV_TPB), 0, sh.stream,
+                           reinterpret_cast<const uint64_t*>(hb), reinterpret_cast<const double*>(hr), sh.d_sblk, sh.d_sres, cnt);
+        HIPCHK(hipGetLastError());
+      } else {
+        HIPCHK(hipMemcpyAsync(sh.d_sblk, blk.data(), cnt * sizeof(uint64_t), hipMemcpyHostToDevice, sh.stream));
+        HIPCHK(hipMemcpyAsync(sh.d_sres, res.data(), cnt * sizeof(double), hipMemcpyHostToDevice, sh.stream));
+      }
       if (bs.super) {                     // (super block, mass) -> (tile, mass) on the device
         hipLaunchKernelGGL(k_locate_super, dim3((unsigned)std::min<uint64_t>(cnt, 65535)), dim3(64), 0, sh.stream,
                            sh.d_tsums, sh.tile_nblocks, sh.d_sblk, sh.d_sres, cnt);

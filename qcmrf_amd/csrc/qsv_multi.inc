@@ -203,6 +203,10 @@ static bool group_is_init_product(const qsv_handle* h, const PendingGroup& g) {
 
 #define QSV_GEN_NT_MIN_L 30
 #define QSV_DEFER_MIN_L 30        // option defer_state = -1: local qubits from which the final generator leaves sums only (DESIGN §5e)
+// option sums_factored = -1: tile-index bits the factored sums launch must remove to be taken.  Measured
+// (profiles/r09_factored_sums.log): 4 bits of 22 at 34 qubits 1.65 -> 0.174 ms, 3 of 15 at 28 qubits 0.390 -> 0.379 ms, 2 of 7 at
+// 20 qubits 0.0342 -> 0.0375 ms (the second launch costs more than a quarter of 128 tiles saves)
+#define QSV_FACTORED_MIN_BITS 3
 template <int R, bool NT, int ZR, int FORM>
 static int launch_init_prod_k(const qsv_handle* h, const Shard& s, uint64_t ntiles, const BitIns& ins, const RegPos& rp,
                               const LanePos& lp, const ProdFactor* f, const ProdCounts& cnt, const ProdGroup& grp,
@@ -256,7 +260,7 @@ static int launch_init_prod(const qsv_handle* h, const Shard& s, int form, uint6
 template <int R, bool REGSUM>
 static int launch_prod_sums_k(const qsv_handle* h, const Shard& s, uint64_t ntiles, const BitIns& ins, const RegPos& rp,
                               const LanePos& lp, const ProdFactor* f, const ProdCounts& cnt, const ProdGroup& grp,
-                              const cplx* tab, int ntab, uint64_t nonmask, double initval, double* tsums) {
+                              const ProdWalk& walk, const cplx* tab, int ntab, uint64_t nonmask, double initval, double* tsums) {
   const size_t lds = (size_t)((ntab + 1) & ~1) * sizeof(double) + (size_t)cnt.nfac * (16 + 64 * sizeof(uint16_t)) +
                      (grp.nb ? ((size_t)cnt.nfac << grp.nb) * sizeof(uint16_t) : 0);
   static thread_local std::unordered_map<size_t, int> occupancy;
@@ -271,19 +275,29 @@ static int launch_prod_sums_k(const qsv_handle* h, const Shard& s, uint64_t ntil
   if (per_cu < 1) return fail(QSV_E_UNSUPPORTED, "k_prod_sums does not fit a CU (%zu B of LDS)", lds);
   uint64_t grid = (uint64_t)per_cu * (uint64_t)s.n_cu;
   if (h->opt_init_prod_grid > 0) grid = std::min<uint64_t>(grid, (uint64_t)h->opt_init_prod_grid);
-  grid = std::min(grid, ntiles >> grp.nb);        // one workgroup per group at most
+  grid = std::max<uint64_t>(1, std::min(grid, walk.nsum >> grp.nb));   // one workgroup per group at most
   hipLaunchKernelGGL((k_prod_sums<R, REGSUM>), dim3((unsigned)grid), dim3(QSV_TPB), std::max<size_t>(lds, 16), s.stream,
-                     ntiles, ins, rp, lp, f, cnt, grp, tab, ntab, nonmask, initval, tsums);
+                     ntiles, ins, rp, lp, f, cnt, grp, walk, tab, ntab, nonmask, initval, tsums);
   return QSV_OK;
 }
 template <int R>
 static int launch_prod_sums(const qsv_handle* h, const Shard& s, uint64_t ntiles, const BitIns& ins, const RegPos& rp, const LanePos& lp,
-                            const ProdFactor* f, const ProdCounts& cnt, const ProdGroup& grp, const cplx* tab, int ntab,
-                            uint64_t nonmask, double initval, double* tsums) {
+                            const ProdFactor* f, const ProdCounts& cnt, const ProdGroup& grp, const ProdWalk& walk,
+                            const cplx* tab, int ntab, uint64_t nonmask, double initval, double* tsums) {
   // only single-register factors on the register bits: the register sum is a product of R two-term sums
   if (cnt.nmulti == 0 && cnt.nmixed == 0)
-    return launch_prod_sums_k<R, false>(h, s, ntiles, ins, rp, lp, f, cnt, grp, tab, ntab, nonmask, initval, tsums);
-  return launch_prod_sums_k<R, true>(h, s, ntiles, ins, rp, lp, f, cnt, grp, tab, ntab, nonmask, initval, tsums);
+    return launch_prod_sums_k<R, false>(h, s, ntiles, ins, rp, lp, f, cnt, grp, walk, tab, ntab, nonmask, initval, tsums);
+  return launch_prod_sums_k<R, true>(h, s, ntiles, ins, rp, lp, f, cnt, grp, walk, tab, ntab, nonmask, initval, tsums);
+}
+// every tile's sum from the inner sums of a factored launch: one thread per tile, each workgroup a few runs of 256 tiles
+static int launch_tile_sums_expand(const qsv_handle* h, const Shard& s, uint64_t ntiles, uint64_t dmask, uint64_t tnon,
+                                   const ExpandFactor* f, int nuni, int nw, const cplx* tab, const double* inner, double* tsums) {
+  const size_t lds = (size_t)nw * sizeof(double) + (size_t)nuni * sizeof(ExpandFactor);
+  uint64_t grid = std::min<uint64_t>((ntiles + QSV_TPB - 1) / QSV_TPB, (uint64_t)s.n_cu * 8);
+  if (h->opt_init_prod_grid > 0) grid = std::min<uint64_t>(grid, (uint64_t)h->opt_init_prod_grid);
+  hipLaunchKernelGGL(k_tile_sums_expand, dim3((unsigned)std::max<uint64_t>(grid, 1)), dim3(QSV_TPB), std::max<size_t>(lds, 16), s.stream,
+                     ntiles, dmask, tnon, f, nuni, nw, tab, inner, tsums);
+  return QSV_OK;
 }
 
 // the generator from a shard's recipe: the writing form (realize) or the listed form (qsv_sample)
@@ -371,77 +385,97 @@ static int flush_init_product_r(qsv_handle* h, Shard& s, PendingGroup& g, bool f
   // and with it the product order of every amplitude -- is too.  First the bits the fewest factors touch, then bits
   // that share no factor with a register bit (such a factor costs a multiply per amplitude), then the lowest.  The
   // choice depends on the tile geometry and the factor list only.
-  ProdGroup grp;
-  memset(&grp, 0, sizeof grp);
-  int gbit_of[64];                                  // address bit -> group bit index, or -1
-  for (int q = 0; q < 64; ++q) gbit_of[q] = -1;
-  {
-    int ntb = 0;
-    while ((1ull << ntb) < ntiles) ++ntb;
-    const int want = std::min(h->opt_init_prod_group < 0 ? 3 : h->opt_init_prod_group, std::min(ntb, QSV_PROD_MAXG));
-    int nfq[64] = {0};
-    bool regq[64] = {false};
-    for (const LocalOp& lo : g.ops) {
-      bool reg = false;
-      for (int q : lo.list) reg |= q >= b0 && q < b0 + R;
-      for (int q : lo.list) { ++nfq[q]; regq[q] |= reg; }
-    }
-    std::vector<int> cand;                          // block bits: wave-index bits 2.. (the tile index)
-    for (int q = 0; q < h->L; ++q)
-      if (wbit_of[q] >= 2 && !((g.nonmask >> q) & 1ull)) cand.push_back(q);
-    std::sort(cand.begin(), cand.end(), [&](int a, int b) {
-      return std::make_tuple(nfq[a], regq[a], a) < std::make_tuple(nfq[b], regq[b], b);
-    });
-    if ((int)cand.size() > want) cand.resize(std::max(want, 0));
-    std::sort(cand.begin(), cand.end());            // the tile map keeps the order of the bits
-    grp.nb = (int)cand.size();
-    for (int i = 0; i < grp.nb; ++i) { grp.tpos[i] = wbit_of[cand[i]] - 2; gbit_of[cand[i]] = i; }
-  }
-  // factor classes: outer, group, register (single / multi), mixed (k_init_prod)
-  std::vector<ProdFactor> outer, grpf, multi, mixed, single[R];
+  // classify(): the group bits and the factor classes -- outer, group, register (single / multi), mixed (k_init_prod) --
+  // of the factors `which` (indices into g.ops, list order kept), group bits taken among the address bits `cand_bits`.
+  // Every op's table keeps its place in the one table array, whichever factors a launch lists.
+  int ntb = 0;
+  while ((1ull << ntb) < ntiles) ++ntb;
   std::vector<double> tables;
-  int nlmax = 0;
-  for (const LocalOp& lo : g.ops) {
-    ProdFactor pf;
-    memset(&pf, 0, sizeof pf);
-    pf.nlist = (int)lo.list.size();
-    pf.tab = (int)(tables.size() / 2);
-    nlmax = std::max(nlmax, pf.nlist);
-    int nreg = 0, creg = 0, ngb = 0;
-    for (int e = 0; e < QSV_MULTI_MAXLIST; ++e) pf.wbit[e >> 2] |= (uint32_t)QSV_PROD_NOBIT << (8 * (e & 3));
-    for (int e = 0; e < pf.nlist; ++e) {
-      const int q = lo.list[e];
-      pf.pos[e] = -1;
-      if (q >= b0 && q < b0 + R) { pf.regw[q - b0] = 1 << e; ++nreg; creg = q - b0; }
-      else if (q < 32 && ((lanemask >> q) & 1u)) pf.pos[e] = q;
-      else {
-        if (wbit_of[q] < 0) return fail(QSV_E_UNSUPPORTED, "init product: address bit %d has no class", q);
-        // a group bit is 0 in the wave index of a group's first tile, which is where the kernel gathers
-        pf.wbit[e >> 2] = (pf.wbit[e >> 2] & ~(0xffu << (8 * (e & 3)))) | ((uint32_t)wbit_of[q] << (8 * (e & 3)));
-        if (gbit_of[q] >= 0) { pf.grpw[gbit_of[q]] = 1 << e; ++ngb; }
-      }
-    }
-    tables.insert(tables.end(), lo.table.begin(), lo.table.end());
-    if (nreg == 0) (ngb ? grpf : outer).push_back(pf);
-    else if (ngb) mixed.push_back(pf);
-    else (nreg == 1 ? single[creg] : multi).push_back(pf);
+  std::vector<int> tab_of(g.ops.size());
+  for (size_t i = 0; i < g.ops.size(); ++i) {
+    tab_of[i] = (int)(tables.size() / 2);
+    tables.insert(tables.end(), g.ops[i].table.begin(), g.ops[i].table.end());
   }
   if (tables.size() / 2 > 2560) return fail(QSV_E_UNSUPPORTED, "init product tables exceed LDS");
   if (g.ops.size() > QSV_PROD_MAXF) return fail(QSV_E_UNSUPPORTED, "init product of %zu factors (limit %d)", g.ops.size(), QSV_PROD_MAXF);
-  ProdCounts cnt;
-  memset(&cnt, 0, sizeof cnt);
-  std::vector<ProdFactor> uni;                      // the factor list in kernel order
-  cnt.nouter = (int)outer.size();
-  uni.insert(uni.end(), outer.begin(), outer.end());
-  cnt.ngrp = (int)grpf.size();
-  uni.insert(uni.end(), grpf.begin(), grpf.end());
-  for (int c = 0; c < R; ++c) { cnt.nsingle[c] = (int)single[c].size(); uni.insert(uni.end(), single[c].begin(), single[c].end()); }
-  cnt.nmulti = (int)multi.size();
-  uni.insert(uni.end(), multi.begin(), multi.end());
-  cnt.nmixed = (int)mixed.size();
-  uni.insert(uni.end(), mixed.begin(), mixed.end());
-  cnt.nfac = (int)uni.size();
-  cnt.nlmax = nlmax;
+  struct Classified { ProdGroup grp; ProdCounts cnt; std::vector<ProdFactor> uni; };   // uni: the factor list in kernel order
+  auto classify = [&](const std::vector<int>& which, uint64_t cand_bits, Classified& out) -> int {
+    ProdGroup& grp = out.grp;
+    memset(&grp, 0, sizeof grp);
+    int gbit_of[64];                                  // address bit -> group bit index, or -1
+    for (int q = 0; q < 64; ++q) gbit_of[q] = -1;
+    {
+      const int want = std::min(h->opt_init_prod_group < 0 ? 3 : h->opt_init_prod_group, std::min(ntb, QSV_PROD_MAXG));
+      int nfq[64] = {0};
+      bool regq[64] = {false};
+      for (int i : which) {
+        const LocalOp& lo = g.ops[i];
+        bool reg = false;
+        for (int q : lo.list) reg |= q >= b0 && q < b0 + R;
+        for (int q : lo.list) { ++nfq[q]; regq[q] |= reg; }
+      }
+      std::vector<int> cand;                          // block bits: wave-index bits 2.. (the tile index)
+      for (int q = 0; q < h->L; ++q)
+        if (wbit_of[q] >= 2 && !((g.nonmask >> q) & 1ull) && ((cand_bits >> q) & 1ull)) cand.push_back(q);
+      std::sort(cand.begin(), cand.end(), [&](int a, int b) {
+        return std::make_tuple(nfq[a], regq[a], a) < std::make_tuple(nfq[b], regq[b], b);
+      });
+      if ((int)cand.size() > want) cand.resize(std::max(want, 0));
+      std::sort(cand.begin(), cand.end());            // the tile map keeps the order of the bits
+      grp.nb = (int)cand.size();
+      for (int i = 0; i < grp.nb; ++i) { grp.tpos[i] = wbit_of[cand[i]] - 2; gbit_of[cand[i]] = i; }
+    }
+    std::vector<ProdFactor> outer, grpf, multi, mixed, single[R];
+    int nlmax = 0;
+    for (int i : which) {
+      const LocalOp& lo = g.ops[i];
+      ProdFactor pf;
+      memset(&pf, 0, sizeof pf);
+      pf.nlist = (int)lo.list.size();
+      pf.tab = tab_of[i];
+      nlmax = std::max(nlmax, pf.nlist);
+      int nreg = 0, creg = 0, ngb = 0;
+      for (int e = 0; e < QSV_MULTI_MAXLIST; ++e) pf.wbit[e >> 2] |= (uint32_t)QSV_PROD_NOBIT << (8 * (e & 3));
+      for (int e = 0; e < pf.nlist; ++e) {
+        const int q = lo.list[e];
+        pf.pos[e] = -1;
+        if (q >= b0 && q < b0 + R) { pf.regw[q - b0] = 1 << e; ++nreg; creg = q - b0; }
+        else if (q < 32 && ((lanemask >> q) & 1u)) pf.pos[e] = q;
+        else {
+          if (wbit_of[q] < 0) return fail(QSV_E_UNSUPPORTED, "init product: address bit %d has no class", q);
+          // a group bit is 0 in the wave index of a group's first tile, which is where the kernel gathers
+          pf.wbit[e >> 2] = (pf.wbit[e >> 2] & ~(0xffu << (8 * (e & 3)))) | ((uint32_t)wbit_of[q] << (8 * (e & 3)));
+          if (gbit_of[q] >= 0) { pf.grpw[gbit_of[q]] = 1 << e; ++ngb; }
+        }
+      }
+      if (nreg == 0) (ngb ? grpf : outer).push_back(pf);
+      else if (ngb) mixed.push_back(pf);
+      else (nreg == 1 ? single[creg] : multi).push_back(pf);
+    }
+    ProdCounts& cnt = out.cnt;
+    memset(&cnt, 0, sizeof cnt);
+    std::vector<ProdFactor>& uni = out.uni;
+    uni.clear();
+    cnt.nouter = (int)outer.size();
+    uni.insert(uni.end(), outer.begin(), outer.end());
+    cnt.ngrp = (int)grpf.size();
+    uni.insert(uni.end(), grpf.begin(), grpf.end());
+    for (int c = 0; c < R; ++c) { cnt.nsingle[c] = (int)single[c].size(); uni.insert(uni.end(), single[c].begin(), single[c].end()); }
+    cnt.nmulti = (int)multi.size();
+    uni.insert(uni.end(), multi.begin(), multi.end());
+    cnt.nmixed = (int)mixed.size();
+    uni.insert(uni.end(), mixed.begin(), mixed.end());
+    cnt.nfac = (int)uni.size();
+    cnt.nlmax = nlmax;
+    return QSV_OK;
+  };
+  std::vector<int> every(g.ops.size());
+  for (size_t i = 0; i < every.size(); ++i) every[i] = (int)i;
+  Classified all;                                   // what the writing and listed generator run with, and the unfactored sums
+  CHK(classify(every, ~0ull, all));
+  const ProdGroup& grp = all.grp;
+  const ProdCounts& cnt = all.cnt;
+  const std::vector<ProdFactor>& uni = all.uni;
   const int ntab = (int)(tables.size() / 2);
   const uint64_t nthreads = n >> R;
   double* tsums = nullptr;
@@ -459,6 +493,64 @@ static int flush_init_product_r(qsv_handle* h, Shard& s, PendingGroup& g, bool f
     s.tile_ins = ins;
     s.tile_nblocks = nb;
     s.tile_xor = 0;
+  }
+  // Factored sums (option sums_factored, DESIGN §5e), the sums launch only.  A factor whose every bit is a block bit is
+  // tile-uniform: one weight for all 256 threads of a tile, so it leaves the tile's sum.  The other factors (inner)
+  // read the tile index only through D, the block bits they touch: k_prod_sums runs over the 2^|D| tiles with every
+  // other tile-index bit held at 0, with group bits and classes of its own taken over the inner factors and D, and
+  // k_tile_sums_expand forms every tile's sum from those.  A nonmask bit is never in D: it is 0 wherever the sum is
+  // not.  Taken when it removes at least QSV_FACTORED_MIN_BITS tile-index bits (sums_factored = 1: one); a function
+  // of the tile geometry and the factor list only.
+  Classified in;
+  std::vector<ExpandFactor> tuf;
+  ProdWalk walk;
+  memset(&walk, 0, sizeof walk);
+  walk.nsum = ntiles;
+  for (int i = 0; i < grp.nb; ++i) walk.cpos[i] = grp.tpos[i];
+  uint64_t dmask = 0, tnon = 0;
+  int nwexp = 0;
+  bool factored = false;
+  if (tsums) {
+    std::vector<int> inner;
+    for (size_t i = 0; i < g.ops.size(); ++i) {
+      bool uniform = true;
+      for (int q : g.ops[i].list) uniform &= wbit_of[q] >= 2;
+      if (!uniform) { inner.push_back((int)i); continue; }
+      ExpandFactor ef;
+      memset(&ef, 0, sizeof ef);
+      ef.nlist = (int)g.ops[i].list.size();
+      ef.tab = tab_of[i];
+      ef.lds = nwexp;
+      for (int e = 0; e < ef.nlist; ++e) ef.tbit[e] = (unsigned char)(wbit_of[g.ops[i].list[e]] - 2);
+      nwexp += 1 << ef.nlist;
+      tuf.push_back(ef);
+    }
+    uint64_t dbits = 0;                             // D as address bits
+    for (int i : inner)
+      for (int q : g.ops[i].list)
+        if (wbit_of[q] >= 2 && !((g.nonmask >> q) & 1ull)) { dmask |= 1ull << (wbit_of[q] - 2); dbits |= 1ull << q; }
+    for (int q = 0; q < h->L; ++q)
+      if (wbit_of[q] >= 2 && ((g.nonmask >> q) & 1ull)) tnon |= 1ull << (wbit_of[q] - 2);
+    const int nd = __builtin_popcountll(dmask);
+    const int need = h->opt_sums_factored > 0 ? 1 : QSV_FACTORED_MIN_BITS;
+    factored = h->opt_sums_factored != 0 && ntb - nd >= need;
+    s.sums_info[0] = factored ? 1 : 0;
+    s.sums_info[1] = nd;
+    s.sums_info[2] = (int)inner.size();
+    s.sums_info[3] = (int)tuf.size();
+    if (factored) {
+      CHK(classify(inner, dbits, in));
+      walk.nsum = 1ull << nd;
+      walk.tfix = (ntiles - 1ull) & ~dmask;
+      for (int i = 0; i < in.grp.nb; ++i) walk.cpos[i] = __builtin_popcountll(dmask & ((1ull << in.grp.tpos[i]) - 1ull));
+      if (s.inner_cap < walk.nsum) {
+        if (s.d_inner) { HIPCHK(hipStreamSynchronize(s.stream)); HIPCHK(hipFree(s.d_inner)); }
+        s.d_inner = nullptr;
+        s.inner_cap = 0;
+        HIPCHK(hipMalloc(&s.d_inner, walk.nsum * sizeof(double)));
+        s.inner_cap = walk.nsum;
+      }
+    }
   }
   // implied zeros: as the program's last pass the generator stores only the amplitudes outside the provably-zero
   // region (planner.choose_layout puts such a qubit on the top bit: half the shard); otherwise every amplitude is
@@ -497,6 +589,12 @@ static int flush_init_product_r(qsv_handle* h, Shard& s, PendingGroup& g, bool f
     CHK(arena_put(s, uni.data(), uni.size() * sizeof(ProdFactor), &dfac));
     CHK(arena_put(s, tables.data(), tbytes, &dtab));
   }
+  void* dfin = nullptr;                             // a factored sums launch: the inner factors in their own order, the tile-uniform ones
+  void* dtuf = nullptr;
+  if (factored) {
+    if (!in.uni.empty()) CHK(arena_put(s, in.uni.data(), in.uni.size() * sizeof(ProdFactor), &dfin));
+    if (!tuf.empty()) CHK(arena_put(s, tuf.data(), tuf.size() * sizeof(ExpandFactor), &dtuf));
+  }
   h->stats.fused_gates += g.ops.size();
   const double initval = g.initval;
   int lr = QSV_OK;
@@ -504,11 +602,18 @@ static int flush_init_product_r(qsv_handle* h, Shard& s, PendingGroup& g, bool f
     const ProdFactor* df = reinterpret_cast<const ProdFactor*>(dfac);
     const cplx* dt = reinterpret_cast<const cplx*>(dtab);
     if (!defer) lr = launch_init_prod<R>(h, s, QSV_GEN_WRITE, ntiles, ins, rp, lp, df, cnt, grp, dt, ntab, nonmask, initval, zskip, zreg);
-    if (lr == QSV_OK && tsums) lr = launch_prod_sums<R>(h, s, ntiles, ins, rp, lp, df, cnt, grp, dt, ntab, nonmask, initval, tsums);
+    if (lr != QSV_OK || !tsums) return;
+    if (!factored) { lr = launch_prod_sums<R>(h, s, ntiles, ins, rp, lp, df, cnt, grp, walk, dt, ntab, nonmask, initval, tsums); return; }
+    lr = launch_prod_sums<R>(h, s, ntiles, ins, rp, lp, reinterpret_cast<const ProdFactor*>(dfin), in.cnt, in.grp, walk, dt, ntab,
+                             nonmask, initval, s.d_inner);
+    if (lr == QSV_OK)
+      lr = launch_tile_sums_expand(h, s, ntiles, dmask, tnon, reinterpret_cast<const ExpandFactor*>(dtuf), (int)tuf.size(), nwexp,
+                                   dt, s.d_inner, tsums);
   });
   CHK(lr);
   s.deferred = defer && r == QSV_OK;
   s.tile_fresh = tsums != nullptr;
+  s.sums_from_gen = tsums != nullptr;
   g = PendingGroup();
   return r;
 }
@@ -912,6 +1017,7 @@ static int flush_group(qsv_handle* h, Shard& s, PendingGroup& g, bool final_pass
     }
   });
   s.tile_fresh = tsums != nullptr;
+  if (tsums) s.sums_from_gen = false;
   g = PendingGroup();
   g.xframe = xleft;
   return r;
