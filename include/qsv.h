@@ -388,7 +388,7 @@ int qsv_get_stats(qsv_handle* h, qsv_stats* out);
  * Deferred state ends with realisation or with the next init that writes; a program refused before its init writes
  * leaves the deferred state, recipe included, as it was.
  * deferred: 1 if a shard of this process is deferred; realize_calls / listed_launches: generator launches so far that
- * realised a shard / that stored a sampler's tile list.  Any out pointer may be NULL. */
+ * realised a shard / that stored a sampler's tile list or (sample_chain 1) located its shots in it.  Any out pointer may be NULL. */
 int qsv_state_info(qsv_handle* h, int* deferred, uint64_t* realize_calls, uint64_t* listed_launches);
 
 /* The per-tile sums of |amp|^2 the last pass of the last program left on local shard `shard` (fused_sums), in
@@ -434,6 +434,8 @@ int qsv_timer_end(qsv_handle* h, double* ms);
  *                                  tile-index bits, 1 at least one, 0 never (the sums differ by rounding only, within the same bound)
  *   memory      nontemporal [-1], multi_nt [-1], init_prod_nt [-1]   non-temporal loads/stores: -1 by shard size, 0 never, 1 always
  *   measurement cache_sums [1], fused_sums [1]   keep / produce per-tile |amp|^2 sums in the last pass of a program
+ *               sample_chain [1]   qsv_sample on one shard's tile sums: 1 the walk over the super sums on the device, a deferred shard's
+ *                                  shots located inside the generator (nothing stored), one host wait; 0 the host walk.  Same words.
  *   kernels     unroll [4], lowt_shuffle [1], pair_variant [0], kq_mfma [1], blocks_per_cu [65536]
  *               swizzle [1]        one-gate kernels: lane bit 5 of a wave access carries address bit 11 (two 512-byte runs 32 KiB apart);
  *                                  1 from 2^26 amplitudes per shard, 2 from 2^14, 0 never        lane_map_min_l [26]  same for k_multi tiles other than bits 6..10

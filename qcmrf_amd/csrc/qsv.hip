@@ -180,6 +180,8 @@ struct Shard {
   double* h_tsums = nullptr;     // ... and their pinned host copy, valid until the state changes
   size_t h_tsums_cap = 0;
   bool h_tsums_valid = false;
+  int d_super_valid = 0;        // bit 0: d_super holds this state's super sums; bit 1: d_walk their prefix, total and last populated entry (k_walk_super)
+  double* d_walk = nullptr;      // sample_chain: P[1..nsuper] | total | last populated super block (as a double); as long as d_super
   bool tile_valid = false, tile_fresh = false;
   int tile_R = 0;
   RegPos tile_rp;
@@ -258,7 +260,8 @@ struct qsv_handle {
   int opt_init_prod_grid = 0;         // workgroups of the persistent generator: 0 = as many as the chip holds, else at most this many
   int opt_defer_state = -1;           // the generator as a program's last pass leaves tile sums only, the state deferred: -1 from QSV_DEFER_MIN_L local qubits, 0 never, 1 always
   int opt_sums_factored = -1;         // the generator's sums launch over the tiles that differ in an inner factor only, expanded by the tile-uniform factors: -1 where that removes at least QSV_FACTORED_MIN_BITS (3) tile-index bits, 0 never, 1 where it removes at least one
-  int opt_init_prod_group = -1;       // group bits of the generator (2^B tiles per workgroup step): -1 auto (up to 3), 0 off, 1..4 that many
+  int opt_sample_chain = 1;           // qsv_sample on one shard's tile sums: 1 the super-sum walk on the device (k_walk_super), a deferred shard's shots located inside the generator (QSV_GEN_LOCATE), one host wait; 0 the host walk, listed tiles stored and read back
+  int opt_init_prod_group = -1;      // group bits of the generator (2^B tiles per workgroup step): -1 auto (up to 3), 0 off, 1..4 that many
   int opt_xframe = 1;                 // uncontrolled X gates inside a pass become an XOR on its store addresses
   int opt_trace_passes = 0;           // 1: one stderr line per k_multi pass (R, mode, ops by update shape) -- a diagnostic
   int opt_pass_budget = 0;            // opt-in cap on the arithmetic of a general pass, percent of one read+write of the shard (0: none)
@@ -315,6 +318,19 @@ static int arena_stage(Shard& s, const void* src, size_t bytes, void** hptr) {
   return QSV_OK;
 }
 
+// ... and an empty slot of the pinned half, for the host to fill in place or a kernel to write a result into
+static int arena_slot(Shard& s, size_t bytes, void** hptr) {
+  const size_t slot = (bytes + 255) & ~size_t(255);
+  if (slot > s.arena_bytes) return fail(QSV_E_BADARG, "table of %zu bytes exceeds arena", bytes);
+  if (s.arena_top + slot > s.arena_bytes) {
+    HIPCHK(hipStreamSynchronize(s.stream));
+    s.arena_top = 0;
+  }
+  *hptr = s.h_arena + s.arena_top;
+  s.arena_top += slot;
+  return QSV_OK;
+}
+
 static int get_event(Shard& s, hipEvent_t* e) {
   if (!s.free_events.empty()) { *e = s.free_events.back(); s.free_events.pop_back(); return QSV_OK; }
   HIPCHK(hipEventCreate(e));
@@ -349,7 +365,7 @@ static int launch(qsv_handle* h, Shard& s, int kind, double bytes, F&& f) {
   }
   f();
   HIPCHK(hipGetLastError());
-  if (kind != QSV_K_PROB) { s.sums_valid = false; s.tile_valid = false; s.h_tsums_valid = false; s.deferred = false; }   // any state change drops cached sums (and whoever changes a deferred state has realised it, or overwrites it)
+  if (kind != QSV_K_PROB) { s.sums_valid = false; s.tile_valid = false; s.h_tsums_valid = false; s.d_super_valid = 0; s.deferred = false; }   // any state change drops cached sums (and whoever changes a deferred state has realised it, or overwrites it)
   if (h->profiling) {
     HIPCHK(hipEventRecord(p.e1, s.stream));
     s.pending.push_back(p);
@@ -467,6 +483,7 @@ extern "C" int qsv_destroy(qsv_handle* h) {
     if (s.ev_ready) hipEventDestroy(s.ev_ready);
     if (s.h_tsums) hipHostFree(s.h_tsums);
     if (s.d_super) hipFree(s.d_super);
+    if (s.d_walk) hipFree(s.d_walk);
     if (s.stream) hipStreamDestroy(s.stream);
   }
   if (h->t0) hipEventDestroy(h->t0);
@@ -759,6 +776,7 @@ static int materialize(qsv_handle* h, Shard& s) {
   s.zmask = 0;
   CHK(shard_set(s));
   const bool sv = s.sums_valid, tv = s.tile_valid, hv = s.h_tsums_valid;
+  const int dv = s.d_super_valid;
   const int nz = __builtin_popcountll(zm);
   CHK(launch(h, s, QSV_K_INIT, 16.0 * ((double)n - (double)(n >> nz)), [&] {
     hipLaunchKernelGGL(k_fill_zero, dim3(grid_for(h, s, n, QSV_TPB * 4)), dim3(QSV_TPB), 0, s.stream, s.amp, n, zm);
@@ -766,6 +784,7 @@ static int materialize(qsv_handle* h, Shard& s) {
   s.sums_valid = sv;
   s.tile_valid = tv;
   s.h_tsums_valid = hv;
+  s.d_super_valid = dv;
   return QSV_OK;
 }
 static int materialize_all(qsv_handle* h) {

@@ -523,6 +523,91 @@ __global__ __launch_bounds__(64) void k_locate_super(const double* __restrict__ 
   }
 }
 
+// The host's walk over the super sums, on the device (option sample_chain).  k_walk_super, ONE workgroup of one
+// wave, turns the n super sums (n a power of two, <= QSV_WALK_MAX) into what the walk needs, with the host's arithmetic:
+//   walk[b] = P[b + 1], P[0] = 0, P[b + 1] = P[b] + super[b]: one thread, one addition after the other, the order of the
+//             host loop `pre += bs[b]`
+//   walk[n] = total, by the association of pairwise_sum (qsv_measure.inc): runs of 64 entries summed left to right from
+//             0, then adjacent halves added, level by level
+//   walk[n + 1] = the last entry > 0 (0 if there is none), as a double
+// It depends on the state alone, so it is launched before the host has drawn the shots' spacings and runs under that.
+// k_walk_shots, one thread per shot, then does per shot what the host did: scale = total / run, r = min(raw * scale,
+// nextafter(total, 0)), the first b with r < P[b + 1] clamped to the last populated entry (P is non-decreasing: the
+// binary search finds what the linear walk finds), blk = b, resid = max(0, r - P[b]).  Every index stays inside
+// [0, last] whatever total is (0, infinite, NaN: the host reads total afterwards and refuses such a state).  Nothing here
+// may be contracted or reassociated: no product feeds a sum.
+#define QSV_WALK_MAX 4096
+__global__ __launch_bounds__(64) void k_walk_super(const double* __restrict__ super, int n, double* __restrict__ walk) {
+  // One wave, everything in registers: the chain of n dependent additions is the kernel's time, and a version that kept
+  // the entries in LDS waited for LDS at every step (80 us for 4096 entries).  Lane l holds entries [64 l, 64 l + 64).
+  const int lane = threadIdx.x;
+  if (n <= 64) {                                       // one leaf: the total is the prefix's last value
+    if (lane == 0) {
+      double pre = 0.0;
+      int last = 0;
+      for (int b = 0; b < n; ++b) {
+        const double v = super[b];
+        if (v > 0.0) last = b;
+        pre += v;
+        walk[b] = pre;
+      }
+      walk[n] = pre;
+      walk[n + 1] = (double)last;
+    }
+    return;
+  }
+  const int nc = n / 64;                               // pairwise_sum's leaves, one per lane; a power of two <= 64
+  const bool live = lane < nc;
+  double v[64];
+#pragma unroll
+  for (int k = 0; k < 64; ++k) v[k] = live ? super[lane * 64 + k] : 0.0;
+  double cs = 0;                                       // the leaf: left to right from 0
+  int last = 0;
+#pragma unroll
+  for (int k = 0; k < 64; ++k) { cs += v[k]; if (v[k] > 0.0) last = lane * 64 + k; }
+  for (int st = 1; st < nc; st <<= 1) cs = cs + __shfl_down(cs, st, 64);   // lane t, t a multiple of 2 st: leaves t .. t + 2 st - 1
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) last = max(last, __shfl_xor(last, o, 64));
+  if (lane == 0) { walk[n] = cs; walk[n + 1] = (double)last; }
+  // the prefix: lane after lane, each continuing from its predecessor's last value
+  double carry = 0.0;
+  for (int l = 0; l < nc; ++l) {
+    double acc = carry;
+    if (lane == l) {
+#pragma unroll
+      for (int k = 0; k < 64; ++k) { acc += v[k]; v[k] = acc; }
+    }
+    carry = __shfl(acc, l, 64);
+  }
+  if (live) {
+#pragma unroll
+    for (int k = 0; k < 64; ++k) walk[lane * 64 + k] = v[k];
+  }
+}
+__global__ __launch_bounds__(QSV_TPB) void k_walk_shots(const double* __restrict__ walk, int n, const double* __restrict__ raw,
+                                                        double run, uint64_t shots, uint64_t* __restrict__ blk,
+                                                        double* __restrict__ resid, double* __restrict__ total_out) {
+  const double total = walk[n];
+  if (blockIdx.x == 0 && threadIdx.x == 0) *total_out = total;
+  int last = (int)walk[n + 1];
+  last = last < 0 ? 0 : (last > n - 1 ? n - 1 : last);
+  const double scale = total / run;
+  // nextafter(total, 0) of a total > 0: the double below it
+  const double cap = total > 0.0 ? __longlong_as_double(__double_as_longlong(total) - 1ll) : total;
+  for (uint64_t s = (uint64_t)blockIdx.x * QSV_TPB + threadIdx.x; s < shots; s += (uint64_t)gridDim.x * QSV_TPB) {
+    const double v = raw[s] * scale;
+    const double r = cap < v ? cap : v;                // std::min(v, cap)
+    int lo = 0, hi = last;
+    while (lo < hi) {
+      const int mid = (lo + hi) >> 1;
+      if (r < walk[mid]) hi = mid; else lo = mid + 1;
+    }
+    const double d = r - (lo ? walk[lo - 1] : 0.0);
+    blk[s] = (uint64_t)lo;
+    resid[s] = 0.0 < d ? d : 0.0;                      // std::max(0.0, d)
+  }
+}
+
 // marginal over up to 26 qubits; only indices with (g & fmask) == fval contribute, where
 // g = hi | i is the global index.  Small tables are pre-reduced in LDS.
 template <bool LDS>
@@ -721,8 +806,9 @@ __device__ __forceinline__ uint32_t prod_gather_wave(uint32_t wi, const uint32_t
   return nl <= 4 ? prod_gather_wave<4>(wi, wb) : prod_gather_wave<QSV_MULTI_MAXLIST>(wi, wb);   // uniform branch
 }
 
-// the two forms of the generator: every amplitude stored | the tiles of a sorted list stored (the sampler)
-enum { QSV_GEN_WRITE = 0, QSV_GEN_LISTED = 2 };
+// the forms of the generator: every amplitude stored | the tiles of a sorted list stored (the sampler,
+// sample_chain = 0) | the tiles of a list formed in registers and each shot located in its tile, nothing stored
+enum { QSV_GEN_WRITE = 0, QSV_GEN_LISTED = 2, QSV_GEN_LOCATE = 3 };
 
 template <int R, bool NT, int ZR, int FORM>
 __global__ __launch_bounds__(QSV_TPB) void k_init_prod(cplx* __restrict__ amp, uint64_t ntiles, BitIns ins, RegPos rp,
@@ -730,7 +816,8 @@ __global__ __launch_bounds__(QSV_TPB) void k_init_prod(cplx* __restrict__ amp, u
                                                        ProdGroup grp, const cplx* __restrict__ tables, int ntab,
                                                        uint64_t nonmask, double initval,
                                                        uint64_t zskip, unsigned zreg_arg,
-                                                       const uint64_t* __restrict__ list, uint64_t nlist) {
+                                                       const uint64_t* __restrict__ list, uint64_t nlist,
+                                                       const double* __restrict__ resid, uint64_t* __restrict__ out) {
   constexpr int NWB = (QSV_MULTI_MAXLIST + 3) / 4;
   static_assert(NWB == 3, "a factor descriptor holds 12 wave-index bit bytes");
   const unsigned zreg = ZR >= 0 ? (unsigned)ZR : zreg_arg;
@@ -811,19 +898,32 @@ __global__ __launch_bounds__(QSV_TPB) void k_init_prod(cplx* __restrict__ amp, u
   // belongs to (the product order is the group order) and storing that one tile.  The list is non-decreasing: an entry
   // equal to its predecessor is skipped (that workgroup stores the tile once for all of them); two different tiles of
   // one group are two walks over that group, each storing its own tile.
+  // QSV_GEN_LOCATE: the same walk, one workgroup per entry = shot, equal entries included (a tile that several shots
+  // share is formed once per shot: the shots of a peaked state spread over the chip instead of queueing in one
+  // workgroup).  Only the listed tile of the group is formed, p[j] = |a|^2 of what the listed form would have stored
+  // stays in registers, and k_locate_tile's scan runs on it: out[gi] = the shot's address, amp is not touched.
   constexpr bool LISTED = FORM == QSV_GEN_LISTED;
+  constexpr bool LOCATE = FORM == QSV_GEN_LOCATE;
+  constexpr bool BYLIST = LISTED || LOCATE;
   uint32_t bsel = 0;
-  for (uint64_t gi = blockIdx.x; gi < (LISTED ? nlist : ngroups);
-       gi += gridDim.x, tile0 = LISTED ? tile0 : ((tile0 | tholes) + dtile) & ~tholes,
-                        base_blk = LISTED ? base_blk : ((base_blk | holes) + dblk) & ~holes) {
-    if constexpr (LISTED) {
+  for (uint64_t gi = blockIdx.x; gi < (BYLIST ? nlist : ngroups);
+       gi += gridDim.x, tile0 = BYLIST ? tile0 : ((tile0 | tholes) + dtile) & ~tholes,
+                        base_blk = BYLIST ? base_blk : ((base_blk | holes) + dblk) & ~holes) {
+    if constexpr (BYLIST) {
       const uint64_t t = list[gi];
-      if (t >= ntiles || (gi && list[gi - 1] == t)) continue;
+      if constexpr (LOCATE) {
+        if (t >= ntiles) { if (threadIdx.x == 0) out[gi] = ~0ull; continue; }
+      } else {
+        if (t >= ntiles || (gi && list[gi - 1] == t)) continue;
+      }
       tile0 = t & ~tholes;
       base_blk = tile_base_blk(tile0, ins, lp);
       bsel = 0;
 #pragma unroll
       for (int i = 0; i < QSV_PROD_MAXG; ++i) if (t & gt[i]) bsel |= 1u << i;
+    }
+    if constexpr (LOCATE) {                        // an implied-zero tile holds no shot: what k_locate_tile leaves for it
+      if (base_blk & zskip) { if (threadIdx.x == 0) out[gi] = ~0ull; continue; }
     }
     if (base_blk & zskip) continue;                // the whole group is implied zero: nothing to store
     // wave-uniform parts of the group's first tile: lane k holds factor k's (and k + 64's) table offset, in bytes
@@ -886,7 +986,8 @@ __global__ __launch_bounds__(QSV_TPB) void k_init_prod(cplx* __restrict__ amp, u
       }
     }
     const int km = k0 + cnt.nmulti;                // the mixed factors
-    for (int b = 0; b < nsub; ++b) {
+    const int bfirst = LOCATE ? (int)bsel : 0, bend = LOCATE ? (int)bsel + 1 : nsub;
+    for (int b = bfirst; b < bend; ++b) {
       // tile b: the group part of the table offsets of the group and mixed factors
       uint32_t gb0 = jb0, gb1 = jb1;
       if (grp.nb) {
@@ -917,9 +1018,84 @@ __global__ __launch_bounds__(QSV_TPB) void k_init_prod(cplx* __restrict__ amp, u
           if (LISTED ? (store && (uint32_t)b == bsel) : store) { if (NT) st_nt((pblk + off) + base_thr, a); else (pblk + off)[base_thr] = a; }
         }
       };
-      if (cnt.nmixed) stores(std::true_type{}, std::true_type{});          // mixed factors exist with group bits only
-      else if (grp.nb) stores(std::true_type{}, std::false_type{});
-      else stores(std::false_type{}, std::false_type{});
+      if constexpr (!LOCATE) {
+        if (cnt.nmixed) stores(std::true_type{}, std::true_type{});          // mixed factors exist with group bits only
+        else if (grp.nb) stores(std::true_type{}, std::false_type{});
+        else stores(std::false_type{}, std::false_type{});
+      } else {
+        // QSV_GEN_LOCATE: the same products, and use(j, p) instead of a store: p = |a|^2 of what would have been stored,
+        // 0 where this thread stores nothing
+        auto values = [&](auto grouped, auto mixed, auto&& use) {
+#pragma unroll
+          for (int j = 0; j < (1 << R); ++j) {
+            if ((unsigned)j & zreg) continue;
+            cplx a = decltype(grouped)::value ? cmul(s, A[j]) : A[j];
+            if (decltype(mixed)::value)
+              for (int k = km; k < km + cnt.nmixed; ++k) {
+                const ProdFactor& pf = fac[k];
+                int jr = 0;
+#pragma unroll
+                for (int c = 0; c < R; ++c) if ((j >> c) & 1) jr += pf.regw[c];
+                a = cmul(a, ldt(entry(gb0, gb1, k) + (uint32_t)jr * sizeof(cplx)));
+              }
+            use(j, store ? fma(a.x, a.x, a.y * a.y) : 0.0);
+          }
+        };
+        auto tile = [&](auto&& use) {
+          if (cnt.nmixed) values(std::true_type{}, std::true_type{}, use);
+          else if (grp.nb) values(std::true_type{}, std::false_type{}, use);
+          else values(std::false_type{}, std::false_type{}, use);
+        };
+        // k_locate_tile<R>'s scan (below) on the tile's |a|^2: thread t owns the 2^R values at base | off(j); the first
+        // (t, j) whose running sum exceeds resid[gi].  The values are not kept: the tile's products (one or a few per
+        // value, A[] stays) are formed once for the thread's sum and once more for the walk through its values, by the
+        // same code, so both see the same numbers -- 2^R doubles per thread less, which at R = 6 do not fit.
+        __shared__ double wtot[QSV_TPB / 64];
+        __shared__ unsigned long long found;
+        __shared__ unsigned long long lastnz;
+        const uint64_t base = base_blk | sub(ga, bsel) | base_thr;
+        const double r = resid[gi];
+        double mine = 0.0;
+        tile([&](int, double pj) { mine += pj; });
+        double inc = mine;                                  // inclusive scan over the 256 threads
+#pragma unroll
+        for (int o = 1; o < 64; o <<= 1) {
+          const double v = __shfl_up(inc, o, 64);
+          if (lane >= o) inc += v;
+        }
+        if (threadIdx.x == 0) { found = ~0ull; lastnz = ~0ull; }
+        if (lane == 63) wtot[wave] = inc;
+        __syncthreads();
+        double before = 0.0;
+        for (uint32_t w = 0; w < wave; ++w) before += wtot[w];
+        const double hi = before + inc, lo = hi - mine;
+        // every thread walks its values (the products need the whole wave); the owner of the crossing reports its hit,
+        // the last populated thread records a fallback
+        double run = lo;
+        int jhit = -1, jlast = 0;
+        tile([&](int j, double pj) {
+          if (pj > 0.0) { jlast = j; run += pj; if (jhit < 0 && run > r) jhit = j; }
+        });
+        if (mine > 0.0) atomicMax(&lastnz, (unsigned long long)threadIdx.x);
+        if (mine > 0.0 && lo <= r && r < hi) {
+          if (jhit < 0) jhit = jlast;
+          uint64_t off = 0;
+#pragma unroll
+          for (int c = 0; c < R; ++c) if ((jhit >> c) & 1) off |= ob[c];
+          atomicMin(&found, (unsigned long long)(base | off));
+        }
+        __syncthreads();
+        if (found == ~0ull && lastnz != ~0ull && threadIdx.x == (unsigned)lastnz) {
+          // rounding slack ran past the tile: take the last populated amplitude of the last populated thread
+          uint64_t off = 0;
+#pragma unroll
+          for (int c = 0; c < R; ++c) if ((jlast >> c) & 1) off |= ob[c];
+          found = base | off;
+        }
+        __syncthreads();
+        if (threadIdx.x == 0) out[gi] = found;
+        __syncthreads();
+      }
     }
   }
 }

@@ -347,7 +347,7 @@ static int rccl_block_exchange(qsv_handle* h, Shard& s, const BitIns& ins, uint6
 static int exchange_multi(qsv_handle* h, const std::vector<int>& G, const std::vector<int>& J) {
   // every cached reduction describes the state BEFORE the swap: block sums, the per-tile sums a
   // program's last pass left and their host copy
-  for (Shard& s : h->shards) { s.sums_valid = false; s.tile_valid = false; s.h_tsums_valid = false; }
+  for (Shard& s : h->shards) { s.sums_valid = false; s.tile_valid = false; s.h_tsums_valid = false; s.d_super_valid = 0; }
   const int k = (int)G.size();
   std::vector<int> gb(k);
   for (int i = 0; i < k; ++i) gb[i] = G[i] - h->L;
@@ -431,7 +431,7 @@ static int exchange_multi(qsv_handle* h, const std::vector<int>& G, const std::v
 // swap shard bit G (>= L) with local bit j between two DEVICES driven by this one process (peer
 // copies through staging buffers); every other configuration goes through exchange_multi
 static int exchange_peer_copy(qsv_handle* h, int G, int j) {
-  for (Shard& s : h->shards) { s.sums_valid = false; s.tile_valid = false; s.h_tsums_valid = false; }
+  for (Shard& s : h->shards) { s.sums_valid = false; s.tile_valid = false; s.h_tsums_valid = false; s.d_super_valid = 0; }
   const int gb = G - h->L;
   const uint64_t n = amps_local(h);
   const uint64_t nhalf = n >> 1;

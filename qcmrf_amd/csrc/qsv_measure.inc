@@ -11,6 +11,32 @@ struct SumView {                 // host copy of a shard's block / tile sums, ow
   double operator[](size_t i) const { return p[i]; }
 };
 
+// the super sums of a shard's tile sums on the device (d_super), formed once per state: the host copy block_sums
+// fetches and the sampler's device walk (sample_chain) share them
+static int super_sums(Shard& s, uint64_t nsuper) {
+  CHK(shard_set(s));
+  if (s.h_tsums_cap < nsuper) {
+    if (s.h_tsums) HIPCHK(hipHostFree(s.h_tsums));
+    if (s.d_super) HIPCHK(hipFree(s.d_super));
+    if (s.d_walk) HIPCHK(hipFree(s.d_walk));
+    s.h_tsums = nullptr;
+    s.d_super = nullptr;
+    s.d_walk = nullptr;
+    s.h_tsums_cap = 0;
+    s.d_super_valid = 0;
+    HIPCHK(hipHostMalloc(&s.h_tsums, nsuper * sizeof(double), hipHostMallocDefault));
+    HIPCHK(hipMalloc(&s.d_super, nsuper * sizeof(double)));
+    HIPCHK(hipMalloc(&s.d_walk, (nsuper + 2) * sizeof(double)));
+    s.h_tsums_cap = nsuper;
+  }
+  if (s.d_super_valid & 1) return QSV_OK;
+  hipLaunchKernelGGL(k_supersum, dim3((unsigned)std::min<uint64_t>(nsuper, 65535)), dim3(QSV_TPB), 0, s.stream,
+                     s.d_tsums, s.tile_nblocks, s.d_super, nsuper);
+  HIPCHK(hipGetLastError());
+  s.d_super_valid |= 1;
+  return QSV_OK;
+}
+
 static int block_sums(qsv_handle* h, Shard& s, SumView& sums) {
   if (s.tile_valid && h->opt_cache_sums) {   // left behind by the last pass of the program: no read pass
     // pinned staging buffer, fetched once per state (norm and sample of one run share it): a
@@ -18,19 +44,7 @@ static int block_sums(qsv_handle* h, Shard& s, SumView& sums) {
     // the sampling itself
     const uint64_t nsuper = (s.tile_nblocks + QSV_SUPER - 1) / QSV_SUPER;
     if (!s.h_tsums_valid) {
-      CHK(shard_set(s));
-      if (s.h_tsums_cap < nsuper) {
-        if (s.h_tsums) HIPCHK(hipHostFree(s.h_tsums));
-        if (s.d_super) HIPCHK(hipFree(s.d_super));
-        s.h_tsums = nullptr;
-        s.d_super = nullptr;
-        HIPCHK(hipHostMalloc(&s.h_tsums, nsuper * sizeof(double), hipHostMallocDefault));
-        HIPCHK(hipMalloc(&s.d_super, nsuper * sizeof(double)));
-        s.h_tsums_cap = nsuper;
-      }
-      hipLaunchKernelGGL(k_supersum, dim3((unsigned)std::min<uint64_t>(nsuper, 65535)), dim3(QSV_TPB), 0, s.stream,
-                         s.d_tsums, s.tile_nblocks, s.d_super, nsuper);
-      HIPCHK(hipGetLastError());
+      CHK(super_sums(s, nsuper));
       HIPCHK(hipMemcpyAsync(s.h_tsums, s.d_super, nsuper * sizeof(double), hipMemcpyDeviceToHost, s.stream));
       HIPCHK(hipStreamSynchronize(s.stream));
       s.h_tsums_valid = true;
@@ -81,12 +95,98 @@ extern "C" int qsv_norm(qsv_handle* h, double* out) {
   return QSV_OK;
 }
 
+// qsv_sample on the tile sums of a handle's one shard, without a host round trip (option sample_chain, DESIGN §6): the
+// super sums, their walk (k_walk_super) and every later step stay on the device, the host draws the spacings while the
+// first two kernels run and waits once, for the words and the total.  A deferred shard's shots are located inside the
+// generator (QSV_GEN_LOCATE): no tile is stored.  The arithmetic is that of qsv_sample's host walk, operation for operation:
+// the same words come out.
+static int sample_chain(qsv_handle* h, Shard& sh, uint64_t shots, uint64_t seed, const MeasMap& mm, uint64_t* out_bits) {
+  const uint64_t nsuper = (sh.tile_nblocks + QSV_SUPER - 1) / QSV_SUPER;
+  CHK(super_sums(sh, nsuper));
+  if (!(sh.d_super_valid & 2)) {
+    hipLaunchKernelGGL(k_walk_super, dim3(1), dim3(64), 0, sh.stream, sh.d_super, (int)nsuper, sh.d_walk);
+    HIPCHK(hipGetLastError());
+    sh.d_super_valid |= 2;
+  }
+  // one pinned slot: the total the device leaves (first 256 bytes), then the running sums of the spacings, unscaled, which
+  // k_walk_shots reads in place
+  void* slot = nullptr;
+  CHK(arena_slot(sh, 256 + shots * sizeof(double), &slot));
+  double* h_total = reinterpret_cast<double*>(slot);
+  double* raw = reinterpret_cast<double*>(reinterpret_cast<char*>(slot) + 256);
+  *h_total = 0.0;
+  std::mt19937_64 rng(seed);
+  double run = 0.0;
+  for (uint64_t s = 0; s < shots; ++s) {
+    run += -std::log((double)((rng() >> 11) + 1ull) * (1.0 / 9007199254740992.0));
+    raw[s] = run;
+  }
+  run += -std::log((double)((rng() >> 11) + 1ull) * (1.0 / 9007199254740992.0));
+  if (sh.sample_cap < shots) {
+    if (sh.d_sblk) { HIPCHK(hipFree(sh.d_sblk)); HIPCHK(hipFree(sh.d_sres)); HIPCHK(hipFree(sh.d_sout)); }
+    sh.d_sblk = nullptr; sh.d_sres = nullptr; sh.d_sout = nullptr;
+    sh.sample_cap = 0;
+    const size_t cap = std::max<size_t>(shots, 8192);
+    HIPCHK(hipMalloc(&sh.d_sblk, cap * sizeof(uint64_t)));
+    HIPCHK(hipMalloc(&sh.d_sres, cap * sizeof(double)));
+    HIPCHK(hipMalloc(&sh.d_sout, cap * sizeof(uint64_t)));
+    sh.sample_cap = cap;
+  }
+  hipLaunchKernelGGL(k_walk_shots, dim3((unsigned)std::min<uint64_t>((shots + QSV_TPB - 1) / QSV_TPB, 1024)), dim3(QSV_TPB), 0, sh.stream,
+                     sh.d_walk, (int)nsuper, raw, run, shots, sh.d_sblk, sh.d_sres, h_total);
+  HIPCHK(hipGetLastError());
+  hipLaunchKernelGGL(k_locate_super, dim3((unsigned)std::min<uint64_t>(shots, 65535)), dim3(64), 0, sh.stream,
+                     sh.d_tsums, sh.tile_nblocks, sh.d_sblk, sh.d_sres, shots);
+  HIPCHK(hipGetLastError());
+  if (sh.deferred) {
+    CHK(launch_recipe(h, sh, QSV_GEN_LOCATE, sh.d_sblk, shots, sh.d_sres, sh.d_sout));
+    HIPCHK(hipGetLastError());
+    h->n_listed += 1;
+  } else {
+    const dim3 g((unsigned)std::min<uint64_t>(shots, 65535));
+#define LT(RR) hipLaunchKernelGGL((k_locate_tile<RR>), g, dim3(QSV_TPB), 0, sh.stream, sh.amp, sh.tile_ins, sh.tile_rp, sh.tile_lp, sh.d_sblk, sh.d_sres, sh.d_sout, shots, sh.tile_xor, sh.zmask)
+    switch (sh.tile_R) {
+      case 0: LT(0); break; case 1: LT(1); break; case 2: LT(2); break; case 3: LT(3); break;
+      case 4: LT(4); break; case 5: LT(5); break; default: LT(6); break;
+    }
+#undef LT
+    HIPCHK(hipGetLastError());
+  }
+  hipLaunchKernelGGL(k_remap_bits, dim3((unsigned)((shots + QSV_TPB - 1) / QSV_TPB)), dim3(QSV_TPB), 0, sh.stream,
+                     sh.d_sout, shots, (uint64_t)sh.index << h->L, mm);
+  HIPCHK(hipGetLastError());
+  std::vector<uint64_t> idx(shots);
+  HIPCHK(hipMemcpyAsync(idx.data(), sh.d_sout, shots * sizeof(uint64_t), hipMemcpyDeviceToHost, sh.stream));
+  HIPCHK(hipStreamSynchronize(sh.stream));
+  const double total = *reinterpret_cast<volatile double*>(h_total);
+  if (!(total > 0)) return fail(QSV_E_BADARG, "state has zero norm on this process; nothing to sample");
+  for (uint64_t s = shots - 1; s > 0; --s) {
+    const uint64_t k = rng() % (s + 1);
+    std::swap(idx[s], idx[k]);
+  }
+  memcpy(out_bits, idx.data(), shots * sizeof(uint64_t));
+  return QSV_OK;
+}
+
 extern "C" int qsv_sample(qsv_handle* h, uint64_t shots, uint64_t seed, const int* meas_qubits, int n_meas,
                           uint64_t* out_bits) {
   if (!h || (shots && !out_bits)) return fail(QSV_E_BADARG, "NULL argument");
   if (meas_qubits && (n_meas < 0 || n_meas > 64)) return fail(QSV_E_BADARG, "n_meas %d out of range", n_meas);
   if (meas_qubits) for (int i = 0; i < n_meas; ++i) if (meas_qubits[i] >= 0) CHK(check_qubit(h, meas_qubits[i], "measured"));
   if (shots == 0) return QSV_OK;
+  if (h->opt_sample_chain && h->shards.size() == 1) {
+    // one shard, the tile path, a power-of-two tile count within k_walk_super's reach, the spacings within a quarter of the
+    // arena; everything else walks on the host as before
+    Shard& sh = h->shards[0];
+    const uint64_t nt = sh.tile_nblocks;
+    if (sh.tile_valid && h->opt_cache_sums && nt && !(nt & (nt - 1)) && (nt + QSV_SUPER - 1) / QSV_SUPER <= QSV_WALK_MAX &&
+        256 + shots * sizeof(double) <= sh.arena_bytes / 4 && (!sh.deferred || sh.zmask == sh.recipe.zskip)) {
+      MeasMap cm;
+      cm.n = meas_qubits ? n_meas : -1;
+      for (int j = 0; j < 64; ++j) cm.pos[j] = (meas_qubits && j < n_meas) ? (signed char)meas_qubits[j] : (signed char)-1;
+      return sample_chain(h, sh, shots, seed, cm, out_bits);
+    }
+  }
   const size_t ns = h->shards.size();
   std::vector<SumView> sums(ns);
   std::vector<double> mass(ns);
@@ -360,7 +460,7 @@ static int amp_copy(qsv_handle* h, uint64_t start, uint64_t count, double* out, 
       CHK(shard_set(*sh));
       HIPCHK(hipStreamSynchronize(sh->stream));
       HIPCHK(hipMemcpy(sh->amp + off, in + 2 * done, m * sizeof(cplx), hipMemcpyHostToDevice));
-      sh->sums_valid = false; sh->tile_valid = false; sh->h_tsums_valid = false;
+      sh->sums_valid = false; sh->tile_valid = false; sh->h_tsums_valid = false; sh->d_super_valid = 0;
     }
     done += m;
   }
@@ -393,7 +493,7 @@ extern "C" int qsv_copy_state(qsv_handle* dst, qsv_handle* src) {
     b.zmask = a.zmask;
     b.sums_valid = false;
     b.tile_valid = false;
-    b.h_tsums_valid = false;
+    b.h_tsums_valid = false; b.d_super_valid = 0;
     dst->stats.per_kind[QSV_K_SWAP].launches += 1;
     dst->stats.per_kind[QSV_K_SWAP].algorithmic_bytes += 2.0 * (double)bytes;
   }

@@ -211,7 +211,7 @@ template <int R, bool NT, int ZR, int FORM>
 static int launch_init_prod_k(const qsv_handle* h, const Shard& s, uint64_t ntiles, const BitIns& ins, const RegPos& rp,
                               const LanePos& lp, const ProdFactor* f, const ProdCounts& cnt, const ProdGroup& grp,
                               const cplx* tab, int ntab, uint64_t nonmask, double initval, uint64_t zskip,
-                              unsigned zreg, const uint64_t* list, uint64_t nlist) {
+                              unsigned zreg, const uint64_t* list, uint64_t nlist, const double* resid, uint64_t* out) {
   // persistent grid: every workgroup the chip holds at once at this kernel's occupancy (option init_prod_grid: fewer)
   const size_t lds = (size_t)ntab * sizeof(cplx) + (size_t)cnt.nfac * (16 + 64 * sizeof(uint16_t)) +
                      (grp.nb ? ((size_t)cnt.nfac << grp.nb) * sizeof(uint16_t) : 0);
@@ -228,27 +228,29 @@ static int launch_init_prod_k(const qsv_handle* h, const Shard& s, uint64_t ntil
   if (per_cu < 1) return fail(QSV_E_UNSUPPORTED, "k_init_prod does not fit a CU (%zu B of LDS)", lds);
   uint64_t grid = (uint64_t)per_cu * (uint64_t)s.n_cu;
   if (h->opt_init_prod_grid > 0) grid = std::min<uint64_t>(grid, (uint64_t)h->opt_init_prod_grid);
-  if (FORM == QSV_GEN_LISTED) grid = std::max<uint64_t>(1, std::min(grid, nlist));   // one workgroup per entry, grid-stride beyond
+  if (FORM == QSV_GEN_LISTED || FORM == QSV_GEN_LOCATE) grid = std::max<uint64_t>(1, std::min(grid, nlist));   // one workgroup per entry, grid-stride beyond
   else grid = std::min(grid, ntiles >> grp.nb);   // one workgroup per group at most
   hipLaunchKernelGGL((k_init_prod<R, NT, ZR, FORM>), dim3((unsigned)grid), dim3(QSV_TPB), std::max<size_t>(lds, 16), s.stream,
-                     s.amp, ntiles, ins, rp, lp, f, cnt, grp, tab, ntab, nonmask, initval, zskip, zreg, list, nlist);
+                     s.amp, ntiles, ins, rp, lp, f, cnt, grp, tab, ntab, nonmask, initval, zskip, zreg, list, nlist, resid, out);
   return QSV_OK;
 }
 template <int R>
 static int launch_init_prod(const qsv_handle* h, const Shard& s, int form, uint64_t ntiles, const BitIns& ins, const RegPos& rp, const LanePos& lp,
                             const ProdFactor* f, const ProdCounts& cnt, const ProdGroup& grp, const cplx* tab, int ntab,
                             uint64_t nonmask, double initval, uint64_t zskip, unsigned zreg,
-                            const uint64_t* list = nullptr, uint64_t nlist = 0) {
+                            const uint64_t* list = nullptr, uint64_t nlist = 0, const double* resid = nullptr, uint64_t* out = nullptr) {
   // non-temporal stores pay on big shards (34 qubits: 6.86 -> 7.11 TB/s; 28 qubits: -1 %; profiles/r02_nt_variants.log)
   const bool nt = h->opt_nt > 0 || (h->opt_init_prod_nt < 0 && h->L >= QSV_GEN_NT_MIN_L) || h->opt_init_prod_nt > 0;
   // the top register bit as the only implied-zero register bit (the layout at 34 qubits) is a compile-time case; any
   // other zreg, none included, is read at run time (a compile-time zreg = 0 took 127 registers at R = 4 against 109
   // and wrote the full state 8 % slower)
   constexpr int ZTOP = 1 << (R - 1);
-#define QSV_LIP(NT, ZR, FORM) return launch_init_prod_k<R, NT, ZR, FORM>(h, s, ntiles, ins, rp, lp, f, cnt, grp, tab, ntab, nonmask, initval, zskip, zreg, list, nlist)
+#define QSV_LIP(NT, ZR, FORM) return launch_init_prod_k<R, NT, ZR, FORM>(h, s, ntiles, ins, rp, lp, f, cnt, grp, tab, ntab, nonmask, initval, zskip, zreg, list, nlist, resid, out)
   // the listed form stores a few tiles that k_locate_tile reads next: one instantiation per (R, ZR), whatever the
   // non-temporal choice of the writing form
   if (form == QSV_GEN_LISTED) { if (zreg == ZTOP) QSV_LIP(false, ZTOP, QSV_GEN_LISTED); QSV_LIP(false, -1, QSV_GEN_LISTED); }
+  // the locating form stores nothing: one instantiation per (R, ZR) likewise
+  if (form == QSV_GEN_LOCATE) { if (zreg == ZTOP) QSV_LIP(false, ZTOP, QSV_GEN_LOCATE); QSV_LIP(false, -1, QSV_GEN_LOCATE); }
   if (nt) { if (zreg == ZTOP) QSV_LIP(true, ZTOP, QSV_GEN_WRITE); QSV_LIP(true, -1, QSV_GEN_WRITE); }
   if (zreg == ZTOP) QSV_LIP(false, ZTOP, QSV_GEN_WRITE);
   QSV_LIP(false, -1, QSV_GEN_WRITE);
@@ -300,10 +302,11 @@ static int launch_tile_sums_expand(const qsv_handle* h, const Shard& s, uint64_t
   return QSV_OK;
 }
 
-// the generator from a shard's recipe: the writing form (realize) or the listed form (qsv_sample)
-static int launch_recipe(const qsv_handle* h, const Shard& s, int form, const uint64_t* list, uint64_t nlist) {
+// the generator from a shard's recipe: the writing form (realize), the listed form or the locating form (qsv_sample)
+static int launch_recipe(const qsv_handle* h, const Shard& s, int form, const uint64_t* list, uint64_t nlist,
+                         const double* resid = nullptr, uint64_t* out = nullptr) {
   const GenRecipe& rc = s.recipe;
-#define QSV_LR(RR) return launch_init_prod<RR>(h, s, form, rc.ntiles, rc.ins, rc.rp, rc.lp, rc.dfac, rc.cnt, rc.grp, rc.dtab, rc.ntab, rc.nonmask, rc.initval, rc.zskip, rc.zreg, list, nlist)
+#define QSV_LR(RR) return launch_init_prod<RR>(h, s, form, rc.ntiles, rc.ins, rc.rp, rc.lp, rc.dfac, rc.cnt, rc.grp, rc.dtab, rc.ntab, rc.nonmask, rc.initval, rc.zskip, rc.zreg, list, nlist, resid, out)
   switch (rc.R) {
     case 3: QSV_LR(3);
     case 4: QSV_LR(4);
@@ -323,6 +326,7 @@ static int realize(qsv_handle* h, Shard& s) {
   const uint64_t n = amps_local(h);
   CHK(shard_set(s));
   const bool sv = s.sums_valid, tv = s.tile_valid, hv = s.h_tsums_valid;
+  const int dv = s.d_super_valid;
   int lr = QSV_OK;
   const int r = launch(h, s, QSV_K_INIT_PROD, 16.0 * (double)(n >> __builtin_popcountll(s.recipe.zskip)), [&] {
     lr = launch_recipe(h, s, QSV_GEN_WRITE, nullptr, 0);
@@ -333,6 +337,7 @@ static int realize(qsv_handle* h, Shard& s) {
   s.sums_valid = sv;
   s.tile_valid = tv;
   s.h_tsums_valid = hv;
+  s.d_super_valid = dv;
   h->n_realize += 1;
   return QSV_OK;
 }
@@ -569,18 +574,37 @@ static int flush_init_product_r(qsv_handle* h, Shard& s, PendingGroup& g, bool f
   const size_t tbytes = tables.size() * sizeof(double);
   void* dfac = nullptr;
   void* dtab = nullptr;
+  void* dfin = nullptr;                             // a factored sums launch: the inner factors in their own order, the tile-uniform ones
+  void* dtuf = nullptr;
   if (defer) {
+    // one upload: [factor descriptors | tables | inner factors | tile-uniform factors], each part at a 256-byte offset
+    // of one pinned block, sent with one copy into the recipe buffer (the last two parts serve this pass's sums launch
+    // only; four copies were four 5 us transfers in a row ahead of k_prod_sums)
+    const size_t ibytes = factored ? in.uni.size() * sizeof(ProdFactor) : 0;
+    const size_t ubytes = factored ? tuf.size() * sizeof(ExpandFactor) : 0;
+    const size_t otab = fbytes, ofin = (otab + tbytes + 255) & ~size_t(255), otuf = (ofin + ibytes + 255) & ~size_t(255);
+    const size_t need = otuf + ubytes;
     GenRecipe& rc = s.recipe;
-    if (rc.cap < fbytes + tbytes) {
+    if (rc.cap < need) {
       if (rc.d_buf) { HIPCHK(hipStreamSynchronize(s.stream)); HIPCHK(hipFree(rc.d_buf)); }
       rc.d_buf = nullptr;
       rc.cap = 0;
-      const size_t cap = std::max<size_t>(fbytes + tbytes, 64u << 10);
+      const size_t cap = std::max<size_t>(need, 64u << 10);
       HIPCHK(hipMalloc(&rc.d_buf, cap));
       rc.cap = cap;
     }
-    CHK(arena_put(s, uni.data(), uni.size() * sizeof(ProdFactor), &dfac, rc.d_buf));
-    CHK(arena_put(s, tables.data(), tbytes, &dtab, rc.d_buf + fbytes));
+    void* hb = nullptr;
+    CHK(arena_slot(s, need, &hb));
+    char* hp = reinterpret_cast<char*>(hb);
+    memcpy(hp, uni.data(), uni.size() * sizeof(ProdFactor));
+    memcpy(hp + otab, tables.data(), tbytes);
+    if (ibytes) memcpy(hp + ofin, in.uni.data(), ibytes);
+    if (ubytes) memcpy(hp + otuf, tuf.data(), ubytes);
+    HIPCHK(hipMemcpyAsync(rc.d_buf, hp, need, hipMemcpyHostToDevice, s.stream));
+    dfac = rc.d_buf;
+    dtab = rc.d_buf + otab;
+    if (ibytes) dfin = rc.d_buf + ofin;
+    if (ubytes) dtuf = rc.d_buf + otuf;
     rc.R = R; rc.ntiles = ntiles; rc.ins = ins; rc.rp = rp; rc.lp = lp; rc.cnt = cnt; rc.grp = grp; rc.ntab = ntab;
     rc.nonmask = nonmask; rc.zskip = zskip; rc.initval = g.initval; rc.zreg = zreg;
     rc.dfac = reinterpret_cast<const ProdFactor*>(dfac);
@@ -588,12 +612,10 @@ static int flush_init_product_r(qsv_handle* h, Shard& s, PendingGroup& g, bool f
   } else {
     CHK(arena_put(s, uni.data(), uni.size() * sizeof(ProdFactor), &dfac));
     CHK(arena_put(s, tables.data(), tbytes, &dtab));
-  }
-  void* dfin = nullptr;                             // a factored sums launch: the inner factors in their own order, the tile-uniform ones
-  void* dtuf = nullptr;
-  if (factored) {
-    if (!in.uni.empty()) CHK(arena_put(s, in.uni.data(), in.uni.size() * sizeof(ProdFactor), &dfin));
-    if (!tuf.empty()) CHK(arena_put(s, tuf.data(), tuf.size() * sizeof(ExpandFactor), &dtuf));
+    if (factored) {
+      if (!in.uni.empty()) CHK(arena_put(s, in.uni.data(), in.uni.size() * sizeof(ProdFactor), &dfin));
+      if (!tuf.empty()) CHK(arena_put(s, tuf.data(), tuf.size() * sizeof(ExpandFactor), &dtuf));
+    }
   }
   h->stats.fused_gates += g.ops.size();
   const double initval = g.initval;
