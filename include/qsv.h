@@ -209,6 +209,24 @@ int qsv_norm(qsv_handle* h, double* out);
 int qsv_sample(qsv_handle* h, uint64_t shots, uint64_t seed, const int* meas_qubits,
                int n_meas, uint64_t* out_bits);
 
+/* qsv_sample restricted to the basis states g with (g & fix_mask) == fix_val (global index bits, shard bits allowed):
+ * shots are drawn from |amp|^2 over those states, normalised by their mass on this process; *mass receives that
+ * mass (not normalised by qsv_norm; mass may be NULL).  shots == 0: the mass only.  fix_mask == 0: the words of
+ * qsv_sample, word for word, and mass = qsv_norm.  mass == 0 with shots > 0: QSV_E_BADARG "post-selected outcome has
+ * zero probability".  fix_val & ~fix_mask != 0, or a mask bit at or above n_qubits: QSV_E_BADARG.
+ * The contract is qsv_sample's, applied to the matching states: std::mt19937_64(seed) draws shots + 1 spacings, the
+ * uniforms are scaled to the conditional mass, the inverse-CDF walk runs in ascending global index over the matching
+ * states, the same Fisher-Yates shuffle follows.
+ * Cost: with f fixed bits local to a shard, the matching amplitudes are a sub-cube of 2^(L-f) entries ("compact index
+ * space"); one read pass over them (booked under QSV_K_PROB with 16 B each) and one locating kernel, nothing else of the
+ * shard is touched, implied zeros are not read.  The sums of a conditioned call are NOT cached: a second call repeats
+ * the 2^-f pass.  At most 28 fixed bits local to a shard (QSV_E_UNSUPPORTED beyond).
+ * A deferred shard (qsv_state_info) is not written out when the call fixes a block bit of the generator's tile index:
+ * the tiles that hold the sub-cube are listed and stored (one listed_launches), the shard stays deferred; otherwise, and
+ * by option post_select_list, it is realised first. */
+int qsv_sample_cond(qsv_handle* h, uint64_t shots, uint64_t seed, const int* meas_qubits, int n_meas,
+                    uint64_t fix_mask, uint64_t fix_val, uint64_t* out_bits, double* mass);
+
 /* copy amplitudes [start, start+count) of the GLOBAL index space into out (2*count doubles);
  * the range must lie inside shards owned by this process. */
 int qsv_get_amplitudes(qsv_handle* h, uint64_t start, uint64_t count, double* out);
@@ -436,6 +454,9 @@ int qsv_timer_end(qsv_handle* h, double* ms);
  *   measurement cache_sums [1], fused_sums [1]   keep / produce per-tile |amp|^2 sums in the last pass of a program
  *               sample_chain [1]   qsv_sample on one shard's tile sums: 1 the walk over the super sums on the device, a deferred shard's
  *                                  shots located inside the generator (nothing stored), one host wait; 0 the host walk.  Same words.
+ *               post_select_list [-1]  qsv_sample_cond on a deferred shard: -1 the tiles holding the matching amplitudes are listed and
+ *                                  stored when they are at most 1/16 of the tiles and the list fits a quarter of the arena, else the
+ *                                  state is realised; 0 always realised; 1 listed whenever a block bit is fixed and the list fits.  Same words.
  *   kernels     unroll [4], lowt_shuffle [1], pair_variant [0], kq_mfma [1], blocks_per_cu [65536]
  *               swizzle [1]        one-gate kernels: lane bit 5 of a wave access carries address bit 11 (two 512-byte runs 32 KiB apart);
  *                                  1 from 2^26 amplitudes per shard, 2 from 2^14, 0 never        lane_map_min_l [26]  same for k_multi tiles other than bits 6..10

@@ -26,7 +26,7 @@ K_COUNT = len(K_NAMES)
 OPTION_DEFAULTS = {"blocks_per_cu": 1 << 16, "unroll": 4, "lowt_shuffle": 1, "nontemporal": -1, "lane_targets": 1,
                    "cache_sums": 1, "fused_sums": 1, "pair_variant": 0, "kq_mfma": 1, "zero_tracking": 0, "implied_zeros": 1, "lane_map": 1,
                    "init_prod_bit0": 0, "init_prod_r": 0, "init_prod": 1, "pass_hints": 1, "dyn_lanes": 3, "multi_r": 5,
-                   "exchange_chunk_log2": 24, "xframe": 1, "pass_budget": 0, "trace_passes": 0, "single_shortcut": 1, "pass_max_ops": 56, "general_r": 4, "general_light_r": 5, "swizzle": 1, "lane_map_min_l": 26, "blocksum_variant": 6, "kq_chunked": 0, "fold_init_h": 1, "general_combos": 1, "lowctl_mask": 1, "kq_variant": -1, "kq3_tile": 1, "kq_blocks_per_cu": 0, "kq_debug": 0, "kq_order": 1, "multi_nt": -1, "init_prod_nt": -1, "init_prod_grid": 0, "init_prod_group": -1, "defer_state": -1, "sums_factored": -1, "noisy_grid": 0, "sample_chain": 1}
+                   "exchange_chunk_log2": 24, "xframe": 1, "pass_budget": 0, "trace_passes": 0, "single_shortcut": 1, "pass_max_ops": 56, "general_r": 4, "general_light_r": 5, "swizzle": 1, "lane_map_min_l": 26, "blocksum_variant": 6, "kq_chunked": 0, "fold_init_h": 1, "general_combos": 1, "lowctl_mask": 1, "kq_variant": -1, "kq3_tile": 1, "kq_blocks_per_cu": 0, "kq_debug": 0, "kq_order": 1, "multi_nt": -1, "init_prod_nt": -1, "init_prod_grid": 0, "init_prod_group": -1, "defer_state": -1, "sums_factored": -1, "noisy_grid": 0, "sample_chain": 1, "post_select_list": -1}
 
 OP_INIT_ZERO, OP_INIT_UNIFORM, OP_1Q, OP_MCX, OP_DIAG, OP_MCPHASE, OP_MUX, OP_KQ, OP_SWAP, OP_PAULI, OP_KRAUS, OP_MEASURE = range(12)
 NOISY_MAX_QUBITS = 13     # qsv_noisy_sample: one trajectory's state lives in the LDS of one workgroup
@@ -83,6 +83,7 @@ SIGNATURES = {
     "qsv_norm": (_i, [_vp, _dp]),
     "qsv_expect_diag": (_i, [_vp, _ip, _i, _dp, _u64, _u64, _dp]),
     "qsv_sample": (_i, [_vp, _u64, _u64, _ip, _i, _u64p]),
+    "qsv_sample_cond": (_i, [_vp, _u64, _u64, _ip, _i, _u64, _u64, _u64p, _dp]),
     "qsv_get_amplitudes": (_i, [_vp, _u64, _u64, _dp]),
     "qsv_set_amplitudes": (_i, [_vp, _u64, _u64, _dp]),
     "qsv_copy_state": (_i, [_vp, _vp]),
@@ -457,6 +458,17 @@ class Engine:
             qa, qp = _ia(meas_qubits)
             _chk(self._lib.qsv_sample(self._h, int(shots), int(seed), qp, len(qa), out.ctypes.data_as(_u64p)))
         return out
+
+    def sample_cond(self, shots, seed, meas_qubits=None, fix_mask=0, fix_val=0):
+        """post-selected shots: ``shots`` words drawn from |amp|^2 over the basis states g with (g & fix_mask) == fix_val
+        (global index bits), and the mass of those states (not normalised by ``norm()``).  shots = 0: the mass only.
+        ValueError where that mass is 0 and shots are asked for (qsv_sample_cond)."""
+        out = np.zeros(int(shots), dtype=np.uint64)
+        mass = C.c_double(0.0)
+        qa, qp = (None, None) if meas_qubits is None else _ia(meas_qubits)
+        _chk(self._lib.qsv_sample_cond(self._h, int(shots), int(seed), qp, 0 if qa is None else len(qa), int(fix_mask), int(fix_val),
+                                       out.ctypes.data_as(_u64p), C.byref(mass)))
+        return out, mass.value
 
     def amplitudes(self, start=0, count=None):
         if count is None:

@@ -276,6 +276,7 @@ class QsvBackend:
         nmeasure = opts.get("noisy_measure", "deferred")
         if nmeasure not in _NOISY_MEASURES:
             raise ValueError("unknown noisy_measure %r; a noisy shot takes its measurements %s" % (nmeasure, ", ".join(_NOISY_MEASURES)))
+        post = self._post_select_of(opts, len(circs), method)
         if method == "density_matrix":
             if nmeasure == "in_place":
                 raise ValueError("method='density_matrix' defers every measurement; noisy_measure='in_place' belongs to noisy shots")
@@ -313,11 +314,49 @@ class QsvBackend:
                     prepared = nxt.result()
                     if i + 1 < len(circs):
                         nxt = pool.submit(self._prepare, circs[i + 1], opts)
-                    exps.append(self._run_one(circs[i], int(shots), int(seed_simulator) + i, opts, prepared))
+                    exps.append(self._run_one(circs[i], int(shots), int(seed_simulator) + i, opts, prepared, post_select=post and post[i]))
         else:
             for i, c in enumerate(circs):
-                exps.append(self._run_one(c, int(shots), int(seed_simulator) + i, opts))
+                exps.append(self._run_one(c, int(shots), int(seed_simulator) + i, opts, post_select=post and post[i]))
         return Job(Result(exps, self._name))
+
+    def _post_select_of(self, opts, n_circuits, method):
+        """the ``post_select`` option as one ``{classical bit: 0 | 1}`` per circuit, or None; refuses what the
+        post-selected sampler does not cover"""
+        post = opts.get("post_select")
+        if post is None:
+            return None
+        if method != "statevector":
+            raise ValueError("post_select belongs to method='statevector', not method=%r" % (method,))
+        if self._noise_of(opts) is not None:
+            raise ValueError("post_select takes no noise_model: the conditioned state of a noisy run is not a state vector")
+        comm = opts["comm"] or SingleProcess()
+        if comm.world > 1:
+            raise ValueError("post_select takes one process (a process group of %d ranks was given; limit 1)" % comm.world)
+        if isinstance(post, dict):
+            post = [post] * n_circuits
+        post = list(post)
+        if len(post) != n_circuits or not all(isinstance(d, dict) for d in post):
+            raise ValueError("post_select is one {classical bit: 0 | 1} dict, or a list of %d of them (one per circuit)" % n_circuits)
+        return post
+
+    @staticmethod
+    def _post_select_mask(post, ing, pl):
+        """(fix_mask, fix_val) over the physical index bits: classical bit -> the qubit measured into it -> its position"""
+        fixed = {}
+        for c, v in post.items():
+            if c not in ing.measure:
+                raise ValueError("post_select names classical bit %r, which no measurement writes" % (c,))
+            if v not in (0, 1):
+                raise ValueError("post_select fixes classical bit %r to %r; a bit reads 0 or 1" % (c, v))
+            q = ing.measure[c]
+            if fixed.setdefault(q, int(v)) != int(v):
+                raise ValueError("post_select fixes qubit %d (classical bit %r) to both 0 and 1" % (q, c))
+        fm = fv = 0
+        for q, v in fixed.items():
+            fm |= 1 << pl.layout[q]
+            fv |= v << pl.layout[q]
+        return fm, fv
 
     @staticmethod
     def _noise_of(opts):
@@ -607,7 +646,7 @@ class QsvBackend:
             vals |= ((bits >> np.uint64(j)) & np.uint64(1)) << np.uint64(c)
         return vals
 
-    def _run_one(self, circuit, shots, seed, opts, prepared=None):
+    def _run_one(self, circuit, shots, seed, opts, prepared=None, post_select=None):
         if opts.get("method", "statevector") == "trajectory":
             return self._run_trajectory(circuit, shots, seed, opts)
         comm = opts["comm"] or SingleProcess()
@@ -615,9 +654,10 @@ class QsvBackend:
         t1 = time.perf_counter()
         t0 = t1 - t_compile
 
+        fix = None if post_select is None else self._post_select_mask(post_select, ing, pl)
         eng = self._get_engine(ing.num_qubits, opts)
         self._apply_engine_options(eng, opts)      # (the plan above was compiled for exactly this call's options)
-        if (shots <= 0 or not ing.measure) and "defer_state" not in (opts["engine_options"] or {}):
+        if (shots <= 0 or not ing.measure) and fix is None and "defer_state" not in (opts["engine_options"] or {}):
             # nothing will be sampled, so the caller is after the state: have the generator write it at once instead of
             # leaving tile sums first and writing it on the first read (the next run's options undo this)
             eng.set_option("defer_state", 0)
@@ -645,7 +685,22 @@ class QsvBackend:
             meas_phys = [pl.layout[ing.measure[c]] for c in clist]
             direct = False
         counts = {}
-        if clist and shots > 0:
+        post_meta = {}
+        if fix is not None:
+            # every shot from the state conditioned on the fixed bits (qsv_sample_cond): the words keep their full width,
+            # the fixed bits reading their values; the mass of the condition over the norm is its exact probability
+            before = eng.state_info()
+            words, mass = eng.sample_cond(max(shots, 0) if clist else 0, seed, meas_phys, fix[0], fix[1])
+            after = eng.state_info()
+            if not mass > 0:
+                raise ValueError("post-selected outcome %r has zero probability" % (post_select,))
+            if clist and shots > 0:
+                uv, uc = np.unique(self._to_clbits(words, clist, direct), return_counts=True)
+                counts = _format_keys(uv, uc, ing.num_clbits, ing.creg_sizes)
+            post_meta = {"post_select": dict(post_select), "post_select_probability": mass / eng.norm(),
+                         "post_select_path": "stored" if not before["deferred"] else
+                                             "realized" if after["realize_calls"] > before["realize_calls"] else "listed"}
+        elif clist and shots > 0:
             if comm.world > 1:
                 # One round trip and one one-way send per run: (1) all-gather of one double per rank, the shard's
                 # probability mass -> the common multinomial split of the shots over the shards (same seed on every
@@ -686,6 +741,7 @@ class QsvBackend:
                 "n_exchanges": pl.n_exchanges, "n_shards": n_shards, "layout": list(pl.layout),
                 "fusion": opts["fusion"], "time_compile": t1 - t0, "time_evolve": t2 - t1,
                 "time_sample": t3 - t2, "time_taken": t3 - t0, "seed_simulator": seed}
+        meta.update(post_meta)
         if comm.world > 1 and opts.get("gather_counts", "root") != "all":
             meta["counts_on_rank"] = 0
         if opts["profile"]:

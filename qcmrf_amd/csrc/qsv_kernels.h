@@ -443,6 +443,71 @@ __global__ __launch_bounds__(64) void k_locate(const cplx* __restrict__ amp, uin
   }
 }
 
+// Post-selected sampling (qsv_sample_cond): the amplitudes whose local fixed bits F hold the post-selected
+// values form a sub-cube of n_c = 2^(L - |F|) entries; compact index j stands for the address ins_bits(j, F) | val,
+// ascending in j as in the address.  The two kernels below are k_blocksum and k_locate over that compact index space: a
+// conditioned draw reads 2^-|F| of the shard.  An address with a zmask bit set is an implied zero: it contributes 0 and
+// is not loaded.  With every fixed bit at or above bit 12 a compact block is one contiguous 64 KiB run (the stream
+// k_blocksum reads); lower fixed bits make the loads strided, which is inherent.
+// sums[b] = sum |amp|^2 over compact block b, k_blocksum's reduction tree (a fixed function of the state)
+template <bool NT>
+__global__ __launch_bounds__(QSV_TPB) void k_blocksum_cond(const cplx* __restrict__ amp, uint64_t nc, BitIns fix, uint64_t val,
+                                                           uint64_t zmask, double* __restrict__ sums, uint64_t nblocks) {
+  __shared__ double part[QSV_TPB / 64];
+  for (uint64_t b = blockIdx.x; b < nblocks; b += gridDim.x) {
+    const uint64_t lo = b * QSV_SBLOCK;
+    double s = 0.0;
+#pragma unroll 4
+    for (int k = 0; k < QSV_SBLOCK / QSV_TPB; ++k) {
+      const uint64_t j = lo + (uint64_t)k * QSV_TPB + threadIdx.x;
+      if (j < nc) {
+        const uint64_t i = ins_bits(j, fix) | val;
+        if (!(i & zmask)) { const cplx a = NT ? ld_nt(amp + i) : amp[i]; s = fma(a.x, a.x, fma(a.y, a.y, s)); }
+      }
+    }
+    s = wave_sum(s);
+    if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = s;
+    __syncthreads();
+    if (threadIdx.x == 0) sums[b] = (part[0] + part[1]) + (part[2] + part[3]);
+    __syncthreads();
+  }
+}
+
+// one wave per shot: k_locate over rows of 64 compact indices of compact block blk[s]; out[s] = the REAL local address
+// of the first entry whose running |amp|^2 exceeds resid[s] (k_remap_bits runs unchanged after it)
+__global__ __launch_bounds__(64) void k_locate_cond(const cplx* __restrict__ amp, uint64_t nc, BitIns fix, uint64_t val,
+                                                    uint64_t zmask, const uint64_t* __restrict__ blk,
+                                                    const double* __restrict__ resid,
+                                                    uint64_t* __restrict__ out, uint64_t shots) {
+  const int lane = threadIdx.x;
+  for (uint64_t s = blockIdx.x; s < shots; s += gridDim.x) {
+    const uint64_t lo = blk[s] * QSV_SBLOCK;
+    const double r = resid[s];
+    double run = 0.0;
+    uint64_t found = ~0ull, last_nz = lo;           // compact indices
+    for (int row = 0; row < QSV_SBLOCK / 64 && found == ~0ull; ++row) {
+      const uint64_t j = lo + (uint64_t)row * 64 + lane;
+      double p = 0.0;
+      if (j < nc) {
+        const uint64_t i = ins_bits(j, fix) | val;
+        if (!(i & zmask)) { const cplx a = amp[i]; p = fma(a.x, a.x, a.y * a.y); }
+      }
+      double inc = p;                       // inclusive wave scan
+#pragma unroll
+      for (int o = 1; o < 64; o <<= 1) {
+        const double v = __shfl_up(inc, o, 64);
+        if (lane >= o) inc += v;
+      }
+      const unsigned long long hit = __ballot(p > 0.0 && run + inc > r);
+      const unsigned long long nz = __ballot(p > 0.0);
+      if (hit) found = lo + (uint64_t)row * 64 + (uint64_t)__builtin_ctzll(hit);
+      if (nz) last_nz = lo + (uint64_t)row * 64 + (uint64_t)(63 - __builtin_clzll(nz));
+      run += __shfl(inc, 63, 64);
+    }
+    if (lane == 0) out[s] = ins_bits((found == ~0ull) ? last_nz : found, fix) | val;   // rounding slack -> last nonzero
+  }
+}
+
 // sampled local indices -> the caller's classical-register layout: bit j <- global index bit pos[j]
 // (pos[j] < 0: a classical bit no measurement writes, stays 0); n < 0: the full global index
 struct MeasMap { int n; signed char pos[64]; };

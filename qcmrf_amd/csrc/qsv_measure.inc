@@ -168,35 +168,18 @@ static int sample_chain(qsv_handle* h, Shard& sh, uint64_t shots, uint64_t seed,
   return QSV_OK;
 }
 
-extern "C" int qsv_sample(qsv_handle* h, uint64_t shots, uint64_t seed, const int* meas_qubits, int n_meas,
-                          uint64_t* out_bits) {
-  if (!h || (shots && !out_bits)) return fail(QSV_E_BADARG, "NULL argument");
-  if (meas_qubits && (n_meas < 0 || n_meas > 64)) return fail(QSV_E_BADARG, "n_meas %d out of range", n_meas);
-  if (meas_qubits) for (int i = 0; i < n_meas; ++i) if (meas_qubits[i] >= 0) CHK(check_qubit(h, meas_qubits[i], "measured"));
-  if (shots == 0) return QSV_OK;
-  if (h->opt_sample_chain && h->shards.size() == 1) {
-    // one shard, the tile path, a power-of-two tile count within k_walk_super's reach, the spacings within a quarter of the
-    // arena; everything else walks on the host as before
-    Shard& sh = h->shards[0];
-    const uint64_t nt = sh.tile_nblocks;
-    if (sh.tile_valid && h->opt_cache_sums && nt && !(nt & (nt - 1)) && (nt + QSV_SUPER - 1) / QSV_SUPER <= QSV_WALK_MAX &&
-        256 + shots * sizeof(double) <= sh.arena_bytes / 4 && (!sh.deferred || sh.zmask == sh.recipe.zskip)) {
-      MeasMap cm;
-      cm.n = meas_qubits ? n_meas : -1;
-      for (int j = 0; j < 64; ++j) cm.pos[j] = (meas_qubits && j < n_meas) ? (signed char)meas_qubits[j] : (signed char)-1;
-      return sample_chain(h, sh, shots, seed, cm, out_bits);
-    }
-  }
+// The compact index space of a post-selected draw (qsv_sample_cond): the local fixed bits, their values, and the
+// number of matching amplitudes of a shard (k_blocksum_cond / k_locate_cond)
+struct CondView { BitIns fix; uint64_t val; uint64_t nc; };
+
+// The host walk of qsv_sample and qsv_sample_cond (DESIGN §6): shards, then blocks, then the device inside a block.
+// sums[i] / mass[i] are shard i's block, super or compact-block sums and their total (mass 0: the shard is skipped);
+// total > 0 is the caller's to check.  cond == NULL: the blocks are those of the state (k_locate / k_locate_tile);
+// otherwise compact blocks of the matching sub-cube (k_locate_cond).
+static int sample_walk(qsv_handle* h, uint64_t shots, uint64_t seed, const int* meas_qubits, int n_meas,
+                       const std::vector<SumView>& sums, const std::vector<double>& mass, double total,
+                       const CondView* cond, uint64_t* out_bits) {
   const size_t ns = h->shards.size();
-  std::vector<SumView> sums(ns);
-  std::vector<double> mass(ns);
-  double total = 0;
-  for (size_t i = 0; i < ns; ++i) {
-    CHK(block_sums(h, h->shards[i], sums[i]));
-    mass[i] = pairwise_sum(sums[i].data(), sums[i].size());
-    total += mass[i];
-  }
-  if (!(total > 0)) return fail(QSV_E_BADARG, "state has zero norm on this process; nothing to sample");
   // sorted uniforms in [0,total) WITHOUT a sort: the order statistics of n iid uniforms are the
   // normalised partial sums of n + 1 iid exponentials (a sort of 4096 doubles cost 0.12 ms, a
   // quarter of the whole call at 34 qubits)
@@ -280,7 +263,10 @@ extern "C" int qsv_sample(qsv_handle* h, uint64_t shots, uint64_t seed, const in
         HIPCHK(hipGetLastError());
         h->n_listed += 1;
       }
-      if (bs.super) {                     // tile order of the program's last pass
+      if (cond) {                         // compact blocks of the matching sub-cube; implied zeros are not read
+        hipLaunchKernelGGL(k_locate_cond, dim3((unsigned)std::min<uint64_t>(cnt, 65535)), dim3(64), 0, sh.stream,
+                           sh.amp, cond->nc, cond->fix, cond->val, sh.zmask, sh.d_sblk, sh.d_sres, sh.d_sout, cnt);
+      } else if (bs.super) {              // tile order of the program's last pass
         const dim3 g((unsigned)std::min<uint64_t>(cnt, 65535));
 #define LT(RR) hipLaunchKernelGGL((k_locate_tile<RR>), g, dim3(QSV_TPB), 0, sh.stream, sh.amp, sh.tile_ins, sh.tile_rp, sh.tile_lp, sh.d_sblk, sh.d_sres, sh.d_sout, cnt, sh.tile_xor, sh.zmask)
         switch (sh.tile_R) {
@@ -311,6 +297,129 @@ extern "C" int qsv_sample(qsv_handle* h, uint64_t shots, uint64_t seed, const in
   }
   memcpy(out_bits, idx.data(), shots * sizeof(uint64_t));
   return QSV_OK;
+}
+
+extern "C" int qsv_sample(qsv_handle* h, uint64_t shots, uint64_t seed, const int* meas_qubits, int n_meas,
+                          uint64_t* out_bits) {
+  if (!h || (shots && !out_bits)) return fail(QSV_E_BADARG, "NULL argument");
+  if (meas_qubits && (n_meas < 0 || n_meas > 64)) return fail(QSV_E_BADARG, "n_meas %d out of range", n_meas);
+  if (meas_qubits) for (int i = 0; i < n_meas; ++i) if (meas_qubits[i] >= 0) CHK(check_qubit(h, meas_qubits[i], "measured"));
+  if (shots == 0) return QSV_OK;
+  if (h->opt_sample_chain && h->shards.size() == 1) {
+    // one shard, the tile path, a power-of-two tile count within k_walk_super's reach, the spacings within a quarter of the
+    // arena; everything else walks on the host as before
+    Shard& sh = h->shards[0];
+    const uint64_t nt = sh.tile_nblocks;
+    if (sh.tile_valid && h->opt_cache_sums && nt && !(nt & (nt - 1)) && (nt + QSV_SUPER - 1) / QSV_SUPER <= QSV_WALK_MAX &&
+        256 + shots * sizeof(double) <= sh.arena_bytes / 4 && (!sh.deferred || sh.zmask == sh.recipe.zskip)) {
+      MeasMap cm;
+      cm.n = meas_qubits ? n_meas : -1;
+      for (int j = 0; j < 64; ++j) cm.pos[j] = (meas_qubits && j < n_meas) ? (signed char)meas_qubits[j] : (signed char)-1;
+      return sample_chain(h, sh, shots, seed, cm, out_bits);
+    }
+  }
+  const size_t ns = h->shards.size();
+  std::vector<SumView> sums(ns);
+  std::vector<double> mass(ns);
+  double total = 0;
+  for (size_t i = 0; i < ns; ++i) {
+    CHK(block_sums(h, h->shards[i], sums[i]));
+    mass[i] = pairwise_sum(sums[i].data(), sums[i].size());
+    total += mass[i];
+  }
+  if (!(total > 0)) return fail(QSV_E_BADARG, "state has zero norm on this process; nothing to sample");
+  return sample_walk(h, shots, seed, meas_qubits, n_meas, sums, mass, total, nullptr, out_bits);
+}
+
+// A deferred shard ahead of a post-selected draw (DESIGN §6): the matching sub-cube lies inside the tiles whose block
+// bits agree with the fixed block bits.  Their indices -- ascending, each once: the free tile-index bits counted up, the
+// fixed ones deposited -- go to the generator's listed form, which stores exactly those tiles; the shard stays deferred.
+// Option post_select_list: -1 lists when the list is at most ntiles >> QSV_PROD_MAXG entries (the listed form walks a whole
+// group, up to 2^QSV_PROD_MAXG tiles of arithmetic, per tile stored; a reasoned break-even, not a measured one) and fits
+// a quarter of the arena; 1 whenever a block bit is fixed and the list fits; 0 never.  Otherwise the state is realised.
+static int cond_prepare_deferred(qsv_handle* h, Shard& s, uint64_t lmask, uint64_t lval) {
+  const GenRecipe& rc = s.recipe;
+  BitIns tf;                                         // fixed bits of the tile index, ascending
+  tf.n = 0;
+  uint64_t tval = 0;
+  for (int b = 0; (1ull << b) < rc.ntiles; ++b) {
+    // tile-index bit b is this address bit (tile_base_blk)
+    const uint64_t a = ins_bits(rc.lp.pos[0] < 0 ? (1ull << b) * QSV_TPB : (1ull << b) << 5, rc.ins);
+    if (!(a & lmask)) continue;
+    tf.pos[tf.n++] = b;
+    if (a & lval) tval |= 1ull << b;
+  }
+  const uint64_t nlist = rc.ntiles >> tf.n;
+  const bool fits = nlist * sizeof(uint64_t) <= s.arena_bytes / 4;
+  const int pl = h->opt_post_select_list;
+  const bool list = tf.n > 0 && fits && s.zmask == rc.zskip && pl != 0 && (pl > 0 || nlist <= (rc.ntiles >> QSV_PROD_MAXG));
+  if (h->opt_trace_passes)
+    fprintf(stderr, "[qsv] post_select shard %d: %d block bits fixed, %llu of %llu tiles hold the sub-cube: %s\n", s.index, tf.n,
+            (unsigned long long)nlist, (unsigned long long)rc.ntiles, list ? "listed" : "realised");
+  if (!list) return realize(h, s);
+  std::vector<uint64_t> tiles(nlist);
+  for (uint64_t j = 0; j < nlist; ++j) tiles[j] = ins_bits(j, tf) | tval;
+  void* dl = nullptr;
+  CHK(arena_put(s, tiles.data(), nlist * sizeof(uint64_t), &dl));
+  CHK(launch_recipe(h, s, QSV_GEN_LISTED, reinterpret_cast<const uint64_t*>(dl), nlist));
+  HIPCHK(hipGetLastError());
+  h->n_listed += 1;
+  return QSV_OK;
+}
+
+extern "C" int qsv_sample_cond(qsv_handle* h, uint64_t shots, uint64_t seed, const int* meas_qubits, int n_meas,
+                               uint64_t fix_mask, uint64_t fix_val, uint64_t* out_bits, double* mass_out) {
+  if (!h || (shots && !out_bits)) return fail(QSV_E_BADARG, "NULL argument");
+  if (meas_qubits && (n_meas < 0 || n_meas > 64)) return fail(QSV_E_BADARG, "n_meas %d out of range", n_meas);
+  if (meas_qubits) for (int i = 0; i < n_meas; ++i) if (meas_qubits[i] >= 0) CHK(check_qubit(h, meas_qubits[i], "measured"));
+  if (fix_val & ~fix_mask) return fail(QSV_E_BADARG, "fix_val has bits outside fix_mask");
+  if (h->W < 64 && (fix_mask >> h->W)) return fail(QSV_E_BADARG, "fix_mask has bits at or above qubit %d", h->W);
+  if (!fix_mask) {                                   // nothing fixed: qsv_sample itself, word for word
+    if (mass_out) CHK(qsv_norm(h, mass_out));
+    return qsv_sample(h, shots, seed, meas_qubits, n_meas, out_bits);
+  }
+  const uint64_t n = amps_local(h);
+  const uint64_t lmask = fix_mask & (n - 1), lval = fix_val & (n - 1);
+  CondView cv;
+  cv.fix.n = 0;
+  for (int q = 0; q < h->L; ++q)
+    if ((lmask >> q) & 1ull) {
+      if (cv.fix.n == QSV_MAXB) return fail(QSV_E_UNSUPPORTED, "more than %d fixed bits local to a shard", QSV_MAXB);
+      cv.fix.pos[cv.fix.n++] = q;
+    }
+  cv.val = lval;
+  cv.nc = n >> cv.fix.n;
+  const uint64_t nblk = (cv.nc + QSV_SBLOCK - 1) / QSV_SBLOCK;
+  const size_t ns = h->shards.size();
+  std::vector<std::vector<double>> csum(ns);         // not cached: a second call repeats the 2^-f pass
+  std::vector<SumView> sums(ns);
+  std::vector<double> mass(ns, 0.0);
+  double total = 0;
+  for (size_t i = 0; i < ns; ++i) {
+    Shard& s = h->shards[i];
+    // a fixed shard bit does not enter the kernels: a shard whose index disagrees with it has mass 0 and is skipped
+    if ((((uint64_t)s.index << h->L) & fix_mask) != (fix_val & ~(n - 1))) continue;
+    CHK(shard_set(s));
+    if (s.deferred) CHK(cond_prepare_deferred(h, s, lmask, lval));
+    CHK(launch(h, s, QSV_K_PROB, 16.0 * (double)cv.nc, [&] {
+      // every fixed bit at or above bit 12: a compact block is one contiguous 64 KiB run, streamed as k_blocksum does
+      const bool nt = (cv.fix.n == 0 || cv.fix.pos[0] >= 12) && (h->opt_multi_nt > 0 || (h->opt_multi_nt < 0 && h->L >= 26));
+      const unsigned grid = (unsigned)std::min<uint64_t>(nblk, (uint64_t)s.n_cu * 16);
+      if (nt) hipLaunchKernelGGL(k_blocksum_cond<true>, dim3(grid), dim3(QSV_TPB), 0, s.stream, s.amp, cv.nc, cv.fix, cv.val, s.zmask, s.d_sums, nblk);
+      else hipLaunchKernelGGL(k_blocksum_cond<false>, dim3(grid), dim3(QSV_TPB), 0, s.stream, s.amp, cv.nc, cv.fix, cv.val, s.zmask, s.d_sums, nblk);
+    }));
+    csum[i].resize(nblk);
+    HIPCHK(hipMemcpyAsync(csum[i].data(), s.d_sums, nblk * sizeof(double), hipMemcpyDeviceToHost, s.stream));
+    HIPCHK(hipStreamSynchronize(s.stream));
+    sums[i].p = csum[i].data();
+    sums[i].n = csum[i].size();
+    mass[i] = pairwise_sum(sums[i].data(), sums[i].size());
+    total += mass[i];
+  }
+  if (mass_out) *mass_out = total;
+  if (shots == 0) return QSV_OK;
+  if (!(total > 0)) return fail(QSV_E_BADARG, "post-selected outcome has zero probability");
+  return sample_walk(h, shots, seed, meas_qubits, n_meas, sums, mass, total, &cv, out_bits);
 }
 
 // reduction scratch of a shard: a marginal or an expectation value per branch node of a trajectory run is thousands of

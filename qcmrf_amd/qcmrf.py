@@ -147,6 +147,15 @@ class QCMRF(QuantumCircuit):
         s0, s1 = backend.expectation_diagonal(tab, qs, fixed)
         return s0 / s1, s1
 
+    def post_selection(self):
+        """``{classical bit: 0}`` for every clique ancilla: the branch in which the circuit prepares the Gibbs state
+        (real part extraction succeeds when the ancilla reads 0, QCMRF.py:239).  For ``backend.run(self, shots,
+        post_select=self.post_selection())``: every shot is then a Gibbs sample, and the metadata entry
+        ``post_select_probability`` is the success probability."""
+        if not self._with_measurements:
+            raise ValueError("post_selection() needs the ancilla measurements: build the circuit with_measurements=True")
+        return {self._n + 1 + i: 0 for i in range(self._num_cliques)}
+
     # ---- circuit construction (QCMRF.py:199-243) ---------------------------------------------
     def _clique_unitary(self, index, C, first_param):
         """cU_C: for every clique state y, AND . cp(2 gamma_y) . AND on (variables, scratch, ancilla)."""

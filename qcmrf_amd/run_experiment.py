@@ -2,7 +2,7 @@
 
     python -m qcmrf_amd.run_experiment [--scale 0.5] [--shots 10000] [--reps 10] [--outdir .]
                                        [--depolarizing P1,P2] [--readout P] [--t1 US --t2 US --gate-time NS1,NS2]
-                                       [--method density_matrix]
+                                       [--method density_matrix] [--post-select]
 
 Same steps, same files: seed numpy with 1984, draw theta = -halfnorm.rvs(scale) for the 7
 hard-coded graphs x REPS, dump ``models_<SCALE>.json``, build the 70 ``QCMRF`` circuits, run them
@@ -23,6 +23,10 @@ ancillas' measurements when they occur and recycles their qubits: n + 2 live qub
 ``--method density_matrix`` evolves every circuit exactly as a density matrix (noisy or not): the counts are drawn from the
 exact distributions, and those are written as well, one ``{bitstring: p}`` per circuit, to ``probs_simulation_<SCALE>.json``
 (``probs_simulation_noisy_<SCALE>.json`` for a noisy run).
+
+``--post-select`` draws every shot from the branch in which all clique ancillas read 0 (``QCMRF.post_selection()``): the
+counts, SHOTS Gibbs samples per circuit with full-width keys, go to ``result_simulation_postselected_<SCALE>.json`` and the
+exact success probabilities, one float per circuit, to ``success_simulation_<SCALE>.json``.  Ideal state-vector runs only.
 """
 from __future__ import annotations
 
@@ -53,6 +57,8 @@ def main(argv=None):
     ap.add_argument("--noisy-measure", default=None, choices=["deferred", "in_place", "auto"],
                     help="noisy run: take every measurement at the end (deferred, the default) or mid-circuit ones when they occur, "
                          "their qubits recycled (in_place; auto: in place iff that makes the per-shot state narrower)")
+    ap.add_argument("--post-select", action="store_true",
+                    help="every shot from the branch in which all clique ancillas read 0; also writes the exact success probabilities")
     args = ap.parse_args(argv)
     model = ibm_like_model(args.depolarizing, args.readout, args.t1, args.t2, args.gate_time)
 
@@ -71,6 +77,9 @@ def main(argv=None):
         f.write(json.dumps({"GRAPHS": GRAPHS, "THETAS": THETAS}, indent=4))
 
     CIRCS = [QCMRF(C, THETAS[j][i], with_measurements=True) for j, C in enumerate(GRAPHS) for i in range(args.reps)]
+    if args.post_select and (model is not None or args.method is not None):
+        raise ValueError("--post-select runs the ideal circuits as state vectors: no noise options, no --method")
+    POST = [qc.post_selection() for qc in CIRCS] if args.post_select else None      # (classical bits: lowering keeps them)
     if HAVE_QISKIT:                                   # pragma: no cover - Qiskit absent in this image
         from qiskit import transpile
         CIRCS = transpile(CIRCS, basis_gates=['cx', 'id', 'rz', 'sx', 'x'])
@@ -85,14 +94,20 @@ def main(argv=None):
         extra["method"] = args.method
     if args.noisy_measure is not None:
         extra["noisy_measure"] = args.noisy_measure
+    if POST is not None:
+        extra["post_select"] = POST
     result = simulator.run(CIRCS, shots=args.shots, seed_simulator=args.seed_simulator, **extra).result()
     counts = result.get_counts()
     dt = time.perf_counter() - t0
     print("%d circuits x %d shots: %.3f s in run().result().get_counts() (%.2f ms per circuit)"
           % (len(CIRCS), args.shots, dt, dt / len(CIRCS) * 1e3), file=sys.stderr)
-    name = "result_simulation_" if model is None else "result_simulation_noisy_"
+    name = "result_simulation_postselected_" if POST is not None else "result_simulation_" if model is None else "result_simulation_noisy_"
     with open(os.path.join(args.outdir, name + str(args.scale) + ".json"), "w") as f:
         f.write(json.dumps(counts, indent=4))
+    if POST is not None:
+        success = [float(r["metadata"]["post_select_probability"]) for r in result.results]
+        with open(os.path.join(args.outdir, "success_simulation_" + str(args.scale) + ".json"), "w") as f:
+            f.write(json.dumps(success, indent=4))
     if args.method == "density_matrix":
         probs = result.get_probabilities()
         name = "probs_simulation_" if model is None else "probs_simulation_noisy_"
