@@ -351,6 +351,37 @@ int qsv_noisy_sample_hbm(qsv_handle* h, const qsv_op* ops, int n_ops, const doub
                          const double* readout /* n_meas x 2: P(flip | 0), P(flip | 1); NULL = none */,
                          uint64_t* out_bits);
 
+/* Noisy shots kept only when fixed bits of their word read given values: rejection sampling, reproducible because a shot is a
+ * pure function of (program, seed, shot index).  The arguments up to `readout` are those of qsv_noisy_sample, with its checks;
+ * hbm = 0 keeps the states in LDS (width limit QSV_NOISY_MAX_QUBITS), hbm = 1 in slots of device memory
+ * (QSV_NOISY_HBM_MAX_QUBITS).  Attempt t = first_shot, first_shot + 1, ... is shot t of qsv_noisy_sample (hbm = 1:
+ * qsv_noisy_sample_hbm) with the same arguments: the same draws and, where the shot is run to its end, the same word.  Attempt
+ * t is accepted iff (word & fix_mask) == fix_val, over the bits of the recorded word.  The call returns the first `shots`
+ * accepted attempts in ascending t: their words in out_bits[0, *accepted), their indices t in out_shot (NULL: not wanted).
+ * *accepted = how many were found; *attempts = the number of indices examined: the last accepted index - first_shot + 1
+ * when *accepted == shots, max_attempts otherwise.  Running out of attempts is QSV_OK with *accepted < shots: the caller
+ * decides what that means.
+ * A trajectory is abandoned as soon as it can no longer be accepted: behind the last MEASURE record that writes a fixed bit
+ * (a bit may be written twice; only its last write may end a shot), if the bit it left in the word -- after the readout flip:
+ * acceptance is on what was read -- differs from fix_val, the remaining records and the final draw of that shot are skipped.
+ * Attempts that fail only on bits the final draw writes run to their end and are filtered.  The word of an abandoned shot is
+ * never returned.
+ * `round` = attempts per launch, 0 = chosen by the library (about `shots` at first, later rounds from the acceptance seen so
+ * far, at most 2^20).  Nothing the call returns depends on `round`, on the noisy_grid option or on whether a rejected
+ * trajectory was abandoned.  With fix_mask = 0 and first_shot = 0, out_bits is the output of qsv_noisy_sample(_hbm) word for
+ * word and *attempts = shots.  The op stream, its tables and the measurement map are encoded and copied to the device once
+ * per call, the slots of hbm = 1 allocated once per call (as qsv_noisy_sample_hbm sizes them for max(64, 4 shots) shots) and
+ * freed before it returns; the loop over the rounds is inside the call.
+ * QSV_E_BADARG, with a message that names the bit: a bit of fix_val outside fix_mask; a bit of fix_mask at or above n_meas
+ * (meas_qubits == NULL: at or above the width); a bit of fix_mask that neither the final draw (meas_qubits[bit] >= 0) nor a
+ * MEASURE record writes.  Also QSV_E_BADARG: max_attempts = 0 with shots > 0; accepted or attempts NULL. */
+int qsv_noisy_sample_accept(qsv_handle* h, const qsv_op* ops, int n_ops, const double* data, uint64_t n_data,
+                            uint64_t shots, uint64_t seed, const int* meas_qubits, int n_meas,
+                            const double* readout /* n_meas x 2: P(flip | 0), P(flip | 1); NULL = none */,
+                            uint64_t fix_mask, uint64_t fix_val, uint64_t first_shot, uint64_t max_attempts,
+                            uint64_t round, int hbm, uint64_t* out_bits /* shots */, uint64_t* out_shot /* shots, or NULL */,
+                            uint64_t* accepted, uint64_t* attempts);
+
 /* ---- density matrix: exact noisy distributions ------------------------------------------- */
 
 #define QSV_DENSITY_MAX_QUBITS 17
@@ -460,7 +491,8 @@ int qsv_timer_end(qsv_handle* h, double* ms);
  *   kernels     unroll [4], lowt_shuffle [1], pair_variant [0], kq_mfma [1], blocks_per_cu [65536]
  *               swizzle [1]        one-gate kernels: lane bit 5 of a wave access carries address bit 11 (two 512-byte runs 32 KiB apart);
  *                                  1 from 2^26 amplitudes per shard, 2 from 2^14, 0 never        lane_map_min_l [26]  same for k_multi tiles other than bits 6..10
- *   noisy       noisy_grid [0]     workgroups of qsv_noisy_sample and qsv_noisy_sample_hbm: 0 = as many as the chip holds at once, else at most this many
+ *   noisy       noisy_grid [0]     workgroups of qsv_noisy_sample, qsv_noisy_sample_hbm and each round of qsv_noisy_sample_accept: 0 = as many as the
+ *                                  chip holds at once, else at most this many
  *   other       zero_tracking [0]  skip amplitudes known to be zero (opt-in)       exchange_chunk_log2 [24]  amplitudes per exchange chunk
  *               implied_zeros [1]  the generator as a program's last pass (and qsv_exec's end) leaves the provably-zero part
  *                                  of a shard unwritten; every reader honours that or writes the zeros first (0: write them always) */

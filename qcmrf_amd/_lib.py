@@ -92,6 +92,8 @@ SIGNATURES = {
     "qsv_exec": (_i, [_vp, _vp, _i, _dp, _u64]),
     "qsv_noisy_sample": (_i, [_vp, _vp, _i, _dp, _u64, _u64, _u64, _ip, _i, _dp, _u64p]),
     "qsv_noisy_sample_hbm": (_i, [_vp, _vp, _i, _dp, _u64, _u64, _u64, _ip, _i, _dp, _u64p]),
+    "qsv_noisy_sample_accept": (_i, [_vp, _vp, _i, _dp, _u64, _u64, _u64, _ip, _i, _dp, _u64, _u64, _u64, _u64, _u64, _i, _u64p, _u64p,
+                                     _u64p, _u64p]),
     "qsv_density_exec": (_i, [_vp, _vp, _i, _dp, _u64]),
     "qsv_density_pauli_table": (_i, [_i, _dp, _dp]),
     "qsv_density_diagonal": (_i, [_vp, _ip, _i, _dp, _dp]),
@@ -382,10 +384,28 @@ class Engine:
         NOISY_HBM_MAX_QUBITS qubits, the same arguments, draws and words"""
         return self._noisy(self._lib.qsv_noisy_sample_hbm, ops, data, shots, seed, meas_qubits, readout)
 
-    def _noisy(self, fn, ops, data, shots, seed, meas_qubits, readout):
+    def noisy_sample_accept(self, ops, data, shots, seed, meas_qubits=None, readout=None, fix_mask=0, fix_val=0, first_shot=0,
+                            max_attempts=None, round=0, hbm=False):
+        """the first ``shots`` attempts t = first_shot, first_shot + 1, ... of ``noisy_sample`` (``hbm``: ``noisy_sample_hbm``)
+        whose word w has (w & fix_mask) == fix_val, at most ``max_attempts`` of them examined (None: 2^20 or 1000 per shot,
+        whichever is more) (qsv_noisy_sample_accept): (words, shot indices, attempts examined); fewer than ``shots`` entries
+        when the attempts ran out.  ``round``: attempts per launch (0: chosen by the library); no result depends on it"""
+        shots = int(shots)
+        if max_attempts is None:
+            max_attempts = max(2 ** 20, 1000 * shots)
+        words, index = np.zeros(shots, dtype=np.uint64), np.zeros(shots, dtype=np.uint64)
+        accepted, attempts = C.c_uint64(), C.c_uint64()
+        self._noisy(self._lib.qsv_noisy_sample_accept, ops, data, shots, seed, meas_qubits, readout, words,
+                    (int(fix_mask), int(fix_val), int(first_shot), int(max_attempts), int(round), int(bool(hbm))),
+                    (index.ctypes.data_as(_u64p), C.byref(accepted), C.byref(attempts)))
+        return words[:accepted.value], index[:accepted.value], int(attempts.value)
+
+    def _noisy(self, fn, ops, data, shots, seed, meas_qubits, readout, out=None, before=(), after=()):
+        """one call of a noisy entry point; ``before`` and ``after``: what it takes around ``out``"""
         ops = np.ascontiguousarray(ops, dtype=OP_DTYPE)
         da, dp = _da(data if len(data) else np.zeros(1))
-        out = np.zeros(int(shots), dtype=np.uint64)
+        if out is None:
+            out = np.zeros(int(shots), dtype=np.uint64)
         if meas_qubits is None:
             qa, qp, nm = None, None, 0
         else:
@@ -394,7 +414,8 @@ class Engine:
         ra, rp = (None, None) if readout is None else _da(readout)
         if ra is not None and (meas_qubits is None or ra.size != 2 * nm):
             raise ValueError("readout needs 2 probabilities per measured bit (%d), got %d" % (nm, ra.size))
-        _chk(fn(self._h, ops.ctypes.data_as(_vp), len(ops), dp, len(data), int(shots), int(seed), qp, nm, rp, out.ctypes.data_as(_u64p)))
+        _chk(fn(self._h, ops.ctypes.data_as(_vp), len(ops), dp, len(data), int(shots), int(seed), qp, nm, rp, *before,
+                out.ctypes.data_as(_u64p), *after))
         return out
 
     # -- density matrix: this engine's 2W qubits hold rho of W qubits, rho[i, j] at i | (j << W)

@@ -164,6 +164,21 @@ class QsvBackend:
                 measurements stay one joint final draw; same limits: <= 64 classical bits, no reset, no gate after a
                 measure, no classical conditions) | 'auto' (in place iff that makes the state narrower).  A shot's Pauli,
                 Kraus and readout draws are the same in both; 'density_matrix' stays deferred
+    accept      (noisy runs and method 'density_matrix') ``{classical bit: 0 | 1}``, or a list with one dict per circuit
+                (``QCMRF.post_selection()`` is a valid value): only shots whose bits read these values are kept, and ``shots`` is
+                the number of KEPT shots.  A noisy run takes attempts 0, 1, 2, ... -- attempt t is shot t of the same run without
+                ``accept`` -- and keeps the first ``shots`` that match (``qsv_noisy_sample_accept``); an attempt is abandoned on
+                the device as soon as a measurement taken in place contradicts, so ``noisy_measure='auto'`` or 'in_place' is
+                what saves work (deferred: every attempt runs to its end and is filtered).  Metadata: ``accept``,
+                ``accept_attempts`` and ``accept_probability`` = (shots - 1) / (attempts - 1), the unbiased estimate of the
+                success rate when sampling stops at the shots-th success (1 / attempts for one shot) -- functions of (circuit,
+                model, seed, shots) alone.  'density_matrix': ``get_probabilities()`` is the exact distribution conditioned on
+                the fixed bits (readout confusion included), ``accept_probability`` the exact mass of the condition, the counts
+                ``numpy.random.default_rng(seed).multinomial(shots, p)``.  Not ``post_select``, which conditions the exact state
+                vector of an ideal run and refuses noise; giving both is an error
+    accept_max_attempts  attempts examined at most (default max(2^20, 1000 shots)); a RuntimeError names the rate seen if they
+                run out
+    accept_round  attempts per launch (default 0: chosen by the library); no result depends on it
     """
 
     def __init__(self, name="qasm_simulator", **options):
@@ -276,6 +291,7 @@ class QsvBackend:
         nmeasure = opts.get("noisy_measure", "deferred")
         if nmeasure not in _NOISY_MEASURES:
             raise ValueError("unknown noisy_measure %r; a noisy shot takes its measurements %s" % (nmeasure, ", ".join(_NOISY_MEASURES)))
+        accept = self._accept_of(opts, len(circs), method)      # (first: it is the one that refuses the two together)
         post = self._post_select_of(opts, len(circs), method)
         if method == "density_matrix":
             if nmeasure == "in_place":
@@ -288,7 +304,8 @@ class QsvBackend:
                     prepared = nxt.result()
                     if i + 1 < len(circs):
                         nxt = pool.submit(self._prepare_density, circs[i + 1], model)
-                    exps.append(self._run_density(circs[i], int(shots), int(seed_simulator) + i, opts, prepared))
+                    exps.append(self._run_density(circs[i], int(shots), int(seed_simulator) + i, opts, prepared,
+                                                  accept=accept and accept[i]))
             return Job(Result(exps, self._name))
         model = self._noise_of(opts)
         if model is not None:
@@ -300,7 +317,8 @@ class QsvBackend:
                     prepared = nxt.result()
                     if i + 1 < len(circs):
                         nxt = pool.submit(self._prepare_noisy, circs[i + 1], model, state, nmeasure)
-                    exps.append(self._run_noisy(circs[i], int(shots), int(seed_simulator) + i, opts, prepared))
+                    exps.append(self._run_noisy(circs[i], int(shots), int(seed_simulator) + i, opts, prepared,
+                                                accept=accept and accept[i]))
             return Job(Result(exps, self._name))
         if len(circs) > 1 and opts.get("method", "statevector") == "statevector":
             # a batch (run_experiment.py:52-56 hands over 70 circuits): compile circuit i+1 on a
@@ -339,6 +357,43 @@ class QsvBackend:
         if len(post) != n_circuits or not all(isinstance(d, dict) for d in post):
             raise ValueError("post_select is one {classical bit: 0 | 1} dict, or a list of %d of them (one per circuit)" % n_circuits)
         return post
+
+    def _accept_of(self, opts, n_circuits, method):
+        """the ``accept`` option as one ``{classical bit: 0 | 1}`` per circuit, or None; refuses the runs that have no shots
+        to reject"""
+        accept = opts.get("accept")
+        if accept is None:
+            return None
+        if opts.get("post_select") is not None:
+            raise ValueError("accept and post_select were both given: post_select conditions the exact state vector of an ideal "
+                             "run, accept keeps the shots of a noisy run whose bits match")
+        if method == "trajectory":
+            raise ValueError("accept belongs to noisy runs and method='density_matrix', not method='trajectory'")
+        comm = opts["comm"] or SingleProcess()
+        if comm.world > 1:
+            raise ValueError("accept takes one process (a process group of %d ranks was given; limit 1)" % comm.world)
+        if method == "statevector" and self._noise_of(opts) is None:
+            raise ValueError("accept keeps the shots of a noisy run whose bits match; an ideal state-vector run has an exact "
+                             "conditioned state: use post_select")
+        if isinstance(accept, dict):
+            accept = [accept] * n_circuits
+        accept = list(accept)
+        if len(accept) != n_circuits or not all(isinstance(d, dict) for d in accept):
+            raise ValueError("accept is one {classical bit: 0 | 1} dict, or a list of %d of them (one per circuit)" % n_circuits)
+        return accept
+
+    @staticmethod
+    def _accept_mask(accept, ing):
+        """(fix_mask, fix_val) over the classical bits (bit c of a recorded word is classical bit c)"""
+        fm = fv = 0
+        for c, v in accept.items():
+            if c not in ing.measure:
+                raise ValueError("accept names classical bit %r, which no measurement writes" % (c,))
+            if v not in (0, 1):
+                raise ValueError("accept fixes classical bit %r to %r; a bit reads 0 or 1" % (c, v))
+            fm |= 1 << int(c)
+            fv |= int(v) << int(c)
+        return fm, fv
 
     @staticmethod
     def _post_select_mask(post, ing, pl):
@@ -453,18 +508,32 @@ class QsvBackend:
             readout[c] = ing.readout.get(c, (0.0, 0.0))
         return ing, rec, data, clist, meas, readout, time.perf_counter() - t0, state, ("in_place", width, n_measure)
 
-    def _run_noisy(self, circuit, shots, seed, opts, prepared):
-        """one qsv_noisy_sample (or qsv_noisy_sample_hbm) call: shots trajectories, sampled and read out on the device"""
+    def _run_noisy(self, circuit, shots, seed, opts, prepared, accept=None):
+        """one qsv_noisy_sample (or qsv_noisy_sample_hbm) call: shots trajectories, sampled and read out on the device;
+        ``accept``: one qsv_noisy_sample_accept call, shots accepted trajectories"""
         ing, rec, data, clist, meas, readout, t_compile, state, (nmeasure, width, n_measure) = prepared
         t1 = time.perf_counter()
         t0 = t1 - t_compile
         counts = {}
         t2 = t1
+        fix = None if accept is None else self._accept_mask(accept, ing)
+        accept_meta = {} if fix is None else {"accept": dict(accept), "accept_attempts": 0, "accept_probability": None}
         if clist and shots > 0:
             eng = self._get_engine(width, dict(opts, comm=None, devices=tuple(opts["devices"])[:1]))
             self._apply_engine_options(eng, opts)
-            sample = eng.noisy_sample_hbm if state == "hbm" else eng.noisy_sample
-            bits = sample(rec, data, shots, seed, meas, readout if ing.readout else None)
+            if fix is not None:
+                limit = opts.get("accept_max_attempts")
+                limit = max(2 ** 20, 1000 * shots) if limit is None else int(limit)
+                bits, _, attempts = eng.noisy_sample_accept(rec, data, shots, seed, meas, readout if ing.readout else None, fix[0], fix[1],
+                                                            0, limit, int(opts.get("accept_round") or 0), state == "hbm")
+                if len(bits) < shots:
+                    raise RuntimeError("accept %r: %d attempts made, %d of %d shots accepted (rate seen %.3g); accept_max_attempts "
+                                       "sets the limit" % (accept, attempts, len(bits), shots, len(bits) / max(attempts, 1)))
+                accept_meta.update(accept_attempts=attempts,
+                                   accept_probability=(shots - 1) / (attempts - 1) if shots > 1 else 1.0 / attempts)
+            else:
+                sample = eng.noisy_sample_hbm if state == "hbm" else eng.noisy_sample
+                bits = sample(rec, data, shots, seed, meas, readout if ing.readout else None)
             t2 = time.perf_counter()
             uv, uc = np.unique(bits, return_counts=True)
             counts = _format_keys(uv, uc, ing.num_clbits, ing.creg_sizes)
@@ -473,6 +542,7 @@ class QsvBackend:
                 "n_circuit_qubits": ing.num_qubits, "n_measure_ops": n_measure, "n_source_ops": ing.n_source_ops, "n_device_ops": len(rec),
                 "n_pauli_ops": ing.n_pauli, "n_kraus_ops": ing.n_kraus, "readout_errors": len(ing.readout), "time_compile": t1 - t0,
                 "time_evolve": t2 - t1, "time_sample": t3 - t2, "time_taken": t3 - t0, "seed_simulator": seed}
+        meta.update(accept_meta)
         self.last_engine = None          # no resident state: every shot had its own
         self.last_plan = None
         self._last_comm = None
@@ -525,8 +595,28 @@ class QsvBackend:
             dist = new
         return dist
 
-    def _run_density(self, circuit, shots, seed, opts, prepared):
-        """qsv_density_exec, then the exact distribution (qsv_density_diagonal + readout confusion) and the shots (qsv_density_sample)"""
+    @staticmethod
+    def _condition(dist, clist, accept):
+        """(dist conditioned on ``accept`` and renormalised, the mass of the condition); index bit j of dist is classical bit
+        clist[j]"""
+        fm = fv = 0
+        for c, v in accept.items():
+            if c not in clist:
+                raise ValueError("accept names classical bit %r, which no measurement writes" % (c,))
+            if v not in (0, 1):
+                raise ValueError("accept fixes classical bit %r to %r; a bit reads 0 or 1" % (c, v))
+            fm |= 1 << clist.index(c)
+            fv |= int(v) << clist.index(c)
+        p = np.clip(dist, 0.0, None)
+        kept = np.where((np.arange(p.size) & fm) == fv, p, 0.0)
+        mass = kept.sum()
+        if not mass > 0:
+            raise ValueError("post-selected outcome %r has zero probability" % (accept,))
+        return kept / mass, float(mass / p.sum())
+
+    def _run_density(self, circuit, shots, seed, opts, prepared, accept=None):
+        """qsv_density_exec, then the exact distribution (qsv_density_diagonal + readout confusion) and the shots (qsv_density_sample);
+        ``accept``: the distribution conditioned on the host, the shots one multinomial draw from it"""
         ing, rec, data, clist, meas, readout, t_compile = prepared
         t1 = time.perf_counter()
         t0 = t1 - t_compile
@@ -546,13 +636,20 @@ class QsvBackend:
         t2 = time.perf_counter()
         marg, trace = eng.density_diagonal([ing.measure[c] for c in clist])
         dist = self._confuse(marg, [tuple(readout[c]) for c in clist])
+        accept_meta = {}
+        if accept is not None:
+            dist, mass = self._condition(dist, clist, accept)
+            accept_meta = {"accept": dict(accept), "accept_probability": mass}
         keep = np.flatnonzero(dist > 0)
         words = np.zeros(keep.size, dtype=np.uint64)            # bit j of the index is classical bit clist[j]
         for j, c in enumerate(clist):
             words |= ((keep.astype(np.uint64) >> np.uint64(j)) & np.uint64(1)) << np.uint64(c)
         probs = dict(zip(_format_keys(words, np.arange(keep.size), ing.num_clbits, ing.creg_sizes).keys(), dist[keep].tolist())) if clist else {}
         counts = {}
-        if clist and shots > 0:
+        if clist and shots > 0 and accept is not None:
+            drawn = np.random.default_rng(seed).multinomial(shots, dist[keep])
+            counts = _format_keys(words[drawn > 0], drawn[drawn > 0], ing.num_clbits, ing.creg_sizes)
+        elif clist and shots > 0:
             bits = eng.density_sample(shots, seed, meas, readout if ing.readout else None)
             uv, uc = np.unique(bits, return_counts=True)
             counts = _format_keys(uv, uc, ing.num_clbits, ing.creg_sizes)
@@ -561,6 +658,7 @@ class QsvBackend:
                 "n_pauli_ops": ing.n_pauli, "n_kraus_ops": ing.n_kraus, "readout_errors": len(ing.readout), "trace": float(trace),
                 "state_bytes": state_bytes, "time_compile": t1 - t0, "time_evolve": t2 - t1, "time_sample": t3 - t2,
                 "time_taken": t3 - t0, "seed_simulator": seed}
+        meta.update(accept_meta)
         self.last_engine = None          # the resident vector is rho, not a state: statevector() has nothing to show
         self.last_plan = None
         self._last_comm = None

@@ -204,9 +204,12 @@ static int nz_check_meas(qsv_handle* h, const int* meas_qubits, int n_meas, cons
 }
 
 // validates every record and appends its compact form to cops, its tables to pool; a MEASURE record is checked against the
-// measurement map it writes beside (meas_qubits, n_meas)
+// measurement map it writes beside (meas_qubits, n_meas).  fix_mask (qsv_noisy_sample_accept; 0 elsewhere, and the stream is
+// then what it was without the parameter): the last MEASURE record to write a bit of it is marked NZ_DECISIVE -- a bit may be
+// written twice, and only its last write may end a shot.  *written (may be NULL): the bits MEASURE records write.
 static int nz_encode(qsv_handle* h, const qsv_op* ops, int n_ops, const double* data, uint64_t n_data, const int* meas_qubits,
-                     int n_meas, std::vector<NzOp>& cops, NzPool& pool, bool* has_kraus, bool* has_measure) {
+                     int n_meas, std::vector<NzOp>& cops, NzPool& pool, bool* has_kraus, bool* has_measure, uint64_t fix_mask = 0,
+                     uint64_t* written = nullptr) {
   cops.reserve(n_ops);
   *has_kraus = false;
   *has_measure = false;
@@ -327,6 +330,14 @@ static int nz_encode(qsv_handle* h, const qsv_op* ops, int n_ops, const double* 
     }
     cops.push_back(c);
   }
+  uint64_t later = 0;                                      // the bits a MEASURE record behind the current one writes
+  for (size_t k = cops.size(); k-- > 0;) {
+    if (cops[k].kind != NZ_MEASURE) continue;
+    const uint64_t bit = 1ull << (cops[k].cmask & 63u);
+    if ((fix_mask & bit) && !(later & bit)) cops[k].cmask |= NZ_DECISIVE;
+    later |= bit;
+  }
+  if (written) *written = later;
   return QSV_OK;
 }
 
@@ -365,9 +376,9 @@ static int nz_stage(Shard& s, const std::vector<NzOp>& cops, const std::vector<d
 // records -> compact records, pool and measurement map of one call
 static int nz_prepare(qsv_handle* h, const qsv_op* ops, int n_ops, const double* data, uint64_t n_data, const int* meas_qubits,
                       int n_meas, const double* readout, std::vector<NzOp>& cops, NzPool& pool, bool* has_kraus, bool* has_measure,
-                      NzMeas* meas) {
+                      NzMeas* meas, uint64_t fix_mask = 0, uint64_t* written = nullptr) {
   CHK(nz_check_meas(h, meas_qubits, n_meas, readout));
-  CHK(nz_encode(h, ops, n_ops, data, n_data, meas_qubits, n_meas, cops, pool, has_kraus, has_measure));
+  CHK(nz_encode(h, ops, n_ops, data, n_data, meas_qubits, n_meas, cops, pool, has_kraus, has_measure, fix_mask, written));
   meas->n = meas_qubits ? n_meas : -1;
   meas->readout = -1;
   meas->pos = nullptr;
@@ -441,31 +452,38 @@ struct NzSlots {
   char* p = nullptr;
   ~NzSlots() { if (p) hipFree(p); }
 };
+// grid = min(shots, noisy_grid if set, workgroups resident at once, slots that fit into 90 % of the free memory), and the
+// slots for it
+static int nz_hbm_slots(qsv_handle* h, Shard& s, uint64_t shots, NzSlots& slots, uint64_t* workgroups) {
+  const uint64_t slot = (uint64_t)16 << h->W;
+  uint64_t grid = 0;
+  HIPCHK(qsv_noise_hbm_resident(s.n_cu, &grid));
+  if (h->opt_noisy_grid > 0 && (uint64_t)h->opt_noisy_grid < grid) grid = (uint64_t)h->opt_noisy_grid;
+  if (shots < grid) grid = shots;
+  size_t free_b = 0, total_b = 0;
+  HIPCHK(hipMemGetInfo(&free_b, &total_b));
+  const uint64_t fit = (uint64_t)((double)free_b * 0.9) / slot;
+  if (fit < 1)
+    return fail(QSV_E_NOMEM, "noisy shots in device memory: one %d-qubit trajectory needs %llu bytes, %llu bytes are free (qsv_device_memory)",
+                h->W, (unsigned long long)slot, (unsigned long long)free_b);
+  if (fit < grid) grid = fit;
+  if (hipMalloc(&slots.p, grid * slot) != hipSuccess) {
+    slots.p = nullptr;
+    (void)hipGetLastError();
+    return fail(QSV_E_NOMEM, "noisy shots in device memory: %llu slots of %llu bytes need %llu bytes, %llu bytes are free (qsv_device_memory)",
+                (unsigned long long)grid, (unsigned long long)slot, (unsigned long long)(grid * slot), (unsigned long long)free_b);
+  }
+  *workgroups = grid;
+  return QSV_OK;
+}
 extern "C" int qsv_noisy_sample_hbm(qsv_handle* h, const qsv_op* ops, int n_ops, const double* data, uint64_t n_data,
                                     uint64_t shots, uint64_t seed, const int* meas_qubits, int n_meas,
                                     const double* readout, uint64_t* out_bits) {
   NzSlots slots;
   return nz_run(h, ops, n_ops, data, n_data, shots, seed, meas_qubits, n_meas, readout, out_bits, QSV_NOISY_HBM_MAX_QUBITS,
                 "a slot of device memory", [&](Shard& s, const NzCall& c, bool) -> int {
-    // grid = min(shots, noisy_grid if set, workgroups resident at once, slots that fit into 90 % of the free memory)
-    const uint64_t slot = (uint64_t)16 << h->W;
     uint64_t grid = 0;
-    HIPCHK(qsv_noise_hbm_resident(s.n_cu, &grid));
-    if (h->opt_noisy_grid > 0 && (uint64_t)h->opt_noisy_grid < grid) grid = (uint64_t)h->opt_noisy_grid;
-    if (shots < grid) grid = shots;
-    size_t free_b = 0, total_b = 0;
-    HIPCHK(hipMemGetInfo(&free_b, &total_b));
-    const uint64_t fit = (uint64_t)((double)free_b * 0.9) / slot;
-    if (fit < 1)
-      return fail(QSV_E_NOMEM, "noisy shots in device memory: one %d-qubit trajectory needs %llu bytes, %llu bytes are free (qsv_device_memory)",
-                  h->W, (unsigned long long)slot, (unsigned long long)free_b);
-    if (fit < grid) grid = fit;
-    if (hipMalloc(&slots.p, grid * slot) != hipSuccess) {
-      slots.p = nullptr;
-      (void)hipGetLastError();
-      return fail(QSV_E_NOMEM, "noisy shots in device memory: %llu slots of %llu bytes need %llu bytes, %llu bytes are free (qsv_device_memory)",
-                  (unsigned long long)grid, (unsigned long long)slot, (unsigned long long)(grid * slot), (unsigned long long)free_b);
-    }
+    CHK(nz_hbm_slots(h, s, shots, slots, &grid));
     NzHbmLaunch l;
     static_cast<NzCall&>(l) = c;
     l.grid = (unsigned)grid;
@@ -473,6 +491,135 @@ extern "C" int qsv_noisy_sample_hbm(qsv_handle* h, const qsv_op* ops, int n_ops,
     HIPCHK(qsv_noise_hbm_launch(l));
     return QSV_OK;
   });
+}
+
+// Noisy shots kept only when fixed bits read given values (the contract is in include/qsv.h).  Attempts are launched in rounds
+// on the accept-aware kernels; the host keeps the words that satisfy the predicate, in ascending attempt index, until it has
+// `shots` of them.  What is returned is a function of the attempts' words alone: the rounds only decide how much work past
+// the last accepted attempt is thrown away.
+#define QSV_NZ_ACCEPT_ROUND_MIN 64ull            // attempts of a round chosen here at least: below this a launch is all overhead
+#define QSV_NZ_ACCEPT_ROUND_MAX (1ull << 20)     // and at most: 8 MiB of words on the device and on the host
+
+// the checks of the fixed bits; `written` = the bits MEASURE records write
+static int nz_check_accept(qsv_handle* h, const int* meas_qubits, int n_meas, uint64_t fix_mask, uint64_t fix_val, uint64_t written) {
+  for (int b = 0; b < 64; ++b) {
+    const uint64_t bit = 1ull << b;
+    if ((fix_val & bit) && !(fix_mask & bit)) return fail(QSV_E_BADARG, "fix_val sets bit %d, which fix_mask does not fix", b);
+    if (!(fix_mask & bit)) continue;
+    if (!meas_qubits) {
+      if (b >= h->W) return fail(QSV_E_BADARG, "fix_mask fixes bit %d, beyond the %d qubits of the full-index word", b, h->W);
+      continue;
+    }
+    if (b >= n_meas) return fail(QSV_E_BADARG, "fix_mask fixes bit %d, outside the %d bits of the call", b, n_meas);
+    if (meas_qubits[b] < 0 && !(written & bit))
+      return fail(QSV_E_BADARG, "fix_mask fixes bit %d, which neither the final draw (meas_qubits[%d] = -1) nor a QSV_OP_MEASURE record writes", b, b);
+  }
+  return QSV_OK;
+}
+
+// attempts of the next round when the library chooses: about `shots` at first, then what the acceptance seen so far asks for
+// the shots still missing, a quarter more; four times what was examined while nothing has been accepted yet
+static uint64_t nz_accept_round(uint64_t shots, uint64_t accepted, uint64_t examined, uint64_t cap) {
+  double want;
+  if (examined == 0) want = (double)shots;
+  else if (accepted == 0) want = 4.0 * (double)examined;
+  else want = 1.25 * (double)(shots - accepted) * (double)examined / (double)accepted;
+  uint64_t n = want >= (double)cap ? cap : (uint64_t)want;
+  if (n < QSV_NZ_ACCEPT_ROUND_MIN) n = QSV_NZ_ACCEPT_ROUND_MIN;
+  return n < cap ? n : cap;
+}
+
+extern "C" int qsv_noisy_sample_accept(qsv_handle* h, const qsv_op* ops, int n_ops, const double* data, uint64_t n_data,
+                                       uint64_t shots, uint64_t seed, const int* meas_qubits, int n_meas, const double* readout,
+                                       uint64_t fix_mask, uint64_t fix_val, uint64_t first_shot, uint64_t max_attempts,
+                                       uint64_t round, int hbm, uint64_t* out_bits, uint64_t* out_shot, uint64_t* accepted,
+                                       uint64_t* attempts) {
+  CHK(nz_check_args(h, ops, n_ops, shots, out_bits));
+  if (!accepted || !attempts) return fail(QSV_E_BADARG, "NULL argument");
+  *accepted = *attempts = 0;
+  const int max_w = hbm ? QSV_NOISY_HBM_MAX_QUBITS : QSV_NOISY_MAX_QUBITS;
+  if (h->W > max_w)
+    return fail(QSV_E_BADARG, "noisy shots keep one %d-qubit state per trajectory in %s: at most %d qubits", h->W,
+                hbm ? "a slot of device memory" : "LDS", max_w);
+  std::vector<NzOp> cops;
+  NzPool pool;
+  bool has_kraus = false, has_measure = false;
+  uint64_t written = 0;
+  NzCall c;
+  CHK(nz_prepare(h, ops, n_ops, data, n_data, meas_qubits, n_meas, readout, cops, pool, &has_kraus, &has_measure, &c.meas, fix_mask,
+                 &written));
+  CHK(nz_check_accept(h, meas_qubits, n_meas, fix_mask, fix_val, written));
+  if (shots == 0) return QSV_OK;
+  if (max_attempts == 0) return fail(QSV_E_BADARG, "max_attempts = 0 with %llu shots to accept", (unsigned long long)shots);
+  if (first_shot + max_attempts < first_shot) return fail(QSV_E_BADARG, "first_shot + max_attempts exceeds 64 bits");
+  // the words buffer holds the largest round
+  uint64_t cap = round ? round : QSV_NZ_ACCEPT_ROUND_MAX;
+  if (cap > max_attempts) cap = max_attempts;
+  Shard& s = h->shards[0];
+  CHK(shard_set(s));
+  NzStaged st;
+  CHK(nz_stage(s, cops, pool.pool, meas_qubits, n_meas, cap, &st));       // ops, pool and map: once per call
+  c.stream = s.stream;
+  c.W = h->W;
+  c.d_ops = st.ops;
+  c.n_ops = (int)cops.size();
+  c.d_pool = st.pool;
+  c.seed = seed;
+  c.meas.pos = st.pos;
+  c.d_out = st.out;
+  c.measure = has_measure;
+  // and the slots: as a plain call of max(64, 4 shots) shots would size them, so that a call for a few shots does not take the
+  // memory of a full grid; a round of more attempts runs them in these
+  NzSlots slots;
+  uint64_t slot_grid = 0;
+  const uint64_t slot_shots = shots < 16 ? 64 : shots < (QSV_NZ_ACCEPT_ROUND_MAX >> 2) ? shots << 2 : QSV_NZ_ACCEPT_ROUND_MAX;
+  int rc = hbm ? nz_hbm_slots(h, s, slot_shots < cap ? slot_shots : cap, slots, &slot_grid) : QSV_OK;
+  std::vector<uint64_t> words;
+  uint64_t got = 0, examined = 0;
+  hipError_t e = hipSuccess;
+  while (rc == QSV_OK && e == hipSuccess && got < shots && examined < max_attempts) {
+    uint64_t n = round ? round : nz_accept_round(shots, got, examined, cap);
+    if (n > max_attempts - examined) n = max_attempts - examined;
+    const NzAccept a = {first_shot + examined, fix_mask, fix_val};
+    c.shots = n;
+    if (hbm) {
+      NzHbmLaunch l;
+      static_cast<NzCall&>(l) = c;
+      l.grid = (unsigned)(n < slot_grid ? n : slot_grid);
+      l.d_slots = slots.p;
+      e = qsv_noise_hbm_launch_accept(l, a);
+    } else {
+      NzLaunch l;
+      static_cast<NzCall&>(l) = c;
+      l.n_cu = s.n_cu;
+      l.max_grid = h->opt_noisy_grid;
+      l.kraus = has_kraus;
+      unsigned grid = 0;
+      e = qsv_noise_launch_accept(l, a, &grid);
+    }
+    if (e != hipSuccess) break;
+    words.resize(n);
+    e = hipMemcpyAsync(words.data(), c.d_out, n * sizeof(uint64_t), hipMemcpyDeviceToHost, s.stream);
+    if (e != hipSuccess) break;
+    e = hipStreamSynchronize(s.stream);
+    if (e != hipSuccess) break;
+    uint64_t i = 0;
+    for (; i < n && got < shots; ++i)
+      if ((words[i] & fix_mask) == fix_val) {
+        out_bits[got] = words[i];
+        if (out_shot) out_shot[got] = a.first_shot + i;
+        ++got;
+      }
+    examined += got == shots ? i : n;                      // up to the last accepted attempt, or the whole round
+  }
+  // idle on every way out, before the slots are freed
+  const hipError_t e2 = hipStreamSynchronize(s.stream);
+  CHK(rc);
+  HIPCHK(e);
+  HIPCHK(e2);
+  *accepted = got;
+  *attempts = examined;
+  return QSV_OK;
 }
 
 // ------------------------------------------------------------------------------------------

@@ -22,7 +22,8 @@ struct NzOp {
   uint32_t n : 16;     // DIAG, PAULI: number of listed qubits; KRAUS: number of operators (1..4)
   uint32_t cmask;      // control qubits (1Q, MCX, MCPHASE: all its qubits); NZ_INIT: the uniform mask.  DIAG, PAULI: listed
   uint32_t cval;       // qubits 0..3 / values the control bits must have.  DIAG, PAULI: listed qubits 4..7, 8 bits each
-                       // MEASURE: cmask = classical bit | release << 8, cval = the record's ordinal among the MEASURE records
+                       // MEASURE: cmask = classical bit | release << 8 | decisive << 9 (NZ_DECISIVE, set for
+                       // qsv_noisy_sample_accept only), cval = the record's ordinal among the MEASURE records
   uint32_t off;        // into the pool (doubles): 1Q 8 = m00 m01 m10 m11; DIAG 2^n complex; MCPHASE (cos, sin);
                        // INIT the amplitude value; PAULI 4^n cumulative probabilities; KRAUS n x 8 = the K_k as 1Q, then
                        // n x 4 = (E00, E11, Re E01, Im E01) of E_k = K_k^dg K_k; MEASURE 2 = P(flip | 0), P(flip | 1)
@@ -30,6 +31,11 @@ struct NzOp {
   uint64_t pad2;
 };
 static_assert(sizeof(NzOp) == 32, "NzOp is 32 bytes");
+
+// A MEASURE record is decisive when it is the last record to write a classical bit that the call fixes (fix_mask of
+// qsv_noisy_sample_accept): the bit it leaves in the shot's word is final, so a shot in which it contradicts fix_val can be
+// abandoned there.  Only the accept-aware kernels (qsv_noise_accept.hip) read the flag, and only their calls set it.
+#define NZ_DECISIVE (1u << 9)
 
 // listed qubit b of a DIAG or PAULI record
 __host__ __device__ __forceinline__ uint32_t nz_qubit(const NzOp& o, uint32_t b) {
@@ -76,6 +82,12 @@ struct NzCall {
   bool measure;             // the stream holds an NZ_MEASURE op: a kernel instantiation that knows the kind is launched
 };
 
+// what an accept-aware launch takes besides: it runs the shots first_shot + [0, shots) and writes shot first_shot + i to
+// d_out[i]; a shot whose word contradicts fix_val at a decisive record ends there (its word as it stands is stored)
+struct NzAccept {
+  uint64_t first_shot, fix_mask, fix_val;
+};
+
 struct NzLaunch : NzCall {
   int n_cu;
   int max_grid;             // 0: as many workgroups as the chip holds at once
@@ -86,3 +98,5 @@ struct NzLaunch : NzCall {
 hipError_t qsv_noise_launch(const NzLaunch& l, unsigned* grid);
 // the same for a stream that holds an NZ_MEASURE op (qsv_noise_measure.hip); qsv_noise_launch comes here by itself
 hipError_t qsv_noise_launch_measure(const NzLaunch& l, unsigned* grid);
+// the accept-aware kernels (qsv_noise_accept.hip), for any stream; l.measure and l.kraus are not looked at
+hipError_t qsv_noise_launch_accept(const NzLaunch& l, const NzAccept& a, unsigned* grid);

@@ -18,3 +18,5 @@ hipError_t qsv_noise_hbm_resident(int n_cu, uint64_t* workgroups);
 hipError_t qsv_noise_hbm_launch(const NzHbmLaunch& l);
 // the same for a stream that holds an NZ_MEASURE op (qsv_noise_measure.hip); qsv_noise_hbm_launch comes here by itself
 hipError_t qsv_noise_hbm_launch_measure(const NzHbmLaunch& l);
+// the accept-aware kernel (qsv_noise_accept.hip), for any stream, after the checks of qsv_noise_hbm_launch
+hipError_t qsv_noise_hbm_launch_accept(const NzHbmLaunch& l, const NzAccept& a);

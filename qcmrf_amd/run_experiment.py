@@ -26,7 +26,12 @@ exact distributions, and those are written as well, one ``{bitstring: p}`` per c
 
 ``--post-select`` draws every shot from the branch in which all clique ancillas read 0 (``QCMRF.post_selection()``): the
 counts, SHOTS Gibbs samples per circuit with full-width keys, go to ``result_simulation_postselected_<SCALE>.json`` and the
-exact success probabilities, one float per circuit, to ``success_simulation_<SCALE>.json``.  Ideal state-vector runs only.
+exact success probabilities, one float per circuit, to ``success_simulation_<SCALE>.json``.  Together with the noise options
+(or ``--method density_matrix``) the condition becomes the run option ``accept``: noisy attempts are made until SHOTS of them
+read 0 on every ancilla (attempts that can no longer be accepted are abandoned on the device; ``--noisy-measure auto`` is
+what lets them), the counts go to ``result_simulation_noisy_postselected_<SCALE>.json`` and the success rates to
+``success_simulation_noisy_<SCALE>.json``: the estimates (SHOTS - 1) / (attempts - 1), or the exact probabilities with
+``--method density_matrix``.
 """
 from __future__ import annotations
 
@@ -58,7 +63,8 @@ def main(argv=None):
                     help="noisy run: take every measurement at the end (deferred, the default) or mid-circuit ones when they occur, "
                          "their qubits recycled (in_place; auto: in place iff that makes the per-shot state narrower)")
     ap.add_argument("--post-select", action="store_true",
-                    help="every shot from the branch in which all clique ancillas read 0; also writes the exact success probabilities")
+                    help="every shot from the branch in which all clique ancillas read 0; also writes the success probabilities "
+                         "(exact; estimated from the attempts made when the run is noisy)")
     args = ap.parse_args(argv)
     model = ibm_like_model(args.depolarizing, args.readout, args.t1, args.t2, args.gate_time)
 
@@ -77,9 +83,8 @@ def main(argv=None):
         f.write(json.dumps({"GRAPHS": GRAPHS, "THETAS": THETAS}, indent=4))
 
     CIRCS = [QCMRF(C, THETAS[j][i], with_measurements=True) for j, C in enumerate(GRAPHS) for i in range(args.reps)]
-    if args.post_select and (model is not None or args.method is not None):
-        raise ValueError("--post-select runs the ideal circuits as state vectors: no noise options, no --method")
     POST = [qc.post_selection() for qc in CIRCS] if args.post_select else None      # (classical bits: lowering keeps them)
+    ACCEPT = POST is not None and (model is not None or args.method is not None)    # no exact conditioned state vector: accept
     if HAVE_QISKIT:                                   # pragma: no cover - Qiskit absent in this image
         from qiskit import transpile
         CIRCS = transpile(CIRCS, basis_gates=['cx', 'id', 'rz', 'sx', 'x'])
@@ -95,18 +100,19 @@ def main(argv=None):
     if args.noisy_measure is not None:
         extra["noisy_measure"] = args.noisy_measure
     if POST is not None:
-        extra["post_select"] = POST
+        extra["accept" if ACCEPT else "post_select"] = POST
     result = simulator.run(CIRCS, shots=args.shots, seed_simulator=args.seed_simulator, **extra).result()
     counts = result.get_counts()
     dt = time.perf_counter() - t0
     print("%d circuits x %d shots: %.3f s in run().result().get_counts() (%.2f ms per circuit)"
           % (len(CIRCS), args.shots, dt, dt / len(CIRCS) * 1e3), file=sys.stderr)
-    name = "result_simulation_postselected_" if POST is not None else "result_simulation_" if model is None else "result_simulation_noisy_"
+    noisy = "" if model is None else "noisy_"
+    name = "result_simulation_" + noisy + ("postselected_" if POST is not None else "")
     with open(os.path.join(args.outdir, name + str(args.scale) + ".json"), "w") as f:
         f.write(json.dumps(counts, indent=4))
     if POST is not None:
-        success = [float(r["metadata"]["post_select_probability"]) for r in result.results]
-        with open(os.path.join(args.outdir, "success_simulation_" + str(args.scale) + ".json"), "w") as f:
+        success = [float(r["metadata"]["accept_probability" if ACCEPT else "post_select_probability"]) for r in result.results]
+        with open(os.path.join(args.outdir, "success_simulation_" + noisy + str(args.scale) + ".json"), "w") as f:
             f.write(json.dumps(success, indent=4))
     if args.method == "density_matrix":
         probs = result.get_probabilities()
