@@ -838,7 +838,7 @@ class QsvBackend:
         meta = {"n_qubits": ing.num_qubits, "n_source_ops": ing.n_source_ops, "n_device_ops": len(pl.ops),
                 "n_exchanges": pl.n_exchanges, "n_shards": n_shards, "layout": list(pl.layout),
                 "fusion": opts["fusion"], "time_compile": t1 - t0, "time_evolve": t2 - t1,
-                "time_sample": t3 - t2, "time_taken": t3 - t0, "seed_simulator": seed}
+                "time_sample": t3 - t2, "time_taken": t3 - t0, "seed_simulator": seed, "ingest_path": ing.ingest_path}
         meta.update(post_meta)
         if comm.world > 1 and opts.get("gather_counts", "root") != "all":
             meta["counts_on_rank"] = 0

@@ -39,6 +39,7 @@ class Ingested:
         self.readout = {}             # clbit index -> (P(flip | 0), P(flip | 1)) of its measurement (noise models only)
         self.n_pauli = 0              # "pauli" ops the noise model added
         self.n_kraus = 0              # "kraus" ops the noise model added
+        self.ingest_path = "python"   # what read this process's clique blocks: "native" (all of them), "python" (all, or there were none), "mixed"
 
 
 def _index_of(circuit, bit, cache):
@@ -342,6 +343,69 @@ def _block_of_key(key):
     return res
 
 
+try:
+    from . import _ingest_native          # built by qcmrf_amd.build next to libqsv.so; absent where Python's headers are missing
+    _ingest_native.set_primitives(_PRIMITIVES)
+except Exception:                         # not built, or does not load here: the blocks are read in Python (same result)
+    _ingest_native = None
+_native_read = _ingest_native.read_block if _ingest_native is not None else None
+
+
+def native_available():
+    """the native block reader was built and loads"""
+    return _ingest_native is not None
+
+
+def use_native(on=True):
+    """force the switch: blocks are read by the native reader (``on``; RuntimeError where it is not available) or by
+    the Python code.  Returns the previous setting.  The default is on wherever the module imports."""
+    global _native_read
+    was = _native_read is not None
+    if on and _ingest_native is None:
+        raise RuntimeError("qcmrf_amd._ingest_native is not built or does not import (python -m qcmrf_amd.build)")
+    _native_read = _ingest_native.read_block if on else None
+    return was
+
+
+def _read_block(definition):
+    """What ``_emit_phase_block`` reads off a definition, in Python: (signature, its phase-gate objects), or None
+    if it cannot be a block of triples.  ``_ingest_native.read_block`` is the same reading in native code."""
+    data = definition.data
+    n = len(data)
+    if n < 3 or n % 3 or getattr(definition, "global_phase", 0):
+        return None
+    qs = getattr(definition, "qubits", None)
+    if qs is None:
+        return None
+    ops, qargs = _flat(definition)
+    for p in ops[1::3]:
+        if getattr(p, "condition", None) is not None or getattr(p, "ctrl_state", None) not in (None, 1):
+            return None
+    # every AND is read afresh, compute and uncompute alike: QCMRF.py:225,227 builds a new object per append
+    t = n // 3
+    ands = ops[0::3] + ops[2::3]
+    try:
+        if any([o.condition for o in ands]):
+            return None
+    except AttributeError:                                  # no .condition attribute at all (Qiskit >= 2)
+        pass
+    defs = [getattr(o, "definition", None) for o in ands]
+    if any([d is None for d in defs]):
+        return None
+    keys = [_and_key(d) for d in defs]
+    if any([k is None for k in keys]):
+        return None
+    and_keys = [None] * n
+    and_keys[0::3] = keys[:t]
+    and_keys[2::3] = keys[t:]
+    qi = {id(b): i for i, b in enumerate(qs)}
+    try:
+        pos = tuple([qi[id(q)] for qa in qargs for q in qa])
+    except KeyError:                                        # bits equal to, but not, the definition's own objects
+        pos = tuple([definition.find_bit(q).index for qa in qargs for q in qa])
+    return (tuple([o.name for o in ops]), tuple([len(qa) for qa in qargs]), pos, tuple(and_keys)), ops[1::3]
+
+
 def _emit_phase_block(definition, qmap, out):
     """A definition that is nothing but ``AND . cp . AND`` triples on one (controls, scratch, other)
     set -- the reference's ``cU_C`` and its inverse (QCMRF.py:218-228,234) -- is a diagonal:
@@ -351,41 +415,19 @@ def _emit_phase_block(definition, qmap, out):
     The whole block is recognised in ONE step: its structural signature (names, qubit positions,
     the signatures of its AND definitions) is read off the objects and looked up; only the phase
     angles are per-instance.  The signature is content, not object identity: nothing is cached on
-    or about the caller's circuit."""
-    data = definition.data
-    n = len(data)
-    if n < 3 or n % 3 or getattr(definition, "global_phase", 0):
-        return False
-    qs = getattr(definition, "qubits", None)
-    if qs is None:
-        return False
-    ops, qargs = _flat(definition)
-    for p in ops[1::3]:
-        if getattr(p, "condition", None) is not None or getattr(p, "ctrl_state", None) not in (None, 1):
+    or about the caller's circuit.
+
+    The signature is read by the native reader where it is on (``use_native``); every shape that one does not take
+    (it answers None and decides nothing) is read by ``_read_block``, as all of them are where it is off."""
+    got = _native_read(definition) if _native_read is not None else None
+    if got is not None:
+        key, lams = got
+        cps = None
+    else:
+        got = _read_block(definition)
+        if got is None:
             return False
-    # every AND is read afresh, compute and uncompute alike: QCMRF.py:225,227 builds a new object per append
-    t = n // 3
-    ands = ops[0::3] + ops[2::3]
-    try:
-        if any([o.condition for o in ands]):
-            return False
-    except AttributeError:                                  # no .condition attribute at all (Qiskit >= 2)
-        pass
-    defs = [getattr(o, "definition", None) for o in ands]
-    if any([d is None for d in defs]):
-        return False
-    keys = [_and_key(d) for d in defs]
-    if any([k is None for k in keys]):
-        return False
-    and_keys = [None] * n
-    and_keys[0::3] = keys[:t]
-    and_keys[2::3] = keys[t:]
-    qi = {id(b): i for i, b in enumerate(qs)}
-    try:
-        pos = tuple([qi[id(q)] for qa in qargs for q in qa])
-    except KeyError:                                        # bits equal to, but not, the definition's own objects
-        pos = tuple([definition.find_bit(q).index for qa in qargs for q in qa])
-    key = (tuple([o.name for o in ops]), tuple([len(qa) for qa in qargs]), pos, tuple(and_keys))
+        key, cps = got
     blk = _block_of_key(key)
     if blk is None:
         return False
@@ -399,8 +441,9 @@ def _emit_phase_block(definition, qmap, out):
     # when the walk is over (ingest -> _finish_phase_blocks)
     op = ir.Op("diag", qubits=tuple(glob), table=None)
     out.ops.append(op)
-    out._phase_blocks.append((op, M, [_fparams(p)[0] for p in ops[1::3]]))
+    out._phase_blocks.append((op, M, lams if cps is None else [_fparams(p)[0] for p in cps]))
     out.n_source_ops += n_src
+    out._read_by[cps is None] += 1
     return True
 
 
@@ -782,6 +825,7 @@ def ingest(circuit, peephole=False, keep_measures=False, comm=None, compact=Fals
     out.noise = noise
     out._measured = set()
     out._phase_blocks = []
+    out._read_by = [0, 0]                    # blocks read by the Python code, by the native reader
     out._part = (comm.rank, comm.world) if (comm is not None and comm.world > 1 and peephole and not keep_measures) else None
     out._nblk, out._remote, out._mine, out._bail, out._exchanged = 0, {}, [], False, False
     flat = False
@@ -806,7 +850,8 @@ def ingest(circuit, peephole=False, keep_measures=False, comm=None, compact=Fals
     cregs = getattr(circuit, "cregs", None)
     if cregs:
         out.creg_sizes = [(getattr(r, "name", "c"), len(r)) for r in cregs]
-    del out._measured, out.noise
+    out.ingest_path = "python" if not out._read_by[1] else "mixed" if out._read_by[0] else "native"
+    del out._measured, out.noise, out._read_by
     return out
 
 
