@@ -275,10 +275,15 @@ enum {
                        qsv_noisy_sample only: data_off points to m x 8 doubles, each K_k row-major with (re, im) pairs as
                        for QSV_OP_1Q, followed by m x 4 doubles, E_k = K_k^dg K_k as (E00, E11, Re E01, Im E01).  Per
                        shot one k is drawn with weight <psi|E_k|psi> and K_k applied, the state keeping its mass. */
-  QSV_OP_MEASURE = 11 /* measurement of qubits[0] (n = 1) taken when it occurs, qsv_noisy_sample only: vals[0] = the classical
+  QSV_OP_MEASURE = 11,/* measurement of qubits[0] (n = 1) taken when it occurs, qsv_noisy_sample only: vals[0] = the classical
                        bit c it writes (0 <= c < 64), vals[1] = release (0 or 1: hand the qubit back in |0>), data_off points
                        to 2 doubles, P(flip | 0) and P(flip | 1) (always present; zeros: no readout error).  The contract
                        is below, next to the one of QSV_OP_KRAUS. */
+  QSV_OP_KRAUS2 = 12 /* two-qubit Kraus channel of m = vals[0] operators (1 <= m <= 16) on the distinct qubits qubits[0] and
+                       qubits[1] (n = 2), qsv_noisy_sample only: data_off points to m x 32 doubles, each K_k (4 x 4) row-major
+                       with (re, im) pairs, matrix index bit j on qubits[j], followed by m x 16 doubles, E_k = K_k^dg K_k packed
+                       as its 4 real diagonal entries E00 E11 E22 E33, then its 6 upper off-diagonal entries (0,1) (0,2) (0,3)
+                       (1,2) (1,3) (2,3) as (re, im).  The contract is below, behind the one of QSV_OP_KRAUS. */
 };
 
 /* scheduling hint from the planner: close the current multi-gate pass before this gate (the
@@ -297,7 +302,7 @@ typedef struct {
   double   angle;                  /* MCPHASE                                              */
 } qsv_op;
 
-/* run a whole program in one call (one ctypes crossing per circuit); QSV_OP_PAULI, QSV_OP_KRAUS and QSV_OP_MEASURE are refused */
+/* run a whole program in one call (one ctypes crossing per circuit); QSV_OP_PAULI, QSV_OP_KRAUS, QSV_OP_KRAUS2 and QSV_OP_MEASURE are refused */
 int qsv_exec(qsv_handle* h, const qsv_op* ops, int n_ops, const double* data, uint64_t n_data);
 
 /* ---- noisy shots: one trajectory per shot ------------------------------------------------ */
@@ -310,12 +315,23 @@ int qsv_exec(qsv_handle* h, const qsv_op* ops, int n_ops, const double* data, ui
  * state from |amp|^2, and records it as qsv_sample does:
  * out_bits[s] bit j = the value of qubit meas_qubits[j] (-1: bit j stays 0; NULL: the full basis index), each
  * measured bit flipped with probability readout[2j + value] (NULL: no readout error).
- * Kinds: INIT_ZERO, INIT_UNIFORM, 1Q, MCX, DIAG, MCPHASE, PAULI, KRAUS, MEASURE; anything else returns QSV_E_UNSUPPORTED.
+ * Kinds: INIT_ZERO, INIT_UNIFORM, 1Q, MCX, DIAG, MCPHASE, PAULI, KRAUS, KRAUS2, MEASURE; anything else returns QSV_E_UNSUPPORTED.
  * A KRAUS record on qubit t: u = the next draw of stream 0 (PAULI and KRAUS records share one draw counter, which
  * advances at every such record, m = 1 included); r00 = sum |a_i0|^2, r11 = sum |a_i1|^2, r10 = sum a_i1 conj(a_i0) over
  * the pairs (a_i0, a_i1) of t, total = r00 + r11; w_k = E00_k r00 + E11_k r11 + 2 Re(E01_k r10); the first k with w_k > 0
  * whose inclusive cumulative sum of the positive w exceeds u total is taken (none: the last k with w_k > 0), and every
  * pair is multiplied by K_k sqrt(total / w_k).
+ * A KRAUS2 record on the qubits (t0, t1) is the same rule one size up.  u = the next draw of stream 0: the draw counter is the
+ * one PAULI and KRAUS records advance, and it advances at every KRAUS2 record too, m = 1 included.  A quad is the four
+ * amplitudes (a_i0, a_i1, a_i2, a_i3) that differ only in the bits t0 and t1, a_ix having bit t0 = x & 1 and bit t1 = x >> 1;
+ * r[x][y] = sum_i a_ix conj(a_iy) over all quads, total = ((r[0][0] + r[1][1]) + r[2][2]) + r[3][3].  With the packed entries
+ * e[0..16) of E_k and the 16 real numbers of r in the same packing -- rr[0..4) = r[x][x], then (Re r[x][y], Im r[x][y]) for
+ * (x, y) = (0,1) (0,2) (0,3) (1,2) (1,3) (2,3) --, w_k = tr(E_k r) = d + 2 f, d = e[0] rr[0] + ... + e[3] rr[3] and
+ * f = e[4] rr[4] + ... + e[15] rr[15], each sum taken in ascending index (Re(E[x][y] r[y][x]) = Re E Re r + Im E Im r).  The
+ * first k with w_k > 0 whose inclusive cumulative sum of the positive w exceeds u total is taken (none: the last k with
+ * w_k > 0), and every quad is multiplied by K_k and by sqrt(total / w_k).  A state without mass stays as it is.
+ * QSV_E_BADARG, with a message that names the op: n != 2, equal qubits, a qubit at or above the width, m outside 1..16, an
+ * entry that is not finite, E tables whose sum is not the identity to 1e-9.
  * A MEASURE record on qubit t with classical bit c: the channel K_0 = |0><0|, K_1 = |1><1| (release: |0><1|) plus one recorded
  * bit.  u = the draw (seed, shot, stream 3, d), d = the ordinal of the record among the MEASURE records of the program; the
  * draw counter of stream 0 does NOT advance, so a shot meets the same Pauli and Kraus draws whether its measurements are
@@ -330,7 +346,7 @@ int qsv_exec(qsv_handle* h, const qsv_op* ops, int n_ops, const double* data, ui
  * MEASURE record writes, a flip outside [0, 1], a release flag other than 0 or 1.
  * Random numbers are Philox-4x32-10 draws keyed by the seed and counted by (shot, stream, draw): shot s of a call
  * is the same whatever the number of shots or the grid.  Runs on the handle's stream (qsv_timer_* bracket it).
- * Replaces: simulator.run(T, shots=SHOTS, noise_model=...) of an Aer noise model of Pauli and one-qubit Kraus errors. */
+ * Replaces: simulator.run(T, shots=SHOTS, noise_model=...) of an Aer noise model of Pauli, one- and two-qubit Kraus errors. */
 int qsv_noisy_sample(qsv_handle* h, const qsv_op* ops, int n_ops, const double* data, uint64_t n_data,
                      uint64_t shots, uint64_t seed, const int* meas_qubits, int n_meas,
                      const double* readout /* n_meas x 2: P(flip | 0), P(flip | 1); NULL = none */,
@@ -392,8 +408,10 @@ int qsv_noisy_sample_accept(qsv_handle* h, const qsv_op* ops, int n_ops, const d
  * qsv_density_exec runs the record stream of qsv_noisy_sample from |0..0><0..0|, exactly: a unitary record U as
  * U rho U^dg (the record on the ket bits and its mirror on the bra bits -- qubits + W, matrix and table conjugated, angle
  * negated -- through the sweeps of qsv_exec), QSV_OP_PAULI as sum_p P(p) P rho P^dg with P(p) the differences of the
- * record's cumulative table, QSV_OP_KRAUS as sum_k K_k rho K_k^dg (its E tables are not read).
- * Kinds: INIT_ZERO, INIT_UNIFORM, 1Q, MCX, DIAG, MCPHASE, PAULI (n = 1, 2), KRAUS (n = 1, 1..4 operators); MUX, KQ, SWAP, MEASURE and
+ * record's cumulative table, QSV_OP_KRAUS and QSV_OP_KRAUS2 as sum_k K_k rho K_k^dg (their E tables are not read; the
+ * 16 x 16 superoperator of a KRAUS2 record is built once per record on the host and read from device memory).
+ * Kinds: INIT_ZERO, INIT_UNIFORM, 1Q, MCX, DIAG, MCPHASE, PAULI (n = 1, 2), KRAUS (n = 1, 1..4 operators), KRAUS2 (n = 2, 1..16
+ * operators); MUX, KQ, SWAP, MEASURE and
  * handles of several shards or ranks return QSV_E_UNSUPPORTED; an odd n_qubits or a record qubit >= W QSV_E_BADARG.  Every
  * record is checked before the first one runs.
  * Replaces: simulator.run(T, noise_model=..., method="density_matrix") of Qiskit Aer. */

@@ -28,7 +28,7 @@ OPTION_DEFAULTS = {"blocks_per_cu": 1 << 16, "unroll": 4, "lowt_shuffle": 1, "no
                    "init_prod_bit0": 0, "init_prod_r": 0, "init_prod": 1, "pass_hints": 1, "dyn_lanes": 3, "multi_r": 5,
                    "exchange_chunk_log2": 24, "xframe": 1, "pass_budget": 0, "trace_passes": 0, "single_shortcut": 1, "pass_max_ops": 56, "general_r": 4, "general_light_r": 5, "swizzle": 1, "lane_map_min_l": 26, "blocksum_variant": 6, "kq_chunked": 0, "fold_init_h": 1, "general_combos": 1, "lowctl_mask": 1, "kq_variant": -1, "kq3_tile": 1, "kq_blocks_per_cu": 0, "kq_debug": 0, "kq_order": 1, "multi_nt": -1, "init_prod_nt": -1, "init_prod_grid": 0, "init_prod_group": -1, "defer_state": -1, "sums_factored": -1, "noisy_grid": 0, "sample_chain": 1, "post_select_list": -1}
 
-OP_INIT_ZERO, OP_INIT_UNIFORM, OP_1Q, OP_MCX, OP_DIAG, OP_MCPHASE, OP_MUX, OP_KQ, OP_SWAP, OP_PAULI, OP_KRAUS, OP_MEASURE = range(12)
+OP_INIT_ZERO, OP_INIT_UNIFORM, OP_1Q, OP_MCX, OP_DIAG, OP_MCPHASE, OP_MUX, OP_KQ, OP_SWAP, OP_PAULI, OP_KRAUS, OP_MEASURE, OP_KRAUS2 = range(13)
 NOISY_MAX_QUBITS = 13     # qsv_noisy_sample: one trajectory's state lives in the LDS of one workgroup
 NOISY_HBM_MAX_QUBITS = 24 # qsv_noisy_sample_hbm: one trajectory's state lives in a slot of device memory
 DENSITY_MAX_QUBITS = 17   # qsv_density_*: rho of W qubits is a vector of 2W qubits, 16 * 4^W bytes
@@ -374,7 +374,7 @@ class Engine:
         _chk(self._lib.qsv_exec(self._h, ops.ctypes.data_as(_vp), len(ops), dp, len(data)))
 
     def noisy_sample(self, ops, data, shots, seed, meas_qubits=None, readout=None):
-        """one trajectory per shot from |0..0> (qsv_noisy_sample): ops (OP_DTYPE records, QSV_OP_PAULI and QSV_OP_KRAUS included) on a
+        """one trajectory per shot from |0..0> (qsv_noisy_sample): ops (OP_DTYPE records, QSV_OP_PAULI, QSV_OP_KRAUS and QSV_OP_KRAUS2 included) on a
         single-shard handle of at most NOISY_MAX_QUBITS qubits; out[s] as ``sample``.  readout: n_meas x 2 array of
         (P(flip | 0), P(flip | 1)) per output bit, or None"""
         return self._noisy(self._lib.qsv_noisy_sample, ops, data, shots, seed, meas_qubits, readout)

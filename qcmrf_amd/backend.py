@@ -540,7 +540,7 @@ class QsvBackend:
         t3 = time.perf_counter()
         meta = {"method": "noisy", "noisy_state": state, "noisy_measure": nmeasure, "n_qubits": width,
                 "n_circuit_qubits": ing.num_qubits, "n_measure_ops": n_measure, "n_source_ops": ing.n_source_ops, "n_device_ops": len(rec),
-                "n_pauli_ops": ing.n_pauli, "n_kraus_ops": ing.n_kraus, "readout_errors": len(ing.readout), "time_compile": t1 - t0,
+                "n_pauli_ops": ing.n_pauli, "n_kraus_ops": ing.n_kraus, "n_kraus2_ops": ing.n_kraus2, "readout_errors": len(ing.readout), "time_compile": t1 - t0,
                 "time_evolve": t2 - t1, "time_sample": t3 - t2, "time_taken": t3 - t0, "seed_simulator": seed}
         meta.update(accept_meta)
         self.last_engine = None          # no resident state: every shot had its own
@@ -655,7 +655,7 @@ class QsvBackend:
             counts = _format_keys(uv, uc, ing.num_clbits, ing.creg_sizes)
         t3 = time.perf_counter()
         meta = {"method": "density_matrix", "n_qubits": W, "n_source_ops": ing.n_source_ops, "n_device_ops": len(rec),
-                "n_pauli_ops": ing.n_pauli, "n_kraus_ops": ing.n_kraus, "readout_errors": len(ing.readout), "trace": float(trace),
+                "n_pauli_ops": ing.n_pauli, "n_kraus_ops": ing.n_kraus, "n_kraus2_ops": ing.n_kraus2, "readout_errors": len(ing.readout), "trace": float(trace),
                 "state_bytes": state_bytes, "time_compile": t1 - t0, "time_evolve": t2 - t1, "time_sample": t3 - t2,
                 "time_taken": t3 - t0, "seed_simulator": seed}
         meta.update(accept_meta)

@@ -32,6 +32,11 @@ struct DmLaunch {
 
 hipError_t qsv_dm_pauli_launch(const DmLaunch& l, int n, const DmPauli& c);
 hipError_t qsv_dm_kraus_launch(const DmLaunch& l, const DmKraus& s);
+// A KRAUS2 record: d_s = the 16 x 16 superoperator in device memory (512 doubles: too large for kernel arguments),
+// S[e][f] (row-major, (re, im)) = sum_k K_k[a][a'] conj(K_k[b][b']), e = a | b << 2, f = a' | b' << 2, with a, b, a', b' the
+// two-bit indices of the record's operators (bit j on error qubit j): block bits 0, 1 the ket bits, 2, 3 the bra bits (DmPos)
+#define QSV_DM_KRAUS2_DOUBLES 512
+hipError_t qsv_dm_kraus2_launch(const DmLaunch& l, const double* d_s);
 
 // out[i] = Re rho[i, i], i < 2^W: one strided read
 hipError_t qsv_dm_diag_launch(hipStream_t stream, const double2* amp, int W, double* out);

@@ -8,6 +8,8 @@
 //                   coefficients per element, chosen by d = (i xor j) on the error qubits, and orbits of 2^N elements.
 //   k_dm_kraus      rho -> sum_k K_k rho K_k^dg on one qubit: every 2 x 2 block B[a, b] over (i_q, j_q) times the 4 x 4
 //                   superoperator S (built once per record on the host).
+//   k_dm_kraus2     the same on two qubits: 4 x 4 blocks of 16 amplitudes times the 16 x 16 superoperator, which comes
+//                   through device memory.
 // A thread owns whole blocks: the 4^N amplitudes that differ only in the ket and bra bits of the error qubits.  For a low
 // error qubit q its loads are adjacent 16-byte pieces of one line (q = 0: v and v + 1); the bra bit q + W is a far stride
 // for every W that matters.  Each amplitude is read once and written once: 32 B per amplitude, a pure stream.
@@ -79,6 +81,29 @@ __global__ __launch_bounds__(QSV_TPB) void k_dm_kraus(cplx* __restrict__ amp, ui
   }
 }
 
+// rho -> sum_k K_k rho K_k^dg on two qubits: every 4 x 4 block B[a, b] over the ket and bra bits of the two error qubits, 16
+// amplitudes, times the 16 x 16 superoperator S.  S is read from device memory at addresses every lane shares (scalar loads
+// that stay in the scalar cache: 4 KiB); the 16 amplitudes of a block are all loaded before the first is stored.
+template <bool NT>
+__global__ __launch_bounds__(QSV_TPB) void k_dm_kraus2(cplx* __restrict__ amp, uint64_t nblocks, DmPos p, const double* __restrict__ S) {
+  uint64_t off[16];
+#pragma unroll
+  for (int e = 0; e < 16; ++e) off[e] = dm_offset<4>(e, p);
+  for (uint64_t t = (uint64_t)blockIdx.x * QSV_TPB + threadIdx.x; t < nblocks; t += (uint64_t)gridDim.x * QSV_TPB) {
+    cplx* b = amp + dm_base<4>(t, p);
+    cplx in[16];
+#pragma unroll
+    for (int e = 0; e < 16; ++e) in[e] = NT ? ld_nt(b + off[e]) : ld(b + off[e]);
+#pragma unroll
+    for (int e = 0; e < 16; ++e) {
+      cplx acc = cmul(make_double2(S[32 * e], S[32 * e + 1]), in[0]);
+#pragma unroll
+      for (int f = 1; f < 16; ++f) acc = cmad(make_double2(S[32 * e + 2 * f], S[32 * e + 2 * f + 1]), in[f], acc);
+      if (NT) st_nt(b + off[e], acc); else st(b + off[e], acc);
+    }
+  }
+}
+
 __global__ __launch_bounds__(QSV_TPB) void k_dm_diag(const cplx* __restrict__ amp, uint64_t n, int W, double* __restrict__ out) {
   for (uint64_t i = (uint64_t)blockIdx.x * QSV_TPB + threadIdx.x; i < n; i += (uint64_t)gridDim.x * QSV_TPB)
     out[i] = amp[i | (i << W)].x;
@@ -126,6 +151,13 @@ hipError_t qsv_dm_pauli_launch(const DmLaunch& l, int n, const DmPauli& c) {
 hipError_t qsv_dm_kraus_launch(const DmLaunch& l, const DmKraus& s) {
   if (l.nt) hipLaunchKernelGGL((k_dm_kraus<true>), dim3(l.grid), dim3(QSV_TPB), 0, l.stream, l.amp, l.nblocks, l.pos, s);
   else hipLaunchKernelGGL((k_dm_kraus<false>), dim3(l.grid), dim3(QSV_TPB), 0, l.stream, l.amp, l.nblocks, l.pos, s);
+  return hipGetLastError();
+}
+
+hipError_t qsv_dm_kraus2_launch(const DmLaunch& l, const double* d_s) {
+  if (!d_s) return hipErrorInvalidValue;
+  if (l.nt) hipLaunchKernelGGL((k_dm_kraus2<true>), dim3(l.grid), dim3(QSV_TPB), 0, l.stream, l.amp, l.nblocks, l.pos, d_s);
+  else hipLaunchKernelGGL((k_dm_kraus2<false>), dim3(l.grid), dim3(QSV_TPB), 0, l.stream, l.amp, l.nblocks, l.pos, d_s);
   return hipGetLastError();
 }
 

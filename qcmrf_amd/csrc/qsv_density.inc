@@ -3,7 +3,7 @@
 // rho of W qubits in the shard of a 2W-qubit handle, rho[i, j] at v = i | (j << W).  The program is the record stream of
 // qsv_noisy_sample.  A unitary record runs as itself on the ket bits and as its mirror on the bra bits (qubits + W,
 // matrix and table conjugated, angle negated); every maximal run of them is ONE qsv_exec program, so ket and bra gates share
-// k_multi passes like any other gates.  PAULI and KRAUS records close the run and have kernels of their own.
+// k_multi passes like any other gates.  PAULI, KRAUS and KRAUS2 records close the run and have kernels of their own.
 // ------------------------------------------------------------------------------------------
 static int dm_check_handle(const qsv_handle* h) {
   if (!h) return fail(QSV_E_BADARG, "NULL handle");
@@ -37,7 +37,9 @@ extern "C" int qsv_density_pauli_table(int n, const double* cum, double* out) {
 
 // the entry protocol of a kernel that reads and writes the shard behind the engine's bookkeeping (as qsv_apply_kq):
 // implied zeros written first; launch() drops the cached sums
-static int dm_channel(qsv_handle* h, int n, const int* qubits, const DmPauli* pauli, const DmKraus* kraus) {
+// kraus2: the 512 doubles of a KRAUS2 record's superoperator on the host; they are staged in the shard's noisy buffer, in stream
+// order behind the kernel of an earlier record that may still read its own
+static int dm_channel(qsv_handle* h, int n, const int* qubits, const DmPauli* pauli, const DmKraus* kraus, const double* kraus2 = nullptr) {
   CHK(materialize_all(h));
   Shard& s = h->shards[0];
   CHK(shard_set(s));
@@ -57,6 +59,20 @@ static int dm_channel(qsv_handle* h, int n, const int* qubits, const DmPauli* pa
   for (int k = 0; k < 2 * n; ++k) l.pos.ins[k] = l.pos.pos[k];
   std::sort(l.pos.ins, l.pos.ins + 2 * n);
   hipError_t e = hipSuccess;
+  if (kraus2) {
+    const size_t bytes = QSV_DM_KRAUS2_DOUBLES * sizeof(double);
+    if (s.noisy_cap < bytes) {
+      if (s.d_noisy) { HIPCHK(hipStreamSynchronize(s.stream)); HIPCHK(hipFree(s.d_noisy)); }
+      s.d_noisy = nullptr;
+      s.noisy_cap = 0;
+      HIPCHK(hipMalloc(&s.d_noisy, bytes));
+      s.noisy_cap = bytes;
+    }
+    HIPCHK(hipMemcpyAsync(s.d_noisy, kraus2, bytes, hipMemcpyHostToDevice, s.stream));
+    CHK(launch(h, s, QSV_K_KQ, 32.0 * (double)N, [&] { e = qsv_dm_kraus2_launch(l, reinterpret_cast<const double*>(s.d_noisy)); }));
+    HIPCHK(e);
+    return QSV_OK;
+  }
   CHK(launch(h, s, QSV_K_KQ, 32.0 * (double)N, [&] { e = pauli ? qsv_dm_pauli_launch(l, n, *pauli) : qsv_dm_kraus_launch(l, *kraus); }));
   HIPCHK(e);
   return QSV_OK;
@@ -114,10 +130,23 @@ extern "C" int qsv_density_exec(qsv_handle* h, const qsv_op* ops, int n_ops, con
           if (!std::isfinite(data[o.data_off + j])) return fail(QSV_E_BADARG, "op %d: Kraus entry %d is not finite", i, j);
         break;
       }
+      case QSV_OP_KRAUS2: {
+        if (o.n != 2) return fail(QSV_E_BADARG, "op %d: QSV_OP_KRAUS2 (a two-qubit Kraus channel) acts on 2 qubits, not %d", i, o.n);
+        for (int b = 0; b < 2; ++b)
+          if (o.qubits[b] < 0 || o.qubits[b] >= W)
+            return fail(QSV_E_BADARG, "op %d: QSV_OP_KRAUS2 qubit %d not in [0,%d) of the density matrix", i, o.qubits[b], W);
+        if (o.qubits[0] == o.qubits[1]) return fail(QSV_E_BADARG, "op %d: QSV_OP_KRAUS2 names qubit %d twice", i, o.qubits[0]);
+        const int m = o.vals[0];
+        if (m < 1 || m > 16) return fail(QSV_E_BADARG, "op %d: QSV_OP_KRAUS2 has 1 to 16 operators, not %d", i, m);
+        CHK(need(i, o, 48ull * m));                        // the record carries its E tables; this method does not read them
+        for (int j = 0; j < 32 * m; ++j)
+          if (!std::isfinite(data[o.data_off + j])) return fail(QSV_E_BADARG, "op %d: QSV_OP_KRAUS2 entry %d is not finite", i, j);
+        break;
+      }
       case QSV_OP_MEASURE:
         return fail(QSV_E_UNSUPPORTED, "op %d: QSV_OP_MEASURE (a measurement taken in place) runs in qsv_noisy_sample only; the density-matrix method defers every measurement", i);
       case QSV_OP_MUX: case QSV_OP_KQ: case QSV_OP_SWAP:
-        return fail(QSV_E_UNSUPPORTED, "op %d: kind %d is not supported by the density-matrix method (INIT, 1Q, MCX, DIAG, MCPHASE, PAULI, KRAUS only)", i, o.kind);
+        return fail(QSV_E_UNSUPPORTED, "op %d: kind %d is not supported by the density-matrix method (INIT, 1Q, MCX, DIAG, MCPHASE, PAULI, KRAUS, KRAUS2 only)", i, o.kind);
       default:
         return fail(QSV_E_BADARG, "op %d: unknown kind %d", i, o.kind);
     }
@@ -187,6 +216,23 @@ extern "C" int qsv_density_exec(qsv_handle* h, const qsv_op* ops, int n_ops, con
             }
         }
         CHK(dm_channel(h, 1, o.qubits, nullptr, &s));
+        break;
+      }
+      case QSV_OP_KRAUS2: {
+        CHK(flush_run());
+        const int m = o.vals[0];
+        std::vector<double> s(QSV_DM_KRAUS2_DOUBLES, 0.0);
+        for (int k = 0; k < m; ++k) {
+          const double* K = d + 32 * k;                    // K[a][a'] at 2 (4a + a')
+          for (int e = 0; e < 16; ++e)
+            for (int f = 0; f < 16; ++f) {
+              const double* x = K + 2 * (4 * (e & 3) + (f & 3));      // K[a][a']
+              const double* y = K + 2 * (4 * (e >> 2) + (f >> 2));    // K[b][b'], conjugated
+              s[32 * e + 2 * f] += x[0] * y[0] + x[1] * y[1];
+              s[32 * e + 2 * f + 1] += x[1] * y[0] - x[0] * y[1];
+            }
+        }
+        CHK(dm_channel(h, 2, o.qubits, nullptr, nullptr, s.data()));
         break;
       }
       default: break;

@@ -136,6 +136,8 @@ extern "C" int qsv_exec(qsv_handle* h, const qsv_op* ops, int n_ops, const doubl
         return fail(QSV_E_BADARG, "op %d: QSV_OP_PAULI (a random Pauli) runs in qsv_noisy_sample only, not in qsv_exec", i);
       case QSV_OP_KRAUS:
         return fail(QSV_E_BADARG, "op %d: QSV_OP_KRAUS (a Kraus channel) runs in qsv_noisy_sample only, not in qsv_exec", i);
+      case QSV_OP_KRAUS2:
+        return fail(QSV_E_BADARG, "op %d: QSV_OP_KRAUS2 (a two-qubit Kraus channel) runs in qsv_noisy_sample only, not in qsv_exec", i);
       case QSV_OP_MEASURE:
         return fail(QSV_E_BADARG, "op %d: QSV_OP_MEASURE (a measurement taken in place) runs in qsv_noisy_sample only, not in qsv_exec", i);
       default:
@@ -208,11 +210,12 @@ static int nz_check_meas(qsv_handle* h, const int* meas_qubits, int n_meas, cons
 // then what it was without the parameter): the last MEASURE record to write a bit of it is marked NZ_DECISIVE -- a bit may be
 // written twice, and only its last write may end a shot.  *written (may be NULL): the bits MEASURE records write.
 static int nz_encode(qsv_handle* h, const qsv_op* ops, int n_ops, const double* data, uint64_t n_data, const int* meas_qubits,
-                     int n_meas, std::vector<NzOp>& cops, NzPool& pool, bool* has_kraus, bool* has_measure, uint64_t fix_mask = 0,
-                     uint64_t* written = nullptr) {
+                     int n_meas, std::vector<NzOp>& cops, NzPool& pool, bool* has_kraus, bool* has_measure, bool* has_kraus2,
+                     uint64_t fix_mask = 0, uint64_t* written = nullptr) {
   cops.reserve(n_ops);
   *has_kraus = false;
   *has_measure = false;
+  *has_kraus2 = false;
   uint32_t n_measure = 0;
   for (int i = 0; i < n_ops; ++i) {
     const qsv_op& o = ops[i];
@@ -304,6 +307,35 @@ static int nz_encode(qsv_handle* h, const qsv_op* ops, int n_ops, const double* 
         *has_kraus = true;
         break;
       }
+      case QSV_OP_KRAUS2: {
+        if (o.n != 2) return fail(QSV_E_BADARG, "op %d: QSV_OP_KRAUS2 (a two-qubit Kraus channel) acts on 2 qubits, not %d", i, o.n);
+        for (int b = 0; b < 2; ++b)
+          if (o.qubits[b] < 0 || o.qubits[b] >= h->W)
+            return fail(QSV_E_BADARG, "op %d: QSV_OP_KRAUS2 qubit %d not in [0,%d)", i, o.qubits[b], h->W);
+        if (o.qubits[0] == o.qubits[1]) return fail(QSV_E_BADARG, "op %d: QSV_OP_KRAUS2 names qubit %d twice", i, o.qubits[0]);
+        const int m = o.vals[0];
+        if (m < 1 || m > 16) return fail(QSV_E_BADARG, "op %d: QSV_OP_KRAUS2 has 1 to 16 operators, not %d", i, m);
+        CHK(need(48ull * m));
+        for (int j = 0; j < 48 * m; ++j)
+          if (!std::isfinite(d[j])) return fail(QSV_E_BADARG, "op %d: QSV_OP_KRAUS2 entry %d is not finite", i, j);
+        double sum[16] = {0.0};
+        for (int k = 0; k < m; ++k) {
+          const double* e = d + 32 * m + 16 * k;
+          for (int j = 0; j < 4; ++j)
+            if (e[j] < 0.0) return fail(QSV_E_BADARG, "op %d: QSV_OP_KRAUS2: K^dg K of operator %d has a negative diagonal", i, k);
+          for (int j = 0; j < 16; ++j) sum[j] += e[j];
+        }
+        for (int j = 0; j < 16; ++j)
+          if (std::fabs(sum[j] - (j < 4 ? 1.0 : 0.0)) > 1e-9)
+            return fail(QSV_E_BADARG, "op %d: QSV_OP_KRAUS2: the K^dg K of a Kraus channel must sum to the identity (packed entry %d sums to %.17g)", i, j, sum[j]);
+        c.kind = NZ_KRAUS2;
+        c.target = (uint8_t)o.qubits[0];
+        c.cmask = (uint32_t)o.qubits[1];
+        c.n = (uint16_t)m;
+        c.off = pool.put(d, 48 * (size_t)m);
+        *has_kraus2 = true;
+        break;
+      }
       case QSV_OP_MEASURE: {
         if (o.n != 1) return fail(QSV_E_BADARG, "op %d: QSV_OP_MEASURE measures 1 qubit, not %d", i, o.n);
         CHK(check_qubit(h, o.qubits[0], "QSV_OP_MEASURE"));
@@ -326,7 +358,7 @@ static int nz_encode(qsv_handle* h, const qsv_op* ops, int n_ops, const double* 
         break;
       }
       default:
-        return fail(QSV_E_UNSUPPORTED, "op %d: kind %d is not supported by noisy shots (INIT, 1Q, MCX, DIAG, MCPHASE, PAULI, KRAUS, MEASURE only)", i, o.kind);
+        return fail(QSV_E_UNSUPPORTED, "op %d: kind %d is not supported by noisy shots (INIT, 1Q, MCX, DIAG, MCPHASE, PAULI, KRAUS, KRAUS2, MEASURE only)", i, o.kind);
     }
     cops.push_back(c);
   }
@@ -376,9 +408,9 @@ static int nz_stage(Shard& s, const std::vector<NzOp>& cops, const std::vector<d
 // records -> compact records, pool and measurement map of one call
 static int nz_prepare(qsv_handle* h, const qsv_op* ops, int n_ops, const double* data, uint64_t n_data, const int* meas_qubits,
                       int n_meas, const double* readout, std::vector<NzOp>& cops, NzPool& pool, bool* has_kraus, bool* has_measure,
-                      NzMeas* meas, uint64_t fix_mask = 0, uint64_t* written = nullptr) {
+                      bool* has_kraus2, NzMeas* meas, uint64_t fix_mask = 0, uint64_t* written = nullptr) {
   CHK(nz_check_meas(h, meas_qubits, n_meas, readout));
-  CHK(nz_encode(h, ops, n_ops, data, n_data, meas_qubits, n_meas, cops, pool, has_kraus, has_measure, fix_mask, written));
+  CHK(nz_encode(h, ops, n_ops, data, n_data, meas_qubits, n_meas, cops, pool, has_kraus, has_measure, has_kraus2, fix_mask, written));
   meas->n = meas_qubits ? n_meas : -1;
   meas->readout = -1;
   meas->pos = nullptr;
@@ -399,9 +431,9 @@ static int nz_run(qsv_handle* h, const qsv_op* ops, int n_ops, const double* dat
   if (h->W > max_w) return fail(QSV_E_BADARG, "noisy shots keep one %d-qubit state per trajectory in %s: at most %d qubits", h->W, where, max_w);
   std::vector<NzOp> cops;
   NzPool pool;
-  bool has_kraus = false, has_measure = false;
+  bool has_kraus = false, has_measure = false, has_kraus2 = false;
   NzCall c;
-  CHK(nz_prepare(h, ops, n_ops, data, n_data, meas_qubits, n_meas, readout, cops, pool, &has_kraus, &has_measure, &c.meas));
+  CHK(nz_prepare(h, ops, n_ops, data, n_data, meas_qubits, n_meas, readout, cops, pool, &has_kraus, &has_measure, &has_kraus2, &c.meas));
   if (shots == 0) return QSV_OK;
   Shard& s = h->shards[0];
   CHK(shard_set(s));
@@ -417,6 +449,7 @@ static int nz_run(qsv_handle* h, const qsv_op* ops, int n_ops, const double* dat
   c.meas.pos = st.pos;
   c.d_out = st.out;
   c.measure = has_measure;
+  c.kraus2 = has_kraus2;
   const int rc = launch(s, c, has_kraus);
   hipError_t e = hipSuccess;
   if (rc == QSV_OK) e = hipMemcpyAsync(out_bits, c.d_out, shots * sizeof(uint64_t), hipMemcpyDeviceToHost, s.stream);
@@ -543,11 +576,11 @@ extern "C" int qsv_noisy_sample_accept(qsv_handle* h, const qsv_op* ops, int n_o
                 hbm ? "a slot of device memory" : "LDS", max_w);
   std::vector<NzOp> cops;
   NzPool pool;
-  bool has_kraus = false, has_measure = false;
+  bool has_kraus = false, has_measure = false, has_kraus2 = false;
   uint64_t written = 0;
   NzCall c;
-  CHK(nz_prepare(h, ops, n_ops, data, n_data, meas_qubits, n_meas, readout, cops, pool, &has_kraus, &has_measure, &c.meas, fix_mask,
-                 &written));
+  CHK(nz_prepare(h, ops, n_ops, data, n_data, meas_qubits, n_meas, readout, cops, pool, &has_kraus, &has_measure, &has_kraus2, &c.meas,
+                 fix_mask, &written));
   CHK(nz_check_accept(h, meas_qubits, n_meas, fix_mask, fix_val, written));
   if (shots == 0) return QSV_OK;
   if (max_attempts == 0) return fail(QSV_E_BADARG, "max_attempts = 0 with %llu shots to accept", (unsigned long long)shots);
@@ -568,6 +601,7 @@ extern "C" int qsv_noisy_sample_accept(qsv_handle* h, const qsv_op* ops, int n_o
   c.meas.pos = st.pos;
   c.d_out = st.out;
   c.measure = has_measure;
+  c.kraus2 = has_kraus2;
   // and the slots: as a plain call of max(64, 4 shots) shots would size them, so that a call for a few shots does not take the
   // memory of a full grid; a round of more attempts runs them in these
   NzSlots slots;

@@ -9,7 +9,7 @@
 #define QSV_NZ_WAVE_MAXW 10       // up to here one wavefront per trajectory (no workgroup barriers)
 #define QSV_NZ_KRAUS_1PAIR_MAXW 7 // up to here a lane owns at most one pair of a Kraus op's target (2^6 pairs, 64 lanes)
 
-enum { NZ_INIT = 0, NZ_1Q, NZ_MCX, NZ_DIAG, NZ_MCPHASE, NZ_PAULI, NZ_KRAUS, NZ_MEASURE };
+enum { NZ_INIT = 0, NZ_1Q, NZ_MCX, NZ_DIAG, NZ_MCPHASE, NZ_PAULI, NZ_KRAUS, NZ_MEASURE, NZ_KRAUS2 };
 
 // One op of the compact stream, 32 bytes: every trajectory reads the whole list, so a record is a quarter of an
 // L2 line instead of the 168 bytes of a qsv_op.  Both paths read this record: qubits < 256, masks of 32 bits (the slot path
@@ -18,15 +18,17 @@ enum { NZ_INIT = 0, NZ_1Q, NZ_MCX, NZ_DIAG, NZ_MCPHASE, NZ_PAULI, NZ_KRAUS, NZ_M
 // (nz_fetch): DIAG and PAULI have no controls, and their first 8 listed qubits take the place of cmask and cval.
 struct NzOp {
   uint32_t kind : 8;   // NZ_*.  Bit fields of one word: the record's first 16 bytes have no hole and load as one piece
-  uint32_t target : 8; // 1Q, MCX, KRAUS, MEASURE
-  uint32_t n : 16;     // DIAG, PAULI: number of listed qubits; KRAUS: number of operators (1..4)
+  uint32_t target : 8; // 1Q, MCX, KRAUS, MEASURE; KRAUS2: its qubit 0 (matrix index bit 0)
+  uint32_t n : 16;     // DIAG, PAULI: number of listed qubits; KRAUS: number of operators (1..4); KRAUS2: the same (1..16)
   uint32_t cmask;      // control qubits (1Q, MCX, MCPHASE: all its qubits); NZ_INIT: the uniform mask.  DIAG, PAULI: listed
   uint32_t cval;       // qubits 0..3 / values the control bits must have.  DIAG, PAULI: listed qubits 4..7, 8 bits each
                        // MEASURE: cmask = classical bit | release << 8 | decisive << 9 (NZ_DECISIVE, set for
                        // qsv_noisy_sample_accept only), cval = the record's ordinal among the MEASURE records
+                       // KRAUS2: cmask = its qubit 1 (matrix index bit 1)
   uint32_t off;        // into the pool (doubles): 1Q 8 = m00 m01 m10 m11; DIAG 2^n complex; MCPHASE (cos, sin);
                        // INIT the amplitude value; PAULI 4^n cumulative probabilities; KRAUS n x 8 = the K_k as 1Q, then
-                       // n x 4 = (E00, E11, Re E01, Im E01) of E_k = K_k^dg K_k; MEASURE 2 = P(flip | 0), P(flip | 1)
+                       // n x 4 = (E00, E11, Re E01, Im E01) of E_k = K_k^dg K_k; MEASURE 2 = P(flip | 0), P(flip | 1);
+                       // KRAUS2 n x 32 = the K_k (4 x 4, row-major, re / im), then n x 16 = the packed E_k of QSV_OP_KRAUS2
   uint64_t ql8;        // DIAG: listed qubit b = 8..15 in bits [8 (b - 8), 8 (b - 8) + 8)
   uint64_t pad2;
 };
@@ -80,6 +82,7 @@ struct NzCall {
   NzMeas meas;
   uint64_t* d_out;
   bool measure;             // the stream holds an NZ_MEASURE op: a kernel instantiation that knows the kind is launched
+  bool kraus2;              // the stream holds an NZ_KRAUS2 op: the kernels of qsv_noise_kraus2.hip, which know every kind
 };
 
 // what an accept-aware launch takes besides: it runs the shots first_shot + [0, shots) and writes shot first_shot + i to
@@ -98,5 +101,9 @@ struct NzLaunch : NzCall {
 hipError_t qsv_noise_launch(const NzLaunch& l, unsigned* grid);
 // the same for a stream that holds an NZ_MEASURE op (qsv_noise_measure.hip); qsv_noise_launch comes here by itself
 hipError_t qsv_noise_launch_measure(const NzLaunch& l, unsigned* grid);
-// the accept-aware kernels (qsv_noise_accept.hip), for any stream; l.measure and l.kraus are not looked at
+// the accept-aware kernels (qsv_noise_accept.hip), for any stream without an NZ_KRAUS2 op; l.measure and l.kraus are not looked
+// at, and a stream with l.kraus2 goes on to qsv_noise_launch_accept_kraus2
 hipError_t qsv_noise_launch_accept(const NzLaunch& l, const NzAccept& a, unsigned* grid);
+// the same two for a stream that holds an NZ_KRAUS2 op (qsv_noise_kraus2.hip); the launchers above come here by themselves
+hipError_t qsv_noise_launch_kraus2(const NzLaunch& l, unsigned* grid);
+hipError_t qsv_noise_launch_accept_kraus2(const NzLaunch& l, const NzAccept& a, unsigned* grid);

@@ -20,3 +20,7 @@ hipError_t qsv_noise_hbm_launch(const NzHbmLaunch& l);
 hipError_t qsv_noise_hbm_launch_measure(const NzHbmLaunch& l);
 // the accept-aware kernel (qsv_noise_accept.hip), for any stream, after the checks of qsv_noise_hbm_launch
 hipError_t qsv_noise_hbm_launch_accept(const NzHbmLaunch& l, const NzAccept& a);
+// the two launches above for a stream that holds an NZ_KRAUS2 op (qsv_noise_kraus2.hip), after their checks; they come here by
+// themselves
+hipError_t qsv_noise_hbm_launch_kraus2(const NzHbmLaunch& l);
+hipError_t qsv_noise_hbm_launch_accept_kraus2(const NzHbmLaunch& l, const NzAccept& a);

@@ -1,6 +1,6 @@
 // qsv_noise_hbm_shots.inc -- the body of the slot-path trajectory kernels (qsv_noise_hbm_kernel.h includes it once per kernel):
 // the shots first + [blockIdx.x, shots) step gridDim.x of one workgroup in its slot, shot first + t to out[t].  The including
-// kernel has TPB, MEAS, ACC (compile-time), first and fix_val in scope besides the arguments of k_noisy_hbm.  Text and not a
+// kernel has TPB, MEAS, ACC, K2 (compile-time), first and fix_val in scope besides the arguments of k_noisy_hbm.  Text and not a
 // function, so that k_noisy_hbm compiles to the instructions it had before the accept-aware kernel existed (see there).
 // ACC (k_noisy_hbm_accept): behind a decisive MEASURE record (NZ_DECISIVE) whose bit in the shot's word differs from fix_val
 // the shot is abandoned as qsv_noise_lds_shots.inc abandons it, and for the same reasons: the branch is uniform and
@@ -24,7 +24,7 @@
     bool dead = false;
     for (int k = 0; k < n_ops; ++k) {
       const NzOp o = nz_fetch(ops, k);
-      nz_apply<TPB, QSV_NZ_HBM_B, 1, MEAS>(st, N, o, pool, tid, seed, shot, draw, mword);
+      nz_apply<TPB, QSV_NZ_HBM_B, 1, MEAS, K2>(st, N, o, pool, tid, seed, shot, draw, mword);
       if constexpr (ACC) {
         if (o.kind == NZ_MEASURE && (o.cmask & NZ_DECISIVE) && (((mword ^ fix_val) >> (o.cmask & 63u)) & 1ull)) {
           dead = true;

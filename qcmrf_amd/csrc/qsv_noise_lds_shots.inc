@@ -1,6 +1,6 @@
 // qsv_noise_lds_shots.inc -- the body of the LDS trajectory kernels (qsv_noise_kernel.h includes it once per kernel): the shots
 // first + [blockIdx.x, shots) step gridDim.x of one workgroup, shot first + t to out[t].  The including kernel has TPB, KRAUS,
-// MEAS, ACC (compile-time), first and fix_val in scope besides the arguments of k_noisy.  Text and not a function, so that
+// MEAS, ACC, K2 (compile-time), first and fix_val in scope besides the arguments of k_noisy.  Text and not a function, so that
 // k_noisy compiles to the instructions it had before the accept-aware kernel existed: through a function the arguments lose
 // their __restrict__ and the schedule changes (the slot kernel's register allocation too).
 // ACC (k_noisy_accept, MEAS only): behind a decisive MEASURE record (NZ_DECISIVE) whose bit in the shot's word differs from
@@ -24,7 +24,7 @@
     bool dead = false;
     for (int k = 0; k < n_ops; ++k) {
       const NzOp o = nz_fetch(ops, k);
-      nz_apply<TPB, 1, KRAUS, MEAS>(st, N, o, pool, tid, seed, shot, draw, mword);
+      nz_apply<TPB, 1, KRAUS, MEAS, K2>(st, N, o, pool, tid, seed, shot, draw, mword);
       if constexpr (ACC) {
         if (o.kind == NZ_MEASURE && (o.cmask & NZ_DECISIVE) && (((mword ^ fix_val) >> (o.cmask & 63u)) & 1ull)) {
           dead = true;

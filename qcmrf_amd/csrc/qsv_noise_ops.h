@@ -266,6 +266,179 @@ __device__ __forceinline__ int kraus_op(cplx* st, const NzOp& o, const double* _
   return b;
 }
 
+// ---- KRAUS2: a general two-qubit Kraus channel (the contract is in include/qsv.h, QSV_OP_KRAUS2) ---------------------------------
+// A quad is the four amplitudes that differ only in the record's two qubits; quad number p is p with a zero bit inserted at
+// the lower and then at the higher of the two positions (lom, him: the masks below them), and amplitude x of it has the bit of
+// qubit 0 = x & 1 and the bit of qubit 1 = x >> 1.  Only these addresses depend on where the two qubits lie.
+__device__ __forceinline__ uint32_t k2_base(uint32_t p, uint32_t lom, uint32_t him) {
+  const uint32_t t = ((p & ~lom) << 1) | (p & lom);
+  return ((t & ~him) << 1) | (t & him);
+}
+__device__ __forceinline__ void k2_load(const cplx* st, uint32_t i0, uint32_t b0, uint32_t b1, cplx (&a)[4]) {
+  a[0] = st[i0];
+  a[1] = st[i0 | b0];
+  a[2] = st[i0 | b1];
+  a[3] = st[i0 | b0 | b1];
+}
+// one quad added to rr, the 16 real numbers of r[x][y] = sum a_x conj(a_y) in the packing of the record's E tables: rr[0..4)
+// the diagonal, then (re, im) of (0,1) (0,2) (0,3) (1,2) (1,3) (2,3).  Every index is a constant after unrolling.
+__device__ __forceinline__ void k2_accum(double (&rr)[16], const cplx (&a)[4]) {
+#pragma unroll
+  for (int x = 0; x < 4; ++x) rr[x] += norm2(a[x]);
+#pragma unroll
+  for (int x = 0; x < 3; ++x) {
+#pragma unroll
+    for (int y = x + 1; y < 4; ++y) {
+      const int n = 4 + 2 * (x == 0 ? y - 1 : x == 1 ? y + 1 : 5);
+      rr[n] += fma(a[x].x, a[y].x, a[x].y * a[y].y);
+      rr[n + 1] += fma(a[x].y, a[y].x, -(a[x].x * a[y].y));
+    }
+  }
+}
+// The operator a KRAUS2 record draws for u and rr, which every lane holds with the same bits: w_k = tr(E_k r) = d + 2 f,
+// d over the diagonal and f over the 12 off-diagonal numbers, each in ascending index; the first k whose cumulative weight
+// exceeds u total.  Returns k, made uniform so that the operator comes in by scalar loads, and s = sqrt(total / w_k);
+// -1: the state has no mass and stays as it is.
+__device__ __forceinline__ int kraus2_pick(const double (&rr)[16], double u, const NzOp& o, const double* __restrict__ pool,
+                                           double& s) {
+  const double* E = pool + o.off + 32u * o.n;
+  const double total = ((rr[0] + rr[1]) + rr[2]) + rr[3], r = u * total;
+  double cum = 0.0, wk = 0.0, wlast = 0.0;
+  int pick = -1, last = -1;
+  for (uint32_t k = 0; k < o.n; ++k) {
+    const double* e = E + 16u * k;
+    double d = e[0] * rr[0], f = e[4] * rr[4];
+#pragma unroll
+    for (int j = 1; j < 4; ++j) d = fma(e[j], rr[j], d);
+#pragma unroll
+    for (int j = 5; j < 16; ++j) f = fma(e[j], rr[j], f);
+    const double w = fma(2.0, f, d);
+    if (w > 0.0) {
+      cum += w;
+      last = (int)k;
+      wlast = w;
+      if (pick < 0 && cum > r) { pick = (int)k; wk = w; }
+    }
+  }
+  if (pick < 0) { pick = last; wk = wlast; }                       // rounding at the top boundary: the last k with weight
+  if (pick < 0) return -1;
+  s = sqrt(total / wk);
+  return __builtin_amdgcn_readfirstlane(pick);
+}
+// n = (m a) s for the 4 x 4 operator m (row-major, re / im: uniform, so its 32 numbers are scalar operands)
+__device__ __forceinline__ void k2_apply(const double* __restrict__ m, double s, const cplx (&a)[4], cplx (&n)[4]) {
+#pragma unroll
+  for (int x = 0; x < 4; ++x) {
+    cplx acc = cmul(make_double2(m[8 * x], m[8 * x + 1]), a[0]);
+#pragma unroll
+    for (int y = 1; y < 4; ++y) acc = cmad(make_double2(m[8 * x + 2 * y], m[8 * x + 2 * y + 1]), a[y], acc);
+    n[x] = make_double2(acc.x * s, acc.y * s);
+  }
+}
+
+// One KRAUS2 record on one trajectory: rr = the 16 numbers of r summed over all quads, then every quad times the operator
+// kraus2_pick draws -- kraus_op one size up.  TPB 64 (W <= 10): a lane owns at most R quads (R = 1 up to W = 7, R = 4 up to
+// W = 10) and keeps them in registers between the reduction and the apply, so the op reads and writes the state once.  Wider
+// workgroups (R unused): the quads are read again, QB of a thread in flight (as many loads as B pairs); a thread sums its
+// quads in index order (quads past the end are zeros), the lanes' sums are made equal on every lane by the xor butterfly, the
+// waves' sums cross through static LDS (4 x 16 doubles) and every thread adds them in wave order.  The caller's barrier after
+// the op also fences that scratch.  false: a state without mass, left as it is.
+template <int TPB, int B, int R>
+__device__ __forceinline__ bool kraus2_op(cplx* st, const NzOp& o, const double* __restrict__ pool, uint32_t N, uint32_t tid,
+                                          double u) {
+  constexpr int QB = B > 1 ? B / 2 : 1;
+  const uint32_t b0 = 1u << o.target, b1 = 1u << (o.cmask & 255u);
+  const uint32_t lom = (b0 < b1 ? b0 : b1) - 1u, him = (b0 < b1 ? b1 : b0) - 1u;
+  const uint32_t nquad = N >> 2;
+  double rr[16];
+#pragma unroll
+  for (int j = 0; j < 16; ++j) rr[j] = 0.0;
+  cplx q[R][4];
+  if constexpr (TPB == 64) {
+#pragma unroll
+    for (int j = 0; j < R; ++j) {
+      const uint32_t p = tid + 64u * (uint32_t)j;
+#pragma unroll
+      for (int x = 0; x < 4; ++x) q[j][x] = make_double2(0.0, 0.0);
+      if (p < nquad) k2_load(st, k2_base(p, lom, him), b0, b1, q[j]);
+      k2_accum(rr, q[j]);
+    }
+  } else {
+    for (uint32_t p0 = tid; p0 < nquad; p0 += QB * TPB) {
+      cplx b[QB][4];
+#pragma unroll
+      for (int j = 0; j < QB; ++j) {
+        const uint32_t p = p0 + (uint32_t)j * TPB;
+#pragma unroll
+        for (int x = 0; x < 4; ++x) b[j][x] = make_double2(0.0, 0.0);
+        if (p < nquad) k2_load(st, k2_base(p, lom, him), b0, b1, b[j]);
+      }
+#pragma unroll
+      for (int j = 0; j < QB; ++j) k2_accum(rr, b[j]);
+    }
+  }
+#pragma unroll
+  for (int j = 0; j < 16; ++j) rr[j] = wave_sum(rr[j]);            // xor butterfly: all 64 lanes end with the same bits
+  if constexpr (TPB > 64) {
+    constexpr int NW = TPB / 64;
+    __shared__ double part2[NW][16];
+    if ((tid & 63u) == 0) {
+#pragma unroll
+      for (int j = 0; j < 16; ++j) part2[tid >> 6][j] = rr[j];
+    }
+    __syncthreads();
+#pragma unroll
+    for (int j = 0; j < 16; ++j) {
+      double v = part2[0][j];
+#pragma unroll
+      for (int w = 1; w < NW; ++w) v += part2[w][j];
+      rr[j] = v;
+    }
+  }
+  double s = 1.0;
+  const int pick = kraus2_pick(rr, u, o, pool, s);
+  if (pick < 0) return false;
+  const double* m = pool + o.off + 32u * (uint32_t)pick;
+  if constexpr (TPB == 64) {
+#pragma unroll
+    for (int j = 0; j < R; ++j) {
+      const uint32_t p = tid + 64u * (uint32_t)j;
+      if (p < nquad) {
+        const uint32_t i0 = k2_base(p, lom, him);
+        cplx n[4];
+        k2_apply(m, s, q[j], n);
+        st[i0] = n[0];
+        st[i0 | b0] = n[1];
+        st[i0 | b1] = n[2];
+        st[i0 | b0 | b1] = n[3];
+      }
+    }
+  } else {
+    for (uint32_t p0 = tid; p0 < nquad; p0 += QB * TPB) {
+      cplx b[QB][4];
+#pragma unroll
+      for (int j = 0; j < QB; ++j) {
+        const uint32_t p = p0 + (uint32_t)j * TPB;
+        if (p < nquad) k2_load(st, k2_base(p, lom, him), b0, b1, b[j]);
+      }
+#pragma unroll
+      for (int j = 0; j < QB; ++j) {
+        const uint32_t p = p0 + (uint32_t)j * TPB;
+        if (p < nquad) {
+          const uint32_t i0 = k2_base(p, lom, him);
+          cplx n[4];
+          k2_apply(m, s, b[j], n);
+          st[i0] = n[0];
+          st[i0 | b0] = n[1];
+          st[i0 | b1] = n[2];
+          st[i0 | b0 | b1] = n[3];
+        }
+      }
+    }
+  }
+  return true;
+}
+
 // One record on one trajectory of N amplitudes, by the TPB threads of its workgroup, and the workgroup barrier that has to
 // follow before the state is read again.  PAULI and KRAUS records take the next draw of the shot's stream NZ_STREAM_PAULI
 // (draw advances at every one of them, whatever is drawn); an identity Pauli leaves the state as it is and skips the barrier.
@@ -273,10 +446,20 @@ __device__ __forceinline__ int kraus_op(cplx* st, const NzOp& o, const double* _
 // MEAS: MEASURE records are known too (KRAUS > 0 with it: the op is built on kraus_op, and one copy of it serves both kinds).
 // A MEASURE record draws from its own stream NZ_STREAM_MEASURE, numbered by the record's ordinal, so `draw` does not advance;
 // it writes its bit, flipped by the readout draw nz_word would take for it, into `word`, which every thread holds alike.
-template <int TPB, int B, int KRAUS, bool MEAS = false>
+// K2: KRAUS2 records are known too (only with MEAS: the kernels that know the kind know every kind).  The record takes the next
+// draw of stream NZ_STREAM_PAULI, like a KRAUS record; at TPB 64 a lane holds 1 quad where it holds 1 pair, else 4 (kraus2_op).
+template <int TPB, int B, int KRAUS, bool MEAS = false, bool K2 = false>
 __device__ __forceinline__ void nz_apply(cplx* st, uint32_t N, const NzOp& o, const double* __restrict__ pool, uint32_t tid,
                                          uint64_t seed, uint64_t shot, uint32_t& draw, uint64_t& word) {
   const uint32_t half = N >> 1;
+  if constexpr (K2) {
+    static_assert(MEAS, "a kernel that knows KRAUS2 records knows MEASURE and KRAUS records");
+    if (o.kind == NZ_KRAUS2) {
+      kraus2_op<TPB, B, KRAUS == 1 ? 1 : 4>(st, o, pool, N, tid, philox_u01(seed, shot, NZ_STREAM_PAULI, draw++));
+      __syncthreads();
+      return;
+    }
+  }
   if constexpr (MEAS) {
     static_assert(KRAUS > 0, "a kernel that knows MEASURE records knows KRAUS records");
     if (o.kind == NZ_MEASURE || o.kind == NZ_KRAUS) {

@@ -39,6 +39,7 @@ class Ingested:
         self.readout = {}             # clbit index -> (P(flip | 0), P(flip | 1)) of its measurement (noise models only)
         self.n_pauli = 0              # "pauli" ops the noise model added
         self.n_kraus = 0              # "kraus" ops the noise model added
+        self.n_kraus2 = 0             # "kraus2" ops the noise model added
         self.ingest_path = "python"   # what read this process's clique blocks: "native" (all of them), "python" (all, or there were none), "mixed"
 
 
@@ -487,13 +488,15 @@ def _emit_conjugated_mcx(definition, qmap, out):
 
 def _noise_after(out, name, q):
     """the error a noise model attaches to primitive ``name`` on qubits ``q``: its terms in order behind the gate, each one
-    "pauli" or one "kraus" op, error qubit j on q[j]"""
+    "pauli", one "kraus" or one "kraus2" op, error qubit j on q[j]"""
     e = out.noise.quantum_error(name, tuple(q))
     if e is not None:
         for kind, qs, table in e.terms():
             out.ops.append(ir.Op(kind, qubits=tuple(q[j] for j in qs), table=table))
             if kind == "pauli":
                 out.n_pauli += 1
+            elif kind == "kraus2":
+                out.n_kraus2 += 1
             else:
                 out.n_kraus += 1
 

@@ -17,6 +17,8 @@ pauli    qubits, table              random Pauli (noise models, trajectory runs 
                                     index p, error qubit j = qubits[j] (x bit p >> 2j & 1, z bit p >> 2j+1 & 1; qcmrf_amd.noise)
 kraus    qubits, table              one-qubit Kraus channel on qubits[0] (noise models, trajectory runs only): table is the stack
                                     of its m <= 4 operators, shape (m, 2, 2); one is drawn per shot with weight <psi|K^dg K|psi>
+kraus2   qubits, table              two-qubit Kraus channel on (qubits[0], qubits[1]) (noise models, noisy runs only): table is the
+                                    stack of its m <= 16 operators, shape (m, 4, 4), matrix index bit j on qubits[j]
 measure  target, mask, vals, table  measurement of ``target`` into classical bit ``mask`` when it occurs (ingest with keep_measures).
                                     For noisy runs that measure in place: vals = (release,), the slot handed back in |0>, and
                                     table = (P(flip | 0), P(flip | 1)) of the measured logical qubit (None: no readout error)
@@ -173,7 +175,7 @@ class Op:
             k = self.kind
             if k in ("u", "x", "mux"):
                 s = tuple(self.ctrls) + (self.target,)
-            elif k in ("diag", "mcphase", "kq", "pauli", "kraus"):
+            elif k in ("diag", "mcphase", "kq", "pauli", "kraus", "kraus2"):
                 s = tuple(self.qubits)
             elif k == "swap":
                 s = tuple(self.a) + tuple(self.b)
@@ -204,8 +206,8 @@ class Op:
             return "kq(%s)" % (list(self.qubits),)
         if self.kind == "pauli":
             return "pauli(%s)" % (list(self.qubits),)
-        if self.kind == "kraus":
-            return "kraus(%s, m=%d)" % (list(self.qubits), len(self.table))
+        if self.kind in ("kraus", "kraus2"):
+            return "%s(%s, m=%d)" % (self.kind, list(self.qubits), len(self.table))
         if self.kind == "init":
             return "init(mask=%#x)" % self.mask
         if self.kind == "swap":

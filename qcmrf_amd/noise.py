@@ -1,4 +1,4 @@
-"""Noise models with the names and conventions of ``qiskit_aer.noise``: Pauli and one-qubit Kraus channels.
+"""Noise models with the names and conventions of ``qiskit_aer.noise``: Pauli channels, one- and two-qubit Kraus channels.
 
     from qcmrf_amd.noise import NoiseModel, depolarizing_error, ReadoutError
     nm = NoiseModel()
@@ -21,9 +21,20 @@ its 4 x 4 superoperator (column-stacking: S = sum_k conj(K_k) (x) K_k) and, unle
 canonical Kraus set from the eigen-decomposition of its Choi matrix (at most four operators, descending eigenvalues).  A
 two-qubit error is an ordered list of terms, each a Pauli table on both qubits or a one-qubit channel on error qubit j:
 tensor products of one-qubit channels composed with two-qubit Pauli errors, which is how Aer's device models build
-their ``cx`` errors.  A general two-qubit Kraus set is refused.  On the device a channel term is one ``kraus`` op: per
-shot the kernel reduces the branch weights <psi|K_k^dg K_k|psi> over the trajectory's state, draws one k, applies K_k and
-renormalises (``qsv_noise.hip``).
+their ``cx`` errors.  On the device a channel term is one ``kraus`` op: per shot the kernel reduces the branch weights
+<psi|K_k^dg K_k|psi> over the trajectory's state, draws one k, applies K_k and renormalises (``qsv_noise.hip``).
+
+A general two-qubit channel is a third kind of term, one dense ``kraus2`` op of up to 16 operators of 4 x 4:
+
+    from qcmrf_amd.noise import two_qubit_kraus_error, coherent_unitary_error, mixed_unitary_error
+    zx = np.kron(X, Z)                                                    # Z on error qubit 0 (the control), X on error qubit 1
+    over = coherent_unitary_error(scipy.linalg.expm(-0.5j * 0.05 * zx))   # over-rotation of the cross-resonance pulse
+    nm.add_all_qubit_quantum_error(over.compose(depolarizing_error(1e-2, 2)), ["cx"])
+
+``two_qubit_kraus_error`` takes the operators, ``coherent_unitary_error`` one unitary (2 x 2 or 4 x 4), ``mixed_unitary_error``
+(unitary, probability) pairs.  Matrix index bit j is error qubit j (Aer's little-endian order: ``np.kron(A1, A0)`` has A0 on error
+qubit 0).  Such an error holds its 16 x 16 superoperator; composing it with anything else on the two qubits gives one dense term,
+the product of the superoperators, so a gate is followed by one record however its error was put together.
 
 Pauli index order (shared with the encoder ``program.encode`` and the kernel ``qsv_noise.hip``):
 index p of an n-qubit Pauli holds, for error qubit j, an x bit ``p >> 2j & 1`` and a z bit
@@ -74,20 +85,27 @@ def _superop_of_pauli(p):
     return sum(w * np.kron(P.conj(), P) for w, P in zip(p, _PAULIS))
 
 
+def _dim(S):
+    """2 for a one-qubit superoperator (4 x 4), 4 for a two-qubit one (16 x 16)"""
+    return 2 if S.shape[0] == 4 else 4
+
+
 def _choi(S):
-    """Choi matrix sum_k vec(K_k) vec(K_k)^dg (vec column-stacking) of a one-qubit superoperator"""
-    return S.reshape(2, 2, 2, 2).transpose(3, 1, 2, 0).reshape(4, 4)
+    """Choi matrix sum_k vec(K_k) vec(K_k)^dg (vec column-stacking) of a one- or two-qubit superoperator"""
+    d = _dim(S)
+    return S.reshape(d, d, d, d).transpose(3, 1, 2, 0).reshape(d * d, d * d)
 
 
 def _canonical_kraus(S):
-    """<= 4 Kraus operators from the eigen-decomposition of the Choi matrix, descending eigenvalues; eigenvalues below
-    1e-14 are dropped; each operator's phase is fixed by making its largest entry real and positive"""
+    """<= 4 (two qubits: <= 16) Kraus operators from the eigen-decomposition of the Choi matrix, descending eigenvalues;
+    eigenvalues below 1e-14 are dropped; each operator's phase is fixed by making its largest entry real and positive"""
+    d = _dim(S)
     lam, vec = np.linalg.eigh(_choi(S))
     out = []
     for i in np.argsort(-lam, kind="stable"):
         if lam[i] < _EIG_DROP:
             continue
-        k = np.sqrt(lam[i]) * vec[:, i].reshape(2, 2).T
+        k = np.sqrt(lam[i]) * vec[:, i].reshape(d, d).T
         big = k.ravel()[np.argmax(np.abs(k.ravel()))]
         out.append(k * (abs(big) / big))
     return out
@@ -102,18 +120,30 @@ def _check_cptp(S, what):
         raise ValueError("%s does not preserve the trace" % what)
 
 
+def _paulis2():
+    """the 16 two-qubit Paulis in Pauli index order: index p has error qubit 0 in its low two bits"""
+    return [np.kron(_PAULIS[p >> 2], _PAULIS[p & 3]) for p in range(16)]
+
+
+def _superop_of_pauli2(p):
+    return sum(w * np.kron(P.conj(), P) for w, P in zip(p, _paulis2()) if w)
+
+
 def _pauli_table_of(S):
-    """the four probabilities if the superoperator is a Pauli channel, else None"""
+    """the 4 (two qubits: 16) probabilities if the superoperator is a Pauli channel, else None"""
     C = _choi(S)
-    p = np.array([np.real(np.vdot(P.T.ravel(), C @ P.T.ravel())) / 4.0 for P in _PAULIS])
-    if np.abs(S - _superop_of_pauli(p)).max() > _TOL or (p < -_TOL).any():
+    two = _dim(S) == 4
+    group = _paulis2() if two else _PAULIS
+    p = np.array([np.real(np.vdot(P.T.ravel(), C @ P.T.ravel())) / float(len(group)) for P in group])
+    if np.abs(S - (_superop_of_pauli2(p) if two else _superop_of_pauli(p))).max() > _TOL or (p < -_TOL).any():
         return None
     p = np.clip(p, 0.0, None)
     return p / p.sum()
 
 
 class _Chan:
-    """a one-qubit channel: its superoperator and, when they were given, its Kraus operators"""
+    """a one-qubit channel (a "chan" term) or a dense two-qubit one (a "k2" term): its superoperator and, when they were
+    given, its Kraus operators"""
     __slots__ = ("S", "given")
 
     def __init__(self, S, given=None):
@@ -124,9 +154,27 @@ class _Chan:
         return list(self.given) if self.given is not None else _canonical_kraus(self.S)
 
 
+def _superop_of_term(kind, qs, x):
+    """the 16 x 16 superoperator of one term of a two-qubit error"""
+    if kind == "k2":
+        return x.S
+    if kind == "pauli":
+        return _superop_of_pauli2(x)
+    I2 = _PAULIS[0]
+    return sum(np.kron(k.conj(), k) for k in (np.kron(I2, k) if qs[0] == 0 else np.kron(k, I2) for k in x.kraus()))
+
+
 def _merge(terms):
     """ordered terms with adjacent terms of one shape on the same qubits merged (one-qubit channels on different qubits
-    commute, so a channel also merges with the last channel on its qubit across channels on the other one)"""
+    commute, so a channel also merges with the last channel on its qubit across channels on the other one).  A dense
+    two-qubit term takes everything else with it: the terms become one "k2" term, the product of their superoperators --
+    one record behind the gate instead of several; a single term keeps the operators it was given"""
+    terms = list(terms)
+    if len(terms) > 1 and any(kind == "k2" for kind, _, _ in terms):
+        S = np.eye(16, dtype=np.complex128)
+        for kind, qs, x in terms:
+            S = _superop_of_term(kind, qs, x) @ S
+        return [("k2", (0, 1), _Chan(S))]
     out = []
     for kind, qs, x in terms:
         if kind == "pauli":
@@ -157,8 +205,8 @@ def _convolve(p, q):
 
 class QuantumError:
     """An n-qubit error (n = 1 or 2).  ``QuantumError(probabilities, n)`` is a Pauli channel: ``probabilities[p]`` is the
-    chance of Pauli index p.  The constructors below and ``compose`` / ``tensor`` also give one-qubit Kraus channels and
-    two-qubit products of them (module docstring)."""
+    chance of Pauli index p.  The constructors below and ``compose`` / ``tensor`` also give one-qubit Kraus channels,
+    two-qubit products of them and dense two-qubit channels (module docstring)."""
 
     def __init__(self, probabilities, num_qubits):
         n = int(num_qubits)
@@ -175,7 +223,8 @@ class QuantumError:
         p.setflags(write=False)
         self._p = p
         self._n = n
-        self._chain = None            # non-Pauli errors: ordered ("pauli", (0, 1), table) / ("chan", (j,), _Chan) terms
+        self._chain = None            # non-Pauli errors: ordered ("pauli", (0, 1), table) / ("chan", (j,), _Chan) terms,
+                                      # or one ("k2", (0, 1), _Chan) term: a dense two-qubit channel
         self._emit = None
 
     @classmethod
@@ -214,7 +263,8 @@ class QuantumError:
     def is_ideal(self):
         if self._chain is None:
             return bool(self._p[0] >= 1.0 - _TOL)
-        return all(np.abs(x.S - np.eye(4)).max() <= _TOL if k == "chan" else x[0] >= 1.0 - _TOL for k, _, x in self._chain)
+        return all(np.abs(x.S - np.eye(x.S.shape[0])).max() <= _TOL if k in ("chan", "k2") else x[0] >= 1.0 - _TOL
+                   for k, _, x in self._chain)
 
     def to_dict(self):
         """{Qiskit label: probability} for the Paulis with non-zero probability"""
@@ -235,30 +285,27 @@ class QuantumError:
         if self._n == 1:
             return self._chan().S.copy()
         S = np.eye(16, dtype=np.complex128)
-        I2 = _PAULIS[0]
         for kind, qs, x in self._terms():
-            if kind == "pauli":
-                ks = [np.sqrt(w) * np.kron(_PAULIS[p >> 2], _PAULIS[p & 3]) for p, w in enumerate(x) if w > 0]
-            else:
-                ks = [np.kron(I2, k) if qs[0] == 0 else np.kron(k, I2) for k in x.kraus()]
-            S = sum(np.kron(k.conj(), k) for k in ks) @ S
+            S = _superop_of_term(kind, qs, x) @ S
         return S
 
     def terms(self):
-        """what ingest walks, in order: ("pauli", error qubits, probability table) or ("kraus", (error qubit,), stack of m
-        2 x 2 operators).  A one-qubit channel without given Kraus operators that is a Pauli channel comes as "pauli"."""
+        """what ingest walks, in order: ("pauli", error qubits, probability table), ("kraus", (error qubit,), stack of m
+        2 x 2 operators) or ("kraus2", (0, 1), stack of m 4 x 4 operators, index bit j on error qubit j).  A channel without
+        given Kraus operators that is a Pauli channel comes as "pauli"."""
         if self._emit is None:
             out = []
             for kind, qs, x in self._terms():
-                if kind == "chan":
+                if kind in ("chan", "k2"):
+                    d = _dim(x.S)
                     p = _pauli_table_of(x.S) if x.given is None else None
                     if p is not None:
                         p.setflags(write=False)
                         out.append(("pauli", qs, p))
                     else:
-                        ks = np.array(x.kraus(), dtype=np.complex128).reshape(-1, 2, 2)
+                        ks = np.array(x.kraus(), dtype=np.complex128).reshape(-1, d, d)
                         ks.setflags(write=False)
-                        out.append(("kraus", qs, ks))
+                        out.append(("kraus" if kind == "chan" else "kraus2", qs, ks))
                 else:
                     out.append((kind, qs, x))
             self._emit = tuple(out)
@@ -267,7 +314,8 @@ class QuantumError:
     def compose(self, other):
         """``other`` after ``self``.  Pauli tables convolve over the Pauli group (phases dropped); one-qubit channels
         multiply their superoperators (a Pauli table is lifted when it meets a non-Pauli partner); on two qubits the
-        ordered terms are concatenated and adjacent terms of one shape on the same qubits merged"""
+        ordered terms are concatenated and adjacent terms of one shape on the same qubits merged; with a dense two-qubit
+        term among them they all become one dense term, the product of the superoperators"""
         other = _as_error(other)
         if other.num_qubits != self._n:
             raise ValueError("cannot compose a %d-qubit error with a %d-qubit one" % (self._n, other.num_qubits))
@@ -321,14 +369,14 @@ def _as_error(e):
 
 def kraus_error(noise_ops):
     """a one-qubit channel from 1 to 4 Kraus operators (2 x 2), kept as given and in order; more than four are reduced
-    to the canonical set.  sum K^dg K must be the identity to 1e-12.  Two-qubit Kraus sets are refused: build a
-    two-qubit error as a tensor product of one-qubit channels, composed with two-qubit Pauli errors"""
+    to the canonical set.  sum K^dg K must be the identity to 1e-12.  4 x 4 operators are refused here: a general
+    two-qubit Kraus set goes to ``two_qubit_kraus_error``"""
     ks = [np.array(k, dtype=np.complex128) for k in noise_ops]
     if not ks:
         raise ValueError("kraus_error needs at least one operator")
     if any(k.shape == (4, 4) for k in ks):
-        raise ValueError("a general two-qubit Kraus set is not supported: only tensor products of one-qubit channels "
-                         "(a.tensor(b) / a.expand(b)), composed with two-qubit Pauli errors")
+        raise ValueError("kraus_error takes 2 x 2 operators: a general two-qubit Kraus set (4 x 4 operators) goes to "
+                         "two_qubit_kraus_error")
     if any(k.shape != (2, 2) for k in ks):
         raise ValueError("Kraus operators are 2 x 2 matrices, got shapes %s" % sorted({k.shape for k in ks}))
     if not all(np.all(np.isfinite(k)) for k in ks):
@@ -340,6 +388,81 @@ def kraus_error(noise_ops):
     for k in ks:
         k.setflags(write=False)
     return QuantumError._from_terms([("chan", (0,), _Chan(S, ks if len(ks) <= 4 else None))], 1)
+
+
+def two_qubit_kraus_error(noise_ops):
+    """a two-qubit channel from 1 or more Kraus operators (4 x 4), matrix index bit j on error qubit j -- the gate's j-th
+    qubit argument, Aer's little-endian order and the order of the two-qubit Pauli index.  Up to 16 operators are kept as
+    given and in order; more are reduced to the canonical set (Choi eigenvalues below 1e-14 dropped, at most 16,
+    descending).  sum K^dg K must be the identity to 1e-12."""
+    ks = [np.array(k, dtype=np.complex128) for k in noise_ops]
+    if not ks:
+        raise ValueError("two_qubit_kraus_error needs at least one operator")
+    if any(k.shape != (4, 4) for k in ks):
+        raise ValueError("two-qubit Kraus operators are 4 x 4 matrices, got shapes %s" % sorted({k.shape for k in ks}))
+    if not all(np.all(np.isfinite(k)) for k in ks):
+        raise ValueError("Kraus operators must be finite")
+    tp = sum(k.conj().T @ k for k in ks)
+    if np.abs(tp - np.eye(4)).max() > _TOL:
+        raise ValueError("not a channel: sum K^dg K differs from the identity by %.3g" % np.abs(tp - np.eye(4)).max())
+    S = _superop_of_kraus(ks)
+    for k in ks:
+        k.setflags(write=False)
+    return QuantumError._from_terms([("k2", (0, 1), _Chan(S, ks if len(ks) <= 16 else None))], 2)
+
+
+def _unitary(u, what):
+    u = np.array(u, dtype=np.complex128)
+    if u.shape not in ((2, 2), (4, 4)):
+        raise ValueError("%s is a 2 x 2 or 4 x 4 matrix, got shape %s" % (what, u.shape))
+    if not np.all(np.isfinite(u)) or np.abs(u.conj().T @ u - np.eye(len(u))).max() > _TOL:
+        raise ValueError("%s is not unitary to 1e-12" % what)
+    return u
+
+
+def coherent_unitary_error(unitary):
+    """the unitary error rho -> U rho U^dg on one (2 x 2) or two (4 x 4) qubits: a Kraus set of one operator"""
+    u = _unitary(unitary, "a coherent error")
+    return kraus_error([u]) if len(u) == 2 else two_qubit_kraus_error([u])
+
+
+def _pauli_index_of(u):
+    """the Pauli index of a unitary that is a Pauli up to a phase, else None"""
+    d = len(u)
+    for p, P in enumerate(_PAULIS if d == 2 else _paulis2()):
+        t = np.vdot(P, u) / d                              # tr(P^dg U) / d: modulus 1 only for a phase times P
+        if abs(abs(t) - 1.0) <= _TOL:
+            return p
+    return None
+
+
+def mixed_unitary_error(noise_ops):
+    """``mixed_unitary_error([(U_0, p_0), (U_1, p_1), ...])``: U_k with probability p_k, on one or two qubits.  The
+    probabilities are non-negative and sum to 1 to 1e-12; terms of probability 0 are dropped; K_k = sqrt(p_k) U_k, kept in
+    order up to 4 operators on one qubit and 16 on two, canonical beyond that.  Unitaries that are all Paulis (up to a
+    phase) make a Pauli error."""
+    pairs = [(_unitary(u, "a term of a mixed-unitary error"), float(p)) for u, p in noise_ops]
+    if not pairs:
+        raise ValueError("mixed_unitary_error needs at least one (unitary, probability) pair")
+    d = len(pairs[0][0])
+    if any(len(u) != d for u, _ in pairs):
+        raise ValueError("the unitaries of a mixed-unitary error differ in size")
+    ps = np.array([p for _, p in pairs])
+    if not np.all(np.isfinite(ps)) or (ps < 0).any():
+        raise ValueError("mixed-unitary probabilities must be finite and non-negative")
+    if abs(ps.sum() - 1.0) > _TOL:
+        raise ValueError("mixed-unitary probabilities sum to %.17g, not 1" % ps.sum())
+    pairs = [(u, p) for u, p in pairs if p > 0]
+    idx = [_pauli_index_of(u) for u, _ in pairs]
+    if all(i is not None for i in idx):
+        table = np.zeros(d * d)
+        for i, (_, p) in zip(idx, pairs):
+            table[i] += p
+        return QuantumError(table / table.sum(), 1 if d == 2 else 2)
+    ks = [np.sqrt(p) * u for u, p in pairs]
+    tp = sum(k.conj().T @ k for k in ks)                   # the identity up to the rounding of sum p: take it out
+    ks = [k / np.sqrt(np.real(np.trace(tp)) / d) for k in ks]
+    return kraus_error(ks) if d == 2 else two_qubit_kraus_error(ks)
 
 
 def phase_amplitude_damping_error(param_amp, param_phase, excited_state_population=0):

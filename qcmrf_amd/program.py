@@ -93,6 +93,16 @@ def encode(ops):
             if flat is None:
                 flat = kraus_seen[id(op.table)] = kraus_tables(ks)
             r["data_off"] = put_real(flat)
+        elif k == "kraus2":
+            ks = np.asarray(op.table, dtype=np.complex128)
+            if len(op.qubits) != 2 or op.qubits[0] == op.qubits[1]:
+                raise ValueError("a kraus2 op acts on two distinct qubits, got %r" % (tuple(op.qubits),))
+            r["kind"] = _lib.OP_KRAUS2
+            fill(r, op.qubits, [len(ks)])
+            flat = kraus_seen.get(id(op.table))                 # the E block once per distinct stack
+            if flat is None:
+                flat = kraus_seen[id(op.table)] = kraus2_tables(ks)
+            r["data_off"] = put_real(flat)
         elif k == "measure":
             c, release = int(op.mask), int(bool(op.vals[0])) if len(op.vals) else 0
             if not 0 <= c < 64:
@@ -136,6 +146,27 @@ def kraus_tables(ks):
     if np.abs(E.sum(axis=0) - np.eye(2)).max() > 1e-9:
         raise ValueError("the operators of a Kraus op do not sum to a channel (sum K^dg K != 1)")
     e = np.stack([E[:, 0, 0].real, E[:, 1, 1].real, E[:, 0, 1].real, E[:, 0, 1].imag], axis=1)
+    return np.concatenate([ks.view(np.float64).ravel(), e.ravel()])
+
+
+_K2_UPPER = ((0, 1), (0, 2), (0, 3), (1, 2), (1, 3), (2, 3))
+
+
+def kraus2_tables(ks):
+    """QSV_OP_KRAUS2 data: the m operators (4 x 4, row-major, re / im: 32 doubles each, matrix index bit j on qubits[j]),
+    then for each E_k = K_k^dg K_k 16 doubles: its 4 real diagonal entries, then its upper off-diagonal entries
+    (0,1) (0,2) (0,3) (1,2) (1,3) (2,3) as (re, im)"""
+    ks = np.ascontiguousarray(ks, dtype=np.complex128)
+    if ks.ndim != 3 or ks.shape[1:] != (4, 4) or not 1 <= len(ks) <= 16:
+        raise ValueError("a kraus2 op holds 1 to 16 operators of 4 x 4, got shape %s" % (ks.shape,))
+    E = np.einsum("kai,kaj->kij", ks.conj(), ks)
+    if np.abs(E.sum(axis=0) - np.eye(4)).max() > 1e-9:
+        raise ValueError("the operators of a kraus2 op do not sum to a channel (sum K^dg K != 1)")
+    e = np.empty((len(ks), 16))
+    e[:, :4] = np.einsum("kii->ki", E).real
+    for j, (a, b) in enumerate(_K2_UPPER):
+        e[:, 4 + 2 * j] = E[:, a, b].real
+        e[:, 5 + 2 * j] = E[:, a, b].imag
     return np.concatenate([ks.view(np.float64).ravel(), e.ravel()])
 
 

@@ -20,6 +20,10 @@ the gate when that is given too.  The circuits are then always lowered to {cx,id
 and the counts go to ``result_simulation_noisy_<SCALE>.json``.  ``--noisy-measure in_place`` (or ``auto``) takes the clique
 ancillas' measurements when they occur and recycles their qubits: n + 2 live qubits per shot instead of n + m + 1.
 
+``--coherent-cx EPS`` composes the coherent over-rotation exp(-i EPS/2 Z(x)X) of the cross-resonance pulse (Z on the control, X
+on the target: ``coherent_unitary_error``, one dense two-qubit Kraus record per ``cx``) onto the ``cx`` error of whatever model
+the other noise options build; with no other noise option it is the only error.
+
 ``--method density_matrix`` evolves every circuit exactly as a density matrix (noisy or not): the counts are drawn from the
 exact distributions, and those are written as well, one ``{bitstring: p}`` per circuit, to ``probs_simulation_<SCALE>.json``
 (``probs_simulation_noisy_<SCALE>.json`` for a noisy run).
@@ -57,6 +61,8 @@ def main(argv=None):
     ap.add_argument("--t1", type=float, default=None, metavar="US", help="T1 in microseconds (noisy run, with --t2 and --gate-time)")
     ap.add_argument("--t2", type=float, default=None, metavar="US", help="T2 in microseconds, at most 2 T1")
     ap.add_argument("--gate-time", default=None, metavar="NS1,NS2", help="duration of sx/x/id and of cx in nanoseconds")
+    ap.add_argument("--coherent-cx", type=float, default=None, metavar="EPS",
+                    help="coherent over-rotation exp(-i EPS/2 Z(x)X) after every cx, composed onto the cx error of the other options (noisy run)")
     ap.add_argument("--method", default=None, choices=["density_matrix"],
                     help="density_matrix: exact distributions (probs_simulation_*.json) next to the counts drawn from them")
     ap.add_argument("--noisy-measure", default=None, choices=["deferred", "in_place", "auto"],
@@ -66,7 +72,7 @@ def main(argv=None):
                     help="every shot from the branch in which all clique ancillas read 0; also writes the success probabilities "
                          "(exact; estimated from the attempts made when the run is noisy)")
     args = ap.parse_args(argv)
-    model = ibm_like_model(args.depolarizing, args.readout, args.t1, args.t2, args.gate_time)
+    model = ibm_like_model(args.depolarizing, args.readout, args.t1, args.t2, args.gate_time, args.coherent_cx)
 
     np.random.seed(1984)
     from scipy.stats import halfnorm
@@ -122,13 +128,20 @@ def main(argv=None):
     return counts
 
 
-def ibm_like_model(depolarizing=None, readout=None, t1=None, t2=None, gate_time=None):
-    """``--depolarizing P1,P2`` / ``--readout P`` / ``--t1 US --t2 US --gate-time NS1,NS2`` -> a NoiseModel (None when none
-    is given).  Thermal relaxation comes first on a gate, the depolarizing error is composed after it."""
+def cx_over_rotation(eps):
+    """exp(-i eps/2 Z(x)X) as a 4 x 4 matrix on the qubits of ``cx(c, t)``: Z on error qubit 0 (c), X on error qubit 1 (t)"""
+    zx = np.kron(np.array([[0, 1], [1, 0]], dtype=np.complex128), np.diag([1.0 + 0j, -1.0]))
+    return np.cos(0.5 * eps) * np.eye(4) - 1j * np.sin(0.5 * eps) * zx
+
+
+def ibm_like_model(depolarizing=None, readout=None, t1=None, t2=None, gate_time=None, coherent_cx=None):
+    """``--depolarizing P1,P2`` / ``--readout P`` / ``--t1 US --t2 US --gate-time NS1,NS2`` / ``--coherent-cx EPS`` -> a
+    NoiseModel (None when none is given).  Thermal relaxation comes first on a gate, the depolarizing error is composed
+    after it, the coherent over-rotation of ``cx`` after both."""
     thermal = [x is not None for x in (t1, t2, gate_time)]
     if any(thermal) and not all(thermal):
         raise ValueError("thermal relaxation needs all of --t1, --t2 and --gate-time")
-    if depolarizing is None and readout is None and not any(thermal):
+    if depolarizing is None and readout is None and not any(thermal) and coherent_cx is None:
         return None
     from .noise import NoiseModel, ReadoutError, depolarizing_error, thermal_relaxation_error
     nm = NoiseModel()
@@ -146,6 +159,9 @@ def ibm_like_model(depolarizing=None, readout=None, t1=None, t2=None, gate_time=
             raise ValueError("--depolarizing takes two numbers P1,P2, got %r" % (depolarizing,))
         nm.add_all_qubit_quantum_error(depolarizing_error(parts[0], 1), ["sx", "x", "id"])
         nm.add_all_qubit_quantum_error(depolarizing_error(parts[1], 2), ["cx"])
+    if coherent_cx is not None:
+        from .noise import coherent_unitary_error
+        nm.add_all_qubit_quantum_error(coherent_unitary_error(cx_over_rotation(float(coherent_cx))), ["cx"])
     if readout is not None:
         p = float(readout)
         nm.add_all_qubit_readout_error(ReadoutError([[1.0 - p, p], [p, 1.0 - p]]))
