@@ -10,6 +10,8 @@ Convention (include/qsv.h): rho of W qubits is the vector of a 2W-qubit engine, 
   DensityNumpyEngine      the three entry points on numpy: the stand-in engine of the host tests
   pair_program            W = 12, 13: entanglement confined to fixed disjoint pairs, so rho is a Kronecker product of 2 x 2 and
                           4 x 4 factors and the reference costs nothing
+  pair_program_k2         the same with KRAUS2 records inside the pairs (factors by ``_kraus2_reference.kraus2_rho``): the
+                          programs of test_gpu_density_forms.py at W = 6 .. 16, with the wrong references of its host tests
 """
 from __future__ import annotations
 
@@ -17,9 +19,11 @@ import functools
 
 import numpy as np
 
+import _kraus2_cases as k2c
 import _kraus_cases as kc
 import _noise_exact_cases as nc
 from _density_matrix import _gate_rows, _init_vector, _pauli_channel, _pauli_probs, _records, word_distribution
+from _kraus2_reference import kraus2_rho
 from _kraus_reference import _apply_2x2, kraus_of_record
 from _philox_reference import STREAM_SAMPLE, TOL, pick_basis_state, record_words, u01
 from qcmrf_amd import _lib, ir, program
@@ -299,3 +303,162 @@ def product_entries(factors, W, rows, cols):
 def product_diagonal(factors, W):
     i = np.arange(1 << W)
     return np.real(product_entries(factors, W, i, i))
+
+
+# ---- W = 6 .. 16: products of pair factors with KRAUS2 records ---------------------------------------------------------------
+
+# negative: counted from W.  (0, W - 1): bra bits W and 2W - 1; an adjacent low pair; where W allows (W <= 11) a qubit whose bra
+# bit is address bit 11: qubit 5 at W = 6, qubit 4 at W = 7, qubit 0 at W = 11
+K2_PAIRS = {6: ((0, -1), (2, 3), (4, 1)), 7: ((0, -1), (5, 2), (1, 4)), 11: ((0, -1), (5, 6), (2, 8)), 13: PAIRS, 14: PAIRS,
+            16: ((0, -1), (5, 6))}
+K2_SEED = 1600
+# ways the engine could be wrong that the comparison with the factors must see (``wrong``; the program stays the true one):
+# the first KRAUS2 record of the pair (0, W - 1) with its two qubits swapped, every Kraus operator conjugated, rho transposed
+# (ket and bra exchanged), the factor of the pair (0, W - 1) left without its channels
+K2_WRONG = ("swapped", "conjugated", "transposed", "no_channel")
+CHANNELS = ("pauli", "kraus", "kraus2")
+
+
+def _wrong_records(sub, wrong, n):
+    if wrong == "swapped" and n == 0:
+        i = next(i for i, o in enumerate(sub) if o.kind == "kraus2")
+        sub = sub[:i] + [k2c.kraus2_op(sub[i].qubits[1], sub[i].qubits[0], sub[i].table)] + sub[i + 1:]
+    elif wrong == "conjugated":
+        sub = [ir.Op(o.kind, qubits=o.qubits, table=o.table.conj()) if o.kind in ("kraus", "kraus2") else o for o in sub]
+    elif wrong == "no_channel" and n == 0:
+        sub = [o for o in sub if o.kind not in CHANNELS]
+    return sub
+
+
+def pair_program_k2(W, pairs, seed, short=False, wrong=None):
+    """(ops, factors) as ``pair_program``, from |+>^W (an INIT_UNIFORM record: every entry of rho has weight before the first
+    gate), with KRAUS2 records inside the pairs: on (q0, q1), on (q1, q0) and on (q0, q1) again, cycling through the stacks
+    of ``_kraus2_cases.menu`` (three pairs: all eight, m = 16 and the correlated damping sets included), two-qubit PAULI in
+    both orders, one-qubit KRAUS of m = 1..4 and PAULI records, the entangling gates of ``pair_program``.
+    ``short``: at most 16 records for the widths where a record is a sweep of many GiB -- gates on the paired qubits only,
+    one KRAUS2 (the first of one operator, the second of two) and one two-qubit PAULI per pair, a one-qubit KRAUS and a
+    PAULI on each qubit of the first pair.  ``wrong`` (one of K2_WRONG) changes the factors alone."""
+    if wrong is not None and wrong not in K2_WRONG:
+        raise ValueError("unknown wrong reference %r" % (wrong,))
+    rng = np.random.RandomState(seed)
+    stacks = k2c.menu(rng)
+    pairs = [tuple(q % W for q in p) for p in pairs]
+    paired = {q for p in pairs for q in p}
+    assert len(paired) == 2 * len(pairs)
+    groups = pairs + [(q,) for q in range(W) if q not in paired]
+    n_k2 = [0]
+
+    def k2(a, b):
+        st = stacks[n_k2[0] % len(stacks)]
+        n_k2[0] += 1
+        return lambda q: k2c.kraus2_op(q[a], q[b], st)
+
+    def pauli(n_qubits, *js):
+        t = 0.3 * rng.dirichlet(np.ones(4 ** n_qubits))             # generic, the identity at 0.7 and more: as noise is, and a
+        t[0] += 1.0 - t.sum()                                       # wrong record elsewhere is not depolarised out of sight
+        return lambda q: ir.Op("pauli", qubits=tuple(q[j] for j in js), table=t)
+
+    per, factors = [], []
+    for n, g in enumerate(groups):
+        k = len(g)
+        mk = []                                                     # each record as a function of the group's qubits
+        if k == 2 or not short:
+            for j in range(k):
+                mk.append(lambda q, j=j, u=nc._unitary(rng): ir.op_u(q[j], u))
+        if k == 2:
+            mk.append(lambda q: ir.op_x(q[1], [q[0]], [1]))
+            mk.append(k2(0, 1))
+            mk.append(pauli(2, 1, 0))
+            if not short:
+                mk.append(lambda q, u=nc._unitary(rng): ir.op_u(q[0], u))
+                mk.append(lambda q: ir.op_x(q[0], [q[1]], [0]))
+                mk.append(k2(1, 0))
+                mk.append(pauli(2, 0, 1))
+                mk.append(k2(0, 1))
+        if short and n == 0:
+            for j in (1, 0):
+                mk.append(lambda q, j=j, ks=kc.isometry_kraus(rng, 2 + 2 * j): kc.kraus_op(q[j], ks))
+                mk.append(pauli(1, 1 - j))
+        elif not short:
+            for j in range(k):
+                mk.append(lambda q, j=j, ks=kc.isometry_kraus(rng, 1 + (n + j) % 4): kc.kraus_op(q[j], ks))
+            if n % 3 == 0:
+                mk.append(pauli(1, k - 1))
+        sub = _wrong_records([ir.op_init((1 << k) - 1)] + [f(list(range(k))) for f in mk], wrong, n)
+        rec, data = program.encode(sub)
+        fac = kraus2_rho(rec, data, k)
+        factors.append((g, fac.T.copy() if wrong == "transposed" else fac))
+        per.append([f(g) for f in mk])
+    order = rng.permutation(len(groups))                            # interleave the groups, the order inside a group kept
+    out = [ir.op_init((1 << W) - 1)]
+    while any(per):
+        for gi in order:
+            if per[gi]:
+                out.append(per[gi].pop(0))
+    return out, factors
+
+
+@functools.lru_cache(maxsize=None)
+def k2_case(W, short=False, seed=None):
+    """dict(W, ops, rec, data, factors) of ``pair_program_k2(W, K2_PAIRS[W], K2_SEED + W)``: made once, shared, left unchanged"""
+    ops, factors = pair_program_k2(W, K2_PAIRS[W], K2_SEED + W if seed is None else seed, short)
+    rec, data = program.encode(ops)
+    for _, f in factors:
+        f.setflags(write=False)
+    return dict(W=W, ops=ops, rec=rec, data=data, factors=factors)
+
+
+def k2_wrong_factors(W, wrong, short=False):
+    return pair_program_k2(W, K2_PAIRS[W], K2_SEED + W, short, wrong)[1]
+
+
+def column_set(W):
+    """the columns rho[:, j] the wide tests read: j = 0, 2^W - 1, every single bit (each bra bit of the address both ways, the
+    top one -- address bit 2W - 1 -- included) and 16 seeded random j"""
+    rng = np.random.RandomState(4000 + W)
+    return [0, (1 << W) - 1] + [1 << b for b in range(W)] + [int(j) for j in rng.randint(1 << W, size=16)]
+
+
+def product_columns(factors, W, cols):
+    """(len(cols), 2^W): row c is rho[:, cols[c]], what ``amplitudes(cols[c] << W, 1 << W)`` reads"""
+    return product_entries(factors, W, np.arange(1 << W)[None, :], np.asarray(cols, dtype=np.int64)[:, None])
+
+
+def product_vector(factors, W, block=64):
+    """the engine's whole vector (v = i | (j << W)) of the Kronecker product, built column block by column block"""
+    N = 1 << W
+    out = np.empty(N * N, dtype=np.complex128)
+    for lo in range(0, N, block):
+        out[lo * N:(lo + block) * N] = product_columns(factors, W, np.arange(lo, min(N, lo + block))).reshape(-1)
+    return out
+
+
+@functools.lru_cache(maxsize=None)
+def k2_vector(W):
+    """the reference vector of ``k2_case(W)``: computed once, shared, left unchanged (64 MiB at W = 11)"""
+    v = product_vector(k2_case(W)["factors"], W)
+    v.setflags(write=False)
+    return v
+
+
+# ---- sampling past the grid cap of the per-shot kernel (4096 workgroups of 256 threads = 2^20 shots) ---------------------------
+
+def big_sample_case():
+    """W = 2: a short noisy program, 2^20 + 777 shots, a seed above 2^32, a permuted register with an unused bit, readout errors"""
+    rng = np.random.RandomState(2020)
+    ops = [ir.op_u(0, nc._unitary(rng)), ir.op_u(1, nc._unitary(rng)), ir.op_x(1, [0], [1]),
+           k2c.kraus2_op(1, 0, k2c.isometry_kraus2(rng, 2)), nc._pauli(rng, [0, 1]), kc.kraus_op(1, kc.isometry_kraus(rng, 2))]
+    rec, data = program.encode(ops)
+    ro = np.array([[0.03, 0.05], [0.2, 0.1], [0.0, 0.07]])
+    return dict(W=2, rec=rec, data=data, shots=2 ** 20 + 777, seed=2 ** 35 + 5, meas=[1, -1, 0], readout=ro)
+
+
+@functools.lru_cache(maxsize=None)
+def big_sample_reference():
+    """(case, words, alt_words, ambiguous, diagonal): computed once, shared, left unchanged"""
+    c = big_sample_case()
+    diag = np.real(np.diag(kraus2_rho(c["rec"], c["data"], c["W"])))
+    ref = exact_density_sample(diag, c["shots"], c["seed"], c["meas"], c["readout"]) + (diag,)
+    for a in ref:
+        a.setflags(write=False)
+    return (c,) + ref
