@@ -227,6 +227,18 @@ int qsv_sample(qsv_handle* h, uint64_t shots, uint64_t seed, const int* meas_qub
 int qsv_sample_cond(qsv_handle* h, uint64_t shots, uint64_t seed, const int* meas_qubits, int n_meas,
                     uint64_t fix_mask, uint64_t fix_val, uint64_t* out_bits, double* mass);
 
+/* qsv_sample and qsv_sample_cond for callers that only count outcomes.  Same arguments.  out_bits receives exactly the
+ * multiset of words the ordered call returns for the same handle state, shots, seed and measurement map; the ORDER is
+ * unspecified (today: ascending in the walk's order, the Fisher-Yates shuffle is neither drawn nor applied, and the words
+ * are copied from the device straight into out_bits, one host wait as before).  Everything else is the ordered call's:
+ * the errors and their text (zero norm, bad qubit, zero mass; out_bits is then undefined), *mass, and the effects on the
+ * handle -- qsv_state_info (deferred, realize_calls, listed_launches), the cached sums, the stats.  Callers that hand
+ * shots out one by one, in order, keep the ordered calls. */
+int qsv_sample_unordered(qsv_handle* h, uint64_t shots, uint64_t seed, const int* meas_qubits,
+                         int n_meas, uint64_t* out_bits);
+int qsv_sample_cond_unordered(qsv_handle* h, uint64_t shots, uint64_t seed, const int* meas_qubits, int n_meas,
+                              uint64_t fix_mask, uint64_t fix_val, uint64_t* out_bits, double* mass);
+
 /* copy amplitudes [start, start+count) of the GLOBAL index space into out (2*count doubles);
  * the range must lie inside shards owned by this process. */
 int qsv_get_amplitudes(qsv_handle* h, uint64_t start, uint64_t count, double* out);

@@ -84,6 +84,8 @@ SIGNATURES = {
     "qsv_expect_diag": (_i, [_vp, _ip, _i, _dp, _u64, _u64, _dp]),
     "qsv_sample": (_i, [_vp, _u64, _u64, _ip, _i, _u64p]),
     "qsv_sample_cond": (_i, [_vp, _u64, _u64, _ip, _i, _u64, _u64, _u64p, _dp]),
+    "qsv_sample_unordered": (_i, [_vp, _u64, _u64, _ip, _i, _u64p]),
+    "qsv_sample_cond_unordered": (_i, [_vp, _u64, _u64, _ip, _i, _u64, _u64, _u64p, _dp]),
     "qsv_get_amplitudes": (_i, [_vp, _u64, _u64, _dp]),
     "qsv_set_amplitudes": (_i, [_vp, _u64, _u64, _dp]),
     "qsv_copy_state": (_i, [_vp, _vp]),
@@ -471,25 +473,40 @@ class Engine:
         _chk(self._lib.qsv_norm(self._h, C.byref(v)))
         return v.value
 
-    def sample(self, shots, seed, meas_qubits=None):
+    def _sample(self, fn, shots, seed, meas_qubits):
         out = np.zeros(int(shots), dtype=np.uint64)
         if meas_qubits is None:
-            _chk(self._lib.qsv_sample(self._h, int(shots), int(seed), None, 0, out.ctypes.data_as(_u64p)))
+            _chk(fn(self._h, int(shots), int(seed), None, 0, out.ctypes.data_as(_u64p)))
         else:
             qa, qp = _ia(meas_qubits)
-            _chk(self._lib.qsv_sample(self._h, int(shots), int(seed), qp, len(qa), out.ctypes.data_as(_u64p)))
+            _chk(fn(self._h, int(shots), int(seed), qp, len(qa), out.ctypes.data_as(_u64p)))
         return out
+
+    def sample(self, shots, seed, meas_qubits=None):
+        return self._sample(self._lib.qsv_sample, shots, seed, meas_qubits)
+
+    def sample_unordered(self, shots, seed, meas_qubits=None):
+        """the words of ``sample`` for the same state, shots, seed and map as a multiset, in no particular order
+        (qsv_sample_unordered): for callers that count them"""
+        return self._sample(self._lib.qsv_sample_unordered, shots, seed, meas_qubits)
+
+    def _sample_cond(self, fn, shots, seed, meas_qubits, fix_mask, fix_val):
+        out = np.zeros(int(shots), dtype=np.uint64)
+        mass = C.c_double(0.0)
+        qa, qp = (None, None) if meas_qubits is None else _ia(meas_qubits)
+        _chk(fn(self._h, int(shots), int(seed), qp, 0 if qa is None else len(qa), int(fix_mask), int(fix_val),
+                out.ctypes.data_as(_u64p), C.byref(mass)))
+        return out, mass.value
 
     def sample_cond(self, shots, seed, meas_qubits=None, fix_mask=0, fix_val=0):
         """post-selected shots: ``shots`` words drawn from |amp|^2 over the basis states g with (g & fix_mask) == fix_val
         (global index bits), and the mass of those states (not normalised by ``norm()``).  shots = 0: the mass only.
         ValueError where that mass is 0 and shots are asked for (qsv_sample_cond)."""
-        out = np.zeros(int(shots), dtype=np.uint64)
-        mass = C.c_double(0.0)
-        qa, qp = (None, None) if meas_qubits is None else _ia(meas_qubits)
-        _chk(self._lib.qsv_sample_cond(self._h, int(shots), int(seed), qp, 0 if qa is None else len(qa), int(fix_mask), int(fix_val),
-                                       out.ctypes.data_as(_u64p), C.byref(mass)))
-        return out, mass.value
+        return self._sample_cond(self._lib.qsv_sample_cond, shots, seed, meas_qubits, fix_mask, fix_val)
+
+    def sample_cond_unordered(self, shots, seed, meas_qubits=None, fix_mask=0, fix_val=0):
+        """``sample_cond`` with the words in no particular order (qsv_sample_cond_unordered); the mass is the same"""
+        return self._sample_cond(self._lib.qsv_sample_cond_unordered, shots, seed, meas_qubits, fix_mask, fix_val)
 
     def amplitudes(self, start=0, count=None):
         if count is None:

@@ -121,6 +121,52 @@ def _format_keys(values, counts, num_clbits, creg_sizes):
     return dict(zip(keys, counts.tolist()))
 
 
+try:
+    from . import _counts_native          # built by qcmrf_amd.build next to libqsv.so; absent where Python's headers are missing
+except Exception:                         # not built, or does not load here: counts are sorted and formatted in Python (same dict)
+    _counts_native = None
+_native_counts = _counts_native.counts_dict if _counts_native is not None else None
+
+
+def native_counts_available():
+    """the native counts formatter was built and loads"""
+    return _counts_native is not None
+
+
+def use_native_counts(on=True):
+    """force the switch: sampled words become the count dict in the native formatter (``on``; RuntimeError where it is not
+    available) or through ``np.unique`` and ``_format_keys``.  Returns the previous setting.  The default is on wherever
+    the module imports.  Either way the dict is the same, insertion order included."""
+    global _native_counts
+    was = _native_counts is not None
+    if on and _counts_native is None:
+        raise RuntimeError("qcmrf_amd._counts_native is not built or does not import (python -m qcmrf_amd.build)")
+    _native_counts = _counts_native.counts_dict if on else None
+    return was
+
+
+def _counts_path_default():
+    """metadata ``counts_path`` of a run that had no words to count: what the switch says"""
+    return "native" if _native_counts is not None else "python"
+
+
+def _counts_of(words, weights, num_clbits, creg_sizes):
+    """(the count dict of ``words``, the path that built it): keys in ascending order of the words, a word's count the
+    number of times it occurs, or the sum of its ``weights`` (int64, one per word) where those are given.  The native
+    formatter where it is on and takes the input (it answers None and decides nothing otherwise), else ``_format_keys``."""
+    if _native_counts is not None:
+        got = _native_counts(words, weights, num_clbits, creg_sizes)
+        if got is not None:
+            return got, "native"
+    if weights is None:
+        uv, uc = np.unique(words, return_counts=True)
+    else:
+        # the same word can come from several parts
+        uv, inv = np.unique(words, return_inverse=True)
+        uc = np.bincount(inv, weights=weights, minlength=uv.size).astype(np.int64) if uv.size != words.size else weights[np.argsort(words, kind="stable")]
+    return _format_keys(uv, uc, num_clbits, creg_sizes), "python"
+
+
 class QsvBackend:
     """MI355X statevector backend.  Options (constructor or per ``run`` call):
 
@@ -515,6 +561,7 @@ class QsvBackend:
         t1 = time.perf_counter()
         t0 = t1 - t_compile
         counts = {}
+        counts_path = _counts_path_default()
         t2 = t1
         fix = None if accept is None else self._accept_mask(accept, ing)
         accept_meta = {} if fix is None else {"accept": dict(accept), "accept_attempts": 0, "accept_probability": None}
@@ -535,13 +582,12 @@ class QsvBackend:
                 sample = eng.noisy_sample_hbm if state == "hbm" else eng.noisy_sample
                 bits = sample(rec, data, shots, seed, meas, readout if ing.readout else None)
             t2 = time.perf_counter()
-            uv, uc = np.unique(bits, return_counts=True)
-            counts = _format_keys(uv, uc, ing.num_clbits, ing.creg_sizes)
+            counts, counts_path = _counts_of(bits, None, ing.num_clbits, ing.creg_sizes)
         t3 = time.perf_counter()
         meta = {"method": "noisy", "noisy_state": state, "noisy_measure": nmeasure, "n_qubits": width,
                 "n_circuit_qubits": ing.num_qubits, "n_measure_ops": n_measure, "n_source_ops": ing.n_source_ops, "n_device_ops": len(rec),
                 "n_pauli_ops": ing.n_pauli, "n_kraus_ops": ing.n_kraus, "n_kraus2_ops": ing.n_kraus2, "readout_errors": len(ing.readout), "time_compile": t1 - t0,
-                "time_evolve": t2 - t1, "time_sample": t3 - t2, "time_taken": t3 - t0, "seed_simulator": seed}
+                "time_evolve": t2 - t1, "time_sample": t3 - t2, "time_taken": t3 - t0, "seed_simulator": seed, "counts_path": counts_path}
         meta.update(accept_meta)
         self.last_engine = None          # no resident state: every shot had its own
         self.last_plan = None
@@ -646,18 +692,19 @@ class QsvBackend:
             words |= ((keep.astype(np.uint64) >> np.uint64(j)) & np.uint64(1)) << np.uint64(c)
         probs = dict(zip(_format_keys(words, np.arange(keep.size), ing.num_clbits, ing.creg_sizes).keys(), dist[keep].tolist())) if clist else {}
         counts = {}
+        counts_path = _counts_path_default()
         if clist and shots > 0 and accept is not None:
             drawn = np.random.default_rng(seed).multinomial(shots, dist[keep])
             counts = _format_keys(words[drawn > 0], drawn[drawn > 0], ing.num_clbits, ing.creg_sizes)
+            counts_path = "python"
         elif clist and shots > 0:
             bits = eng.density_sample(shots, seed, meas, readout if ing.readout else None)
-            uv, uc = np.unique(bits, return_counts=True)
-            counts = _format_keys(uv, uc, ing.num_clbits, ing.creg_sizes)
+            counts, counts_path = _counts_of(bits, None, ing.num_clbits, ing.creg_sizes)
         t3 = time.perf_counter()
         meta = {"method": "density_matrix", "n_qubits": W, "n_source_ops": ing.n_source_ops, "n_device_ops": len(rec),
                 "n_pauli_ops": ing.n_pauli, "n_kraus_ops": ing.n_kraus, "n_kraus2_ops": ing.n_kraus2, "readout_errors": len(ing.readout), "trace": float(trace),
                 "state_bytes": state_bytes, "time_compile": t1 - t0, "time_evolve": t2 - t1, "time_sample": t3 - t2,
-                "time_taken": t3 - t0, "seed_simulator": seed}
+                "time_taken": t3 - t0, "seed_simulator": seed, "counts_path": counts_path}
         meta.update(accept_meta)
         self.last_engine = None          # the resident vector is rho, not a state: statevector() has nothing to show
         self.last_plan = None
@@ -783,18 +830,22 @@ class QsvBackend:
             meas_phys = [pl.layout[ing.measure[c]] for c in clist]
             direct = False
         counts = {}
+        counts_path = _counts_path_default()
         post_meta = {}
+        # the words are only counted here: the draws without the shuffle (qsv_sample_unordered, the same multiset); an engine
+        # that has only the ordered calls is asked for those
+        draw = getattr(eng, "sample_unordered", None) or eng.sample
         if fix is not None:
             # every shot from the state conditioned on the fixed bits (qsv_sample_cond): the words keep their full width,
             # the fixed bits reading their values; the mass of the condition over the norm is its exact probability
+            draw_cond = getattr(eng, "sample_cond_unordered", None) or eng.sample_cond
             before = eng.state_info()
-            words, mass = eng.sample_cond(max(shots, 0) if clist else 0, seed, meas_phys, fix[0], fix[1])
+            words, mass = draw_cond(max(shots, 0) if clist else 0, seed, meas_phys, fix[0], fix[1])
             after = eng.state_info()
             if not mass > 0:
                 raise ValueError("post-selected outcome %r has zero probability" % (post_select,))
             if clist and shots > 0:
-                uv, uc = np.unique(self._to_clbits(words, clist, direct), return_counts=True)
-                counts = _format_keys(uv, uc, ing.num_clbits, ing.creg_sizes)
+                counts, counts_path = _counts_of(self._to_clbits(words, clist, direct), None, ing.num_clbits, ing.creg_sizes)
             post_meta = {"post_select": dict(post_select), "post_select_probability": mass / eng.norm(),
                          "post_select_path": "stored" if not before["deferred"] else
                                              "realized" if after["realize_calls"] > before["realize_calls"] else "listed"}
@@ -812,7 +863,7 @@ class QsvBackend:
                                     else comm.allgather(eng.norm()), dtype=np.float64)
                 split = np.random.RandomState(seed % (2 ** 32)).multinomial(shots, masses / masses.sum())
                 k = int(split[comm.rank])
-                mine = eng.sample(k, (seed * 1315423911 + comm.rank) % (2 ** 63), meas_phys) if k else np.zeros(0, dtype=np.uint64)
+                mine = draw(k, (seed * 1315423911 + comm.rank) % (2 ** 63), meas_phys) if k else np.zeros(0, dtype=np.uint64)
                 uv, uc = np.unique(self._to_clbits(mine, clist, direct), return_counts=True)
                 pairs = np.concatenate([uv, uc.astype(np.uint64)])
                 everyone = opts.get("gather_counts", "root") == "all"
@@ -824,21 +875,19 @@ class QsvBackend:
                     parts = [np.frombuffer(b, dtype=np.uint64) for b in raw]
                     av = np.concatenate([b[:b.size // 2] for b in parts])
                     ac = np.concatenate([b[b.size // 2:] for b in parts]).astype(np.int64)
-                    # shards that differ only in an unmeasured qubit can produce the same outcome
-                    uv, inv = np.unique(av, return_inverse=True)
-                    uc = np.bincount(inv, weights=ac, minlength=uv.size).astype(np.int64) if uv.size != av.size else ac[np.argsort(av, kind="stable")]
-                    counts = _format_keys(uv, uc, ing.num_clbits, ing.creg_sizes)
+                    # shards that differ only in an unmeasured qubit can produce the same outcome: their counts are summed
+                    counts, counts_path = _counts_of(av, ac, ing.num_clbits, ing.creg_sizes)
             else:
-                vals = self._to_clbits(eng.sample(shots, seed, meas_phys), clist, direct)
-                uv, uc = np.unique(vals, return_counts=True)
-                counts = _format_keys(uv, uc, ing.num_clbits, ing.creg_sizes)
+                vals = self._to_clbits(draw(shots, seed, meas_phys), clist, direct)
+                counts, counts_path = _counts_of(vals, None, ing.num_clbits, ing.creg_sizes)
         elif shots > 0:
             counts = {}
         t3 = time.perf_counter()
         meta = {"n_qubits": ing.num_qubits, "n_source_ops": ing.n_source_ops, "n_device_ops": len(pl.ops),
                 "n_exchanges": pl.n_exchanges, "n_shards": n_shards, "layout": list(pl.layout),
                 "fusion": opts["fusion"], "time_compile": t1 - t0, "time_evolve": t2 - t1,
-                "time_sample": t3 - t2, "time_taken": t3 - t0, "seed_simulator": seed, "ingest_path": ing.ingest_path}
+                "time_sample": t3 - t2, "time_taken": t3 - t0, "seed_simulator": seed, "ingest_path": ing.ingest_path,
+                "counts_path": counts_path}
         meta.update(post_meta)
         if comm.world > 1 and opts.get("gather_counts", "root") != "all":
             meta["counts_on_rank"] = 0

@@ -1,4 +1,4 @@
-"""Build libqsv.so for gfx950 and the host-only ingest reader in-tree:  python -m qcmrf_amd.build [--force]"""
+"""Build libqsv.so for gfx950 and the host-only modules (ingest reader, counts formatter) in-tree:  python -m qcmrf_amd.build [--force]"""
 from __future__ import annotations
 
 import os
@@ -16,10 +16,15 @@ DEPENDS = SOURCES + ["qsv_common.h", "qsv_kernels.h", "qsv_kmulti.h", "qsv_kmult
 CFLAGS = ["-O3", "--offload-arch=gfx950", "-std=c++17", "-fPIC", "-munsafe-fp-atomics",
           "-Wno-unused-value", "-Wno-unused-result"]
 OBJDIR = os.path.join(CSRC, "_obj")
-# the native reader of clique-block signatures (qcmrf_amd.ingest): host C++ against Python's own headers, no HIP in it
-EXT_SOURCES = ["ingest_native.cpp"]
-EXT_OUT = os.path.join(HERE, "_ingest_native" + (sysconfig.get_config_var("EXT_SUFFIX") or ".so"))
+# host-only CPython modules next to libqsv.so (host C++ against Python's own headers, no HIP in them):
+# (module, sources, what Python does in its place where the module cannot be built)
+EXT_MODULES = [("_ingest_native", ["ingest_native.cpp"], "ingest reads blocks in Python"),         # reader of clique-block signatures (qcmrf_amd.ingest)
+               ("_counts_native", ["counts_native.cpp"], "counts are sorted and formatted in Python")]   # sampled words -> count dict (qcmrf_amd.backend)
 EXT_CFLAGS = ["-O2", "-std=c++17", "-fPIC", "-fvisibility=hidden", "-fno-exceptions", "-fno-rtti", "-Wall"]
+
+
+def ext_out(name):
+    return os.path.join(HERE, name + (sysconfig.get_config_var("EXT_SUFFIX") or ".so"))
 
 
 def _newer(out, deps):
@@ -34,43 +39,52 @@ def lib_stale():
 
 
 def ext_stale():
-    return _newer(EXT_OUT, EXT_SOURCES)
+    return any(_newer(ext_out(name), sources) for name, sources, _ in EXT_MODULES)
 
 
 def stale():
     return lib_stale() or ext_stale()
 
 
-def build_ext(verbose=True):
-    """_ingest_native: one host compile and link.  Returns its path, or None where it cannot be built (no host C++
-    compiler, no Python headers): ingest then reads the blocks in Python, so that is not an error."""
+def build_ext(verbose=True, force=True):
+    """the host-only modules (EXT_MODULES): one host compile and link each.  Returns the paths of the ones that stand
+    built; a module that cannot be built (no host C++ compiler, no Python headers) is left out and its work stays in
+    Python, so that is not an error."""
     include = sysconfig.get_paths()["include"]
-    if not os.path.exists(os.path.join(include, "Python.h")):
-        if verbose:
-            print("[qcmrf_amd.build] no Python.h under %s: _ingest_native not built, ingest reads blocks in Python" % include, flush=True)
-        return None
+    have_headers = os.path.exists(os.path.join(include, "Python.h"))
     cxx = os.environ.get("CXX", "c++")
-    tmp = EXT_OUT + ".tmp%d" % os.getpid()
-    cmd = [cxx] + EXT_CFLAGS + ["-I" + include, "-shared", "-o", tmp] + EXT_SOURCES
-    if verbose:
-        print("[qcmrf_amd.build]", " ".join(cmd), flush=True)
-    try:
-        subprocess.check_call(cmd, cwd=CSRC)
-        os.replace(tmp, EXT_OUT)
-    except (OSError, subprocess.CalledProcessError) as e:
+    built = []
+    for name, sources, instead in EXT_MODULES:
+        out = ext_out(name)
+        if not force and not _newer(out, sources):
+            built.append(out)
+            continue
+        if not have_headers:
+            if verbose:
+                print("[qcmrf_amd.build] no Python.h under %s: %s not built, %s" % (include, name, instead), flush=True)
+            continue
+        tmp = out + ".tmp%d" % os.getpid()
+        cmd = [cxx] + EXT_CFLAGS + ["-I" + include, "-shared", "-o", tmp] + sources
         if verbose:
-            print("[qcmrf_amd.build] _ingest_native not built (%s): ingest reads blocks in Python" % e, flush=True)
-        if os.path.exists(tmp):
-            os.remove(tmp)
-        return None
-    return EXT_OUT
+            print("[qcmrf_amd.build]", " ".join(cmd), flush=True)
+        try:
+            subprocess.check_call(cmd, cwd=CSRC)
+            os.replace(tmp, out)
+        except (OSError, subprocess.CalledProcessError) as e:
+            if verbose:
+                print("[qcmrf_amd.build] %s not built (%s): %s" % (name, e, instead), flush=True)
+            if os.path.exists(tmp):
+                os.remove(tmp)
+            continue
+        built.append(out)
+    return built
 
 
 def build(force=False, verbose=True):
     """one object per translation unit, compiled side by side (the k_multi instantiations are most of
-    the work: qsv_kmulti_inst.h), then one link; next to it the ingest reader (build_ext)"""
+    the work: qsv_kmulti_inst.h), then one link; next to it the host-only modules (build_ext)"""
     if force or ext_stale():
-        build_ext(verbose)
+        build_ext(verbose, force)
     if not force and not lib_stale():
         return OUT
     from concurrent.futures import ThreadPoolExecutor

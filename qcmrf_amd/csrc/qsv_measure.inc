@@ -99,8 +99,9 @@ extern "C" int qsv_norm(qsv_handle* h, double* out) {
 // super sums, their walk (k_walk_super) and every later step stay on the device, the host draws the spacings while the
 // first two kernels run and waits once, for the words and the total.  A deferred shard's shots are located inside the
 // generator (QSV_GEN_LOCATE): no tile is stored.  The arithmetic is that of qsv_sample's host walk, operation for operation:
-// the same words come out.
-static int sample_chain(qsv_handle* h, Shard& sh, uint64_t shots, uint64_t seed, const MeasMap& mm, uint64_t* out_bits) {
+// the same words come out.  shuffle false (qsv_sample_unordered): the words land in out_bits as the device leaves them,
+// ascending in the walk's order; the shuffle's random numbers are not drawn.
+static int sample_chain(qsv_handle* h, Shard& sh, uint64_t shots, uint64_t seed, const MeasMap& mm, bool shuffle, uint64_t* out_bits) {
   const uint64_t nsuper = (sh.tile_nblocks + QSV_SUPER - 1) / QSV_SUPER;
   CHK(super_sums(sh, nsuper));
   if (!(sh.d_super_valid & 2)) {
@@ -155,11 +156,12 @@ static int sample_chain(qsv_handle* h, Shard& sh, uint64_t shots, uint64_t seed,
   hipLaunchKernelGGL(k_remap_bits, dim3((unsigned)((shots + QSV_TPB - 1) / QSV_TPB)), dim3(QSV_TPB), 0, sh.stream,
                      sh.d_sout, shots, (uint64_t)sh.index << h->L, mm);
   HIPCHK(hipGetLastError());
-  std::vector<uint64_t> idx(shots);
-  HIPCHK(hipMemcpyAsync(idx.data(), sh.d_sout, shots * sizeof(uint64_t), hipMemcpyDeviceToHost, sh.stream));
+  std::vector<uint64_t> idx(shuffle ? shots : 0);
+  HIPCHK(hipMemcpyAsync(shuffle ? idx.data() : out_bits, sh.d_sout, shots * sizeof(uint64_t), hipMemcpyDeviceToHost, sh.stream));
   HIPCHK(hipStreamSynchronize(sh.stream));
   const double total = *reinterpret_cast<volatile double*>(h_total);
   if (!(total > 0)) return fail(QSV_E_BADARG, "state has zero norm on this process; nothing to sample");
+  if (!shuffle) return QSV_OK;
   for (uint64_t s = shots - 1; s > 0; --s) {
     const uint64_t k = rng() % (s + 1);
     std::swap(idx[s], idx[k]);
@@ -175,10 +177,11 @@ struct CondView { BitIns fix; uint64_t val; uint64_t nc; };
 // The host walk of qsv_sample and qsv_sample_cond (DESIGN §6): shards, then blocks, then the device inside a block.
 // sums[i] / mass[i] are shard i's block, super or compact-block sums and their total (mass 0: the shard is skipped);
 // total > 0 is the caller's to check.  cond == NULL: the blocks are those of the state (k_locate / k_locate_tile);
-// otherwise compact blocks of the matching sub-cube (k_locate_cond).
+// otherwise compact blocks of the matching sub-cube (k_locate_cond).  shuffle false (the unordered entry points): every
+// shard's words are copied straight into out_bits, in the walk's ascending order, and no shuffle is drawn.
 static int sample_walk(qsv_handle* h, uint64_t shots, uint64_t seed, const int* meas_qubits, int n_meas,
                        const std::vector<SumView>& sums, const std::vector<double>& mass, double total,
-                       const CondView* cond, uint64_t* out_bits) {
+                       const CondView* cond, bool shuffle, uint64_t* out_bits) {
   const size_t ns = h->shards.size();
   // sorted uniforms in [0,total) WITHOUT a sort: the order statistics of n iid uniforms are the
   // normalised partial sums of n + 1 iid exponentials (a sort of 4096 doubles cost 0.12 ms, a
@@ -195,7 +198,8 @@ static int sample_walk(qsv_handle* h, uint64_t shots, uint64_t seed, const int* 
     const double scale = total / run;
     for (uint64_t s = 0; s < shots; ++s) r[s] = std::min(r[s] * scale, std::nextafter(total, 0.0));
   }
-  std::vector<uint64_t> idx(shots);
+  std::vector<uint64_t> idx(shuffle ? shots : 0);
+  uint64_t* const words = shuffle ? idx.data() : out_bits;
   MeasMap mm;
   mm.n = meas_qubits ? n_meas : -1;                      // -1: the full basis index
   for (int j = 0; j < 64; ++j) mm.pos[j] = (meas_qubits && j < n_meas) ? (signed char)meas_qubits[j] : (signed char)-1;
@@ -284,12 +288,13 @@ static int sample_walk(qsv_handle* h, uint64_t shots, uint64_t seed, const int* 
       hipLaunchKernelGGL(k_remap_bits, dim3((unsigned)((cnt + QSV_TPB - 1) / QSV_TPB)), dim3(QSV_TPB), 0, sh.stream,
                          sh.d_sout, cnt, (uint64_t)sh.index << h->L, mm);
       HIPCHK(hipGetLastError());
-      HIPCHK(hipMemcpyAsync(&idx[s0], sh.d_sout, cnt * sizeof(uint64_t), hipMemcpyDeviceToHost, sh.stream));
+      HIPCHK(hipMemcpyAsync(words + s0, sh.d_sout, cnt * sizeof(uint64_t), hipMemcpyDeviceToHost, sh.stream));
       HIPCHK(hipStreamSynchronize(sh.stream));
     }
     base += mass[i];
     s0 = s1;
   }
+  if (!shuffle) return QSV_OK;
   // shots come out sorted by index; decorrelate the order with the same generator
   for (uint64_t s = shots - 1; s > 0; --s) {
     const uint64_t k = rng() % (s + 1);
@@ -299,8 +304,8 @@ static int sample_walk(qsv_handle* h, uint64_t shots, uint64_t seed, const int* 
   return QSV_OK;
 }
 
-extern "C" int qsv_sample(qsv_handle* h, uint64_t shots, uint64_t seed, const int* meas_qubits, int n_meas,
-                          uint64_t* out_bits) {
+static int sample_any(qsv_handle* h, uint64_t shots, uint64_t seed, const int* meas_qubits, int n_meas, bool shuffle,
+                      uint64_t* out_bits) {
   if (!h || (shots && !out_bits)) return fail(QSV_E_BADARG, "NULL argument");
   if (meas_qubits && (n_meas < 0 || n_meas > 64)) return fail(QSV_E_BADARG, "n_meas %d out of range", n_meas);
   if (meas_qubits) for (int i = 0; i < n_meas; ++i) if (meas_qubits[i] >= 0) CHK(check_qubit(h, meas_qubits[i], "measured"));
@@ -315,7 +320,7 @@ extern "C" int qsv_sample(qsv_handle* h, uint64_t shots, uint64_t seed, const in
       MeasMap cm;
       cm.n = meas_qubits ? n_meas : -1;
       for (int j = 0; j < 64; ++j) cm.pos[j] = (meas_qubits && j < n_meas) ? (signed char)meas_qubits[j] : (signed char)-1;
-      return sample_chain(h, sh, shots, seed, cm, out_bits);
+      return sample_chain(h, sh, shots, seed, cm, shuffle, out_bits);
     }
   }
   const size_t ns = h->shards.size();
@@ -328,7 +333,15 @@ extern "C" int qsv_sample(qsv_handle* h, uint64_t shots, uint64_t seed, const in
     total += mass[i];
   }
   if (!(total > 0)) return fail(QSV_E_BADARG, "state has zero norm on this process; nothing to sample");
-  return sample_walk(h, shots, seed, meas_qubits, n_meas, sums, mass, total, nullptr, out_bits);
+  return sample_walk(h, shots, seed, meas_qubits, n_meas, sums, mass, total, nullptr, shuffle, out_bits);
+}
+extern "C" int qsv_sample(qsv_handle* h, uint64_t shots, uint64_t seed, const int* meas_qubits, int n_meas,
+                          uint64_t* out_bits) {
+  return sample_any(h, shots, seed, meas_qubits, n_meas, true, out_bits);
+}
+extern "C" int qsv_sample_unordered(qsv_handle* h, uint64_t shots, uint64_t seed, const int* meas_qubits, int n_meas,
+                                    uint64_t* out_bits) {
+  return sample_any(h, shots, seed, meas_qubits, n_meas, false, out_bits);
 }
 
 // A deferred shard ahead of a post-selected draw (DESIGN §6): the matching sub-cube lies inside the tiles whose block
@@ -367,8 +380,8 @@ static int cond_prepare_deferred(qsv_handle* h, Shard& s, uint64_t lmask, uint64
   return QSV_OK;
 }
 
-extern "C" int qsv_sample_cond(qsv_handle* h, uint64_t shots, uint64_t seed, const int* meas_qubits, int n_meas,
-                               uint64_t fix_mask, uint64_t fix_val, uint64_t* out_bits, double* mass_out) {
+static int sample_cond_any(qsv_handle* h, uint64_t shots, uint64_t seed, const int* meas_qubits, int n_meas,
+                           uint64_t fix_mask, uint64_t fix_val, bool shuffle, uint64_t* out_bits, double* mass_out) {
   if (!h || (shots && !out_bits)) return fail(QSV_E_BADARG, "NULL argument");
   if (meas_qubits && (n_meas < 0 || n_meas > 64)) return fail(QSV_E_BADARG, "n_meas %d out of range", n_meas);
   if (meas_qubits) for (int i = 0; i < n_meas; ++i) if (meas_qubits[i] >= 0) CHK(check_qubit(h, meas_qubits[i], "measured"));
@@ -376,7 +389,7 @@ extern "C" int qsv_sample_cond(qsv_handle* h, uint64_t shots, uint64_t seed, con
   if (h->W < 64 && (fix_mask >> h->W)) return fail(QSV_E_BADARG, "fix_mask has bits at or above qubit %d", h->W);
   if (!fix_mask) {                                   // nothing fixed: qsv_sample itself, word for word
     if (mass_out) CHK(qsv_norm(h, mass_out));
-    return qsv_sample(h, shots, seed, meas_qubits, n_meas, out_bits);
+    return sample_any(h, shots, seed, meas_qubits, n_meas, shuffle, out_bits);
   }
   const uint64_t n = amps_local(h);
   const uint64_t lmask = fix_mask & (n - 1), lval = fix_val & (n - 1);
@@ -419,7 +432,15 @@ extern "C" int qsv_sample_cond(qsv_handle* h, uint64_t shots, uint64_t seed, con
   if (mass_out) *mass_out = total;
   if (shots == 0) return QSV_OK;
   if (!(total > 0)) return fail(QSV_E_BADARG, "post-selected outcome has zero probability");
-  return sample_walk(h, shots, seed, meas_qubits, n_meas, sums, mass, total, &cv, out_bits);
+  return sample_walk(h, shots, seed, meas_qubits, n_meas, sums, mass, total, &cv, shuffle, out_bits);
+}
+extern "C" int qsv_sample_cond(qsv_handle* h, uint64_t shots, uint64_t seed, const int* meas_qubits, int n_meas,
+                               uint64_t fix_mask, uint64_t fix_val, uint64_t* out_bits, double* mass_out) {
+  return sample_cond_any(h, shots, seed, meas_qubits, n_meas, fix_mask, fix_val, true, out_bits, mass_out);
+}
+extern "C" int qsv_sample_cond_unordered(qsv_handle* h, uint64_t shots, uint64_t seed, const int* meas_qubits, int n_meas,
+                                         uint64_t fix_mask, uint64_t fix_val, uint64_t* out_bits, double* mass_out) {
+  return sample_cond_any(h, shots, seed, meas_qubits, n_meas, fix_mask, fix_val, false, out_bits, mass_out);
 }
 
 // reduction scratch of a shard: a marginal or an expectation value per branch node of a trajectory run is thousands of
