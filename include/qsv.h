@@ -429,6 +429,27 @@ int qsv_noisy_sample_accept(qsv_handle* h, const qsv_op* ops, int n_ops, const d
  * Replaces: simulator.run(T, noise_model=..., method="density_matrix") of Qiskit Aer. */
 int qsv_density_exec(qsv_handle* h, const qsv_op* ops, int n_ops, const double* data, uint64_t n_data);
 
+/* qsv_density_exec with the measurements taken in place where their outcome is fixed by the caller: the same stream, body and
+ * checks, and in addition QSV_OP_MEASURE records as qsv_noisy_sample documents them (qubits[0] = t < W, vals[0] = the classical
+ * bit c < 64, vals[1] = release, data_off -> f0, f1 = P(flip | 0), P(flip | 1)).  A density matrix cannot follow a measured
+ * bit without branching, but "bit c read v, qubit handed on" is ONE linear, trace-decreasing map: for every 2 x 2 block B over
+ * (ket bit t, bra bit t + W)
+ *     release = 0:  B' = [[w0 B00, 0], [0, w1 B11]]        release = 1:  B' = [[w0 B00 + w1 B11, 0], [0, 0]]  (t back in |0>)
+ * with w_b = P(read v | true b) -- 1 - f_b if b == v, f_b otherwise: acceptance is on the bit as read, as in
+ * qsv_noisy_sample_accept -- when c is in fix_mask and v = bit c of fix_val, and w0 = w1 = 1 when c is not in fix_mask (the
+ * outcome is forgotten: the dephasing channel, with release the reset channel; the trace stays).  Of a fixed bit that several
+ * MEASURE records write only the LAST write conditions, the earlier ones are forgotten (the rule of
+ * qsv_noisy_sample_accept).  The trace is NOT renormalised: after the call it is the probability that every conditioning
+ * record read its value.  A fix_mask bit that no MEASURE record writes is allowed and does nothing: the caller conditions
+ * it on the diagonal.  A MEASURE record closes the run of mirrored unitary records, as PAULI and KRAUS do, and is one kernel:
+ * from qubit 3 up its own (2 loads and 4 stores per block: 24 bytes per amplitude), below that the KRAUS kernel with the
+ * superoperator of sqrt(w0) |0><0| and sqrt(w1) |1><1| (release: |0><1|) -- option density_measure_kernel.
+ * QSV_E_BADARG, with a message that names the op or the bit: t >= W, c >= 64, release not 0 or 1, a flip outside [0, 1] or
+ * not finite, the data range outside the pool, a bit of fix_val outside fix_mask.  Every record is checked before the first
+ * one runs.  With fix_mask = 0 and no MEASURE record the vector is bit for bit that of qsv_density_exec. */
+int qsv_density_exec_accept(qsv_handle* h, const qsv_op* ops, int n_ops, const double* data, uint64_t n_data,
+                            uint64_t fix_mask, uint64_t fix_val);
+
 /* the 4^n real coefficients a PAULI record (n = 1, 2) comes to on a density matrix (host only, no device needed):
  * out[x * 2^n + d] = sum_z P(x, z) (-1)^(z . d), with x, z the x and z bits of the Pauli index (QSV_OP_PAULI) and P the
  * differences of `cum`; then rho'[v] = sum_x out[x][d(v)] rho[v ^ m_x], m_x = the x bits on both sides, d(v) = (i xor j)
@@ -523,7 +544,11 @@ int qsv_timer_end(qsv_handle* h, double* ms);
  *                                  1 from 2^26 amplitudes per shard, 2 from 2^14, 0 never        lane_map_min_l [26]  same for k_multi tiles other than bits 6..10
  *   noisy       noisy_grid [0]     workgroups of qsv_noisy_sample, qsv_noisy_sample_hbm and each round of qsv_noisy_sample_accept: 0 = as many as the
  *                                  chip holds at once, else at most this many
- *   other       zero_tracking [0]  skip amplitudes known to be zero (opt-in)       exchange_chunk_log2 [24]  amplitudes per exchange chunk
+ *   density     density_measure_kernel [-1]  a MEASURE record of qsv_density_exec_accept: -1 its own kernel (24 bytes per amplitude) from
+ *                                  qubit 3 up, below that -- where the entries it skips share the lines of those it loads -- the same map as
+ *                                  a two-operator superoperator through the KRAUS kernel (32); 0 always the latter; 1 always its own.
+ *                                  The same map either way.
+ *   other      zero_tracking [0]  skip amplitudes known to be zero (opt-in)       exchange_chunk_log2 [24]  amplitudes per exchange chunk
  *               implied_zeros [1]  the generator as a program's last pass (and qsv_exec's end) leaves the provably-zero part
  *                                  of a shard unwritten; every reader honours that or writes the zeros first (0: write them always) */
 int qsv_set_option(qsv_handle* h, const char* name, int value);

@@ -26,6 +26,7 @@ _METHODS = ("statevector", "trajectory", "density_matrix")
 _WALKS = ("depth", "levels")
 _NOISY_STATES = ("lds", "hbm", "auto")
 _NOISY_MEASURES = ("deferred", "in_place", "auto")
+_DENSITY_MEASURES = ("deferred", "in_place", "auto")
 DENSITY_MAX_CLBITS = 20       # method="density_matrix" returns 2^k probabilities over the k written classical bits
 
 _NAMES = ("qasm_simulator", "aer_simulator", "aer_simulator_statevector", "statevector_simulator",
@@ -209,7 +210,16 @@ class QsvBackend:
                 QSV_OP_MEASURE record, and its qubit recycled: n + 2 live qubits for any number of cliques; the trailing
                 measurements stay one joint final draw; same limits: <= 64 classical bits, no reset, no gate after a
                 measure, no classical conditions) | 'auto' (in place iff that makes the state narrower).  A shot's Pauli,
-                Kraus and readout draws are the same in both; 'density_matrix' stays deferred
+                Kraus and readout draws are the same in both; 'density_matrix' has ``density_measure`` instead
+    density_measure  (method 'density_matrix' only) when rho is measured: 'deferred' (default: every measurement at the end,
+                W = n + m + 1 for a QCMRF circuit, W <= 17 and <= 20 written classical bits) | 'in_place' (a mid-circuit
+                measurement whose bit ``accept`` fixes is applied where it occurs, as the one linear map "read the accepted
+                value, hand the qubit back in |0>" (``qsv_density_exec_accept``), and its qubit recycled: n + 2 live qubits for
+                any number of cliques; the limits hold for the live width and for the bits of the trailing measurements,
+                which stay the final read-out of the diagonal; every mid-circuit bit must be fixed by ``accept`` and written
+                once, otherwise a ValueError names the bit) | 'auto' (in place iff that is possible and makes rho narrower).
+                ``accept_probability`` and ``get_probabilities()`` mean what they mean deferred; metadata gains
+                ``density_measure`` (resolved), ``n_qubits`` (live), ``n_circuit_qubits`` and ``n_measure_ops``
     accept      (noisy runs and method 'density_matrix') ``{classical bit: 0 | 1}``, or a list with one dict per circuit
                 (``QCMRF.post_selection()`` is a valid value): only shots whose bits read these values are kept, and ``shots`` is
                 the number of KEPT shots.  A noisy run takes attempts 0, 1, 2, ... -- attempt t is shot t of the same run without
@@ -337,6 +347,11 @@ class QsvBackend:
         nmeasure = opts.get("noisy_measure", "deferred")
         if nmeasure not in _NOISY_MEASURES:
             raise ValueError("unknown noisy_measure %r; a noisy shot takes its measurements %s" % (nmeasure, ", ".join(_NOISY_MEASURES)))
+        dmeasure = opts.get("density_measure")
+        if dmeasure is not None and dmeasure not in _DENSITY_MEASURES:
+            raise ValueError("unknown density_measure %r; a density matrix takes its measurements %s" % (dmeasure, ", ".join(_DENSITY_MEASURES)))
+        if dmeasure is not None and method != "density_matrix":
+            raise ValueError("density_measure belongs to method='density_matrix', not method=%r (noisy shots have noisy_measure)" % (method,))
         accept = self._accept_of(opts, len(circs), method)      # (first: it is the one that refuses the two together)
         post = self._post_select_of(opts, len(circs), method)
         if method == "density_matrix":
@@ -345,13 +360,14 @@ class QsvBackend:
             model = self._density_model_of(opts)
             from concurrent.futures import ThreadPoolExecutor
             with ThreadPoolExecutor(max_workers=1) as pool:     # host compile of circuit i+1 while the device evolves circuit i
-                nxt = pool.submit(self._prepare_density, circs[0], model)
+                prepare = lambda i: self._prepare_density_measure(circs[i], model, dmeasure, accept and accept[i])     # noqa: E731
+                nxt = pool.submit(prepare, 0)
                 for i in range(len(circs)):
-                    prepared = nxt.result()
+                    prepared, place = nxt.result()
                     if i + 1 < len(circs):
-                        nxt = pool.submit(self._prepare_density, circs[i + 1], model)
+                        nxt = pool.submit(prepare, i + 1)
                     exps.append(self._run_density(circs[i], int(shots), int(seed_simulator) + i, opts, prepared,
-                                                  accept=accept and accept[i]))
+                                                  accept=accept and accept[i], place=place))
             return Job(Result(exps, self._name))
         model = self._noise_of(opts)
         if model is not None:
@@ -629,6 +645,78 @@ class QsvBackend:
         return ing, rec, data, clist, meas, readout, time.perf_counter() - t0
 
     @staticmethod
+    def _prepare_density_measure(circuit, model, measure, accept):
+        """(the tuple of ``_prepare_density``, place) for the run option density_measure: ``place`` is None for the default
+        (``measure`` None or 'deferred': today's path and metadata), else {"mode": the option resolved, ...}"""
+        if measure is None or measure == "deferred":
+            return QsvBackend._prepare_density(circuit, model), None
+        t0 = time.perf_counter()
+        got = QsvBackend._prepare_density_in_place(circuit, model, accept, measure == "auto", t0)
+        if got is not None:
+            return got
+        prepared = QsvBackend._prepare_density(circuit, model)
+        return prepared, {"mode": "deferred", "width": prepared[0].num_qubits, "n_measure": 0}
+
+    @staticmethod
+    def _prepare_density_in_place(circuit, model, accept, auto, t0):
+        """``_prepare_density`` with the mid-circuit measurements applied where they occur: the ops of the deferred ingest in
+        their order, remapped to live slots (``trajectory.plan_slots``), every mid-circuit measure a "measure" op built as
+        ``_prepare_noisy_in_place`` builds it (one QSV_OP_MEASURE record, its flips those of the measured logical qubit); the
+        trailing measures stay the read-out of the diagonal (``clist``, ``meas`` and ``readout`` cover them alone).  rho
+        cannot follow a bit that is free, so every mid-circuit bit has to be fixed by ``accept`` and written once: otherwise
+        a ValueError, or None under ``auto``, which also answers None when the live width is the circuit's"""
+        from . import ir, trajectory
+        ing = _ingest.ingest(circuit, noise=model, keep_measures=True)
+        staged, width, finals = trajectory.plan_slots(ing.ops)
+        width = max(width, 1)
+        if auto and width >= ing.num_qubits:
+            return None
+        early = [item for item in staged if item[0] == "measure"]
+        written = {}
+        for c in [item[2] for item in early] + [c for _, c in finals]:
+            written[c] = written.get(c, 0) + 1
+        for _, s, c, release, q in early:
+            if accept is not None and c in accept and accept[c] not in (0, 1):
+                raise ValueError("accept fixes classical bit %r to %r; a bit reads 0 or 1" % (c, accept[c]))
+            if accept is not None and c in accept and written[c] == 1:
+                continue
+            if auto:
+                return None
+            why = "is written %d times" % written[c] if accept is not None and c in accept else "is not fixed by accept"
+            raise ValueError("density_measure='in_place': classical bit %d is measured mid-circuit (qubit %d) and %s; a density matrix "
+                             "follows a measurement taken in place only where its outcome is fixed and written once: pass "
+                             "accept=qc.post_selection(), or density_measure='deferred' or 'auto'" % (c, q, why))
+        if width > _lib.DENSITY_MAX_QUBITS:
+            raise ValueError("method='density_matrix' holds rho of at most %d qubits (16 * 4^W bytes), the circuit has %d live at once "
+                             "with its measurements taken in place" % (_lib.DENSITY_MAX_QUBITS, width))
+        final = dict((c, s) for s, c in finals)             # (a bit two trailing measures write: the last one reads it)
+        clist = sorted(final)
+        if len(clist) > DENSITY_MAX_CLBITS:
+            raise ValueError("method='density_matrix' returns the distribution over at most %d written classical bits, the "
+                             "circuit's trailing measurements write %d" % (DENSITY_MAX_CLBITS, len(clist)))
+        every = sorted(ing.measure)
+        if every and every[-1] >= 64:
+            raise ValueError("method='density_matrix' records at most 64 classical bits, the circuit writes bit %d" % every[-1])
+        ops, fm, fv = [], 0, 0
+        for item in staged:
+            if item[0] == "ops":
+                ops += item[1]
+            else:
+                _, s, c, release, q = item
+                ops.append(ir.Op("measure", target=s, mask=c, vals=(int(release),), table=model.readout_flips(q)))
+                fm |= 1 << int(c)
+                fv |= int(accept[c]) << int(c)
+        ing.ops = ops
+        rec, data = program.encode(ops)
+        meas = [-1] * (every[-1] + 1) if every else []
+        readout = np.zeros((len(meas), 2))
+        for c in clist:
+            meas[c] = final[c]
+            readout[c] = ing.readout.get(c, (0.0, 0.0))
+        place = {"mode": "in_place", "width": width, "n_measure": len(early), "fix": (fm, fv)}
+        return (ing, rec, data, clist, meas, readout, time.perf_counter() - t0), place
+
+    @staticmethod
     def _confuse(dist, flips):
         """readout confusion on the host: bit j of the index flipped with flips[j][value]"""
         words = np.arange(dist.size)
@@ -642,9 +730,9 @@ class QsvBackend:
         return dist
 
     @staticmethod
-    def _condition(dist, clist, accept):
+    def _condition(dist, clist, accept, total=None):
         """(dist conditioned on ``accept`` and renormalised, the mass of the condition); index bit j of dist is classical bit
-        clist[j]"""
+        clist[j].  ``total``: what the mass is a share of (default: the sum of dist)"""
         fm = fv = 0
         for c, v in accept.items():
             if c not in clist:
@@ -658,15 +746,21 @@ class QsvBackend:
         mass = kept.sum()
         if not mass > 0:
             raise ValueError("post-selected outcome %r has zero probability" % (accept,))
-        return kept / mass, float(mass / p.sum())
+        return kept / mass, float(mass / (p.sum() if total is None else total))
 
-    def _run_density(self, circuit, shots, seed, opts, prepared, accept=None):
+    def _run_density(self, circuit, shots, seed, opts, prepared, accept=None, place=None):
         """qsv_density_exec, then the exact distribution (qsv_density_diagonal + readout confusion) and the shots (qsv_density_sample);
-        ``accept``: the distribution conditioned on the host, the shots one multinomial draw from it"""
+        ``accept``: the distribution conditioned on the host, the shots one multinomial draw from it.
+        ``place`` (``_prepare_density_measure``) in place: qsv_density_exec_accept with the accepted bits its MEASURE records
+        write -- rho comes back with their share of the success probability as its trace --, the diagonal over the slots of
+        the trailing measurements, the accepted bits among those conditioned on the host"""
         ing, rec, data, clist, meas, readout, t_compile = prepared
         t1 = time.perf_counter()
         t0 = t1 - t_compile
-        W = ing.num_qubits
+        in_place = place is not None and place["mode"] == "in_place"
+        W = place["width"] if in_place else ing.num_qubits
+        if in_place and accept is not None:
+            self._accept_mask(accept, ing)                     # (its refusals: a bit nothing writes, a value that is no bit)
         state_bytes = 16 * 4 ** W
         dev = tuple(opts["devices"])[0]
         memory = _lib.device_memory if self._engine_factory is None else getattr(self._engine_factory, "device_memory", None)
@@ -677,23 +771,32 @@ class QsvBackend:
                                  % (W, W, state_bytes, dev, free))
         eng = self._get_engine(2 * W, dict(opts, comm=None, devices=tuple(opts["devices"])[:1]))
         self._apply_engine_options(eng, opts)
-        eng.density_exec(rec, data)
+        if in_place:
+            eng.density_exec_accept(rec, data, *place["fix"])
+        else:
+            eng.density_exec(rec, data)
         eng.sync()
         t2 = time.perf_counter()
-        marg, trace = eng.density_diagonal([ing.measure[c] for c in clist])
+        marg, trace = eng.density_diagonal([meas[c] if in_place else ing.measure[c] for c in clist])
         dist = self._confuse(marg, [tuple(readout[c]) for c in clist])
         accept_meta = {}
-        if accept is not None:
+        if accept is not None and in_place:
+            # the records' share is in the trace already: the mass of the matching words is the whole success probability
+            dist, mass = self._condition(dist, clist, {c: v for c, v in accept.items() if not (place["fix"][0] >> int(c)) & 1}, total=1.0)
+            accept_meta = {"accept": dict(accept), "accept_probability": mass}
+        elif accept is not None:
             dist, mass = self._condition(dist, clist, accept)
             accept_meta = {"accept": dict(accept), "accept_probability": mass}
         keep = np.flatnonzero(dist > 0)
         words = np.zeros(keep.size, dtype=np.uint64)            # bit j of the index is classical bit clist[j]
         for j, c in enumerate(clist):
             words |= ((keep.astype(np.uint64) >> np.uint64(j)) & np.uint64(1)) << np.uint64(c)
-        probs = dict(zip(_format_keys(words, np.arange(keep.size), ing.num_clbits, ing.creg_sizes).keys(), dist[keep].tolist())) if clist else {}
+        if in_place:
+            words |= np.uint64(place["fix"][1])                 # full-width keys: the bits the records wrote read their accepted values
+        probs = dict(zip(_format_keys(words, np.arange(keep.size), ing.num_clbits, ing.creg_sizes).keys(), dist[keep].tolist())) if clist or (in_place and place["n_measure"]) else {}
         counts = {}
         counts_path = _counts_path_default()
-        if clist and shots > 0 and accept is not None:
+        if (clist or (in_place and place["n_measure"])) and shots > 0 and accept is not None:
             drawn = np.random.default_rng(seed).multinomial(shots, dist[keep])
             counts = _format_keys(words[drawn > 0], drawn[drawn > 0], ing.num_clbits, ing.creg_sizes)
             counts_path = "python"
@@ -705,6 +808,8 @@ class QsvBackend:
                 "n_pauli_ops": ing.n_pauli, "n_kraus_ops": ing.n_kraus, "n_kraus2_ops": ing.n_kraus2, "readout_errors": len(ing.readout), "trace": float(trace),
                 "state_bytes": state_bytes, "time_compile": t1 - t0, "time_evolve": t2 - t1, "time_sample": t3 - t2,
                 "time_taken": t3 - t0, "seed_simulator": seed, "counts_path": counts_path}
+        if place is not None:
+            meta.update(density_measure=place["mode"], n_circuit_qubits=ing.num_qubits, n_measure_ops=place["n_measure"])
         meta.update(accept_meta)
         self.last_engine = None          # the resident vector is rho, not a state: statevector() has nothing to show
         self.last_plan = None

@@ -261,6 +261,7 @@ struct qsv_handle {
   int opt_defer_state = -1;           // the generator as a program's last pass leaves tile sums only, the state deferred: -1 from QSV_DEFER_MIN_L local qubits, 0 never, 1 always
   int opt_sums_factored = -1;         // the generator's sums launch over the tiles that differ in an inner factor only, expanded by the tile-uniform factors: -1 where that removes at least QSV_FACTORED_MIN_BITS (3) tile-index bits, 0 never, 1 where it removes at least one
   int opt_sample_chain = 1;           // qsv_sample on one shard's tile sums: 1 the super-sum walk on the device (k_walk_super), a deferred shard's shots located inside the generator (QSV_GEN_LOCATE), one host wait; 0 the host walk, listed tiles stored and read back
+  int opt_density_measure_kernel = -1;  // a MEASURE record of qsv_density_exec_accept: -1 k_dm_measure from qubit QSV_DM_MEASURE_MIN_QUBIT up, the two-operator superoperator through k_dm_kraus below; 0 always k_dm_kraus; 1 always k_dm_measure
   int opt_post_select_list = -1;      // qsv_sample_cond on a deferred shard: -1 the tiles that hold the matching sub-cube are listed and stored when they are at most ntiles >> QSV_PROD_MAXG and fit a quarter of the arena, else the state is realised; 0 always realised; 1 listed whenever a block bit is fixed and the list fits
   int opt_init_prod_group = -1;     // group bits of the generator (2^B tiles per workgroup step): -1 auto (up to 3), 0 off, 1..4 that many
   int opt_xframe = 1;                 // uncontrolled X gates inside a pass become an XOR on its store addresses

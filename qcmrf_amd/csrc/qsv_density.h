@@ -32,6 +32,13 @@ struct DmLaunch {
 
 hipError_t qsv_dm_pauli_launch(const DmLaunch& l, int n, const DmPauli& c);
 hipError_t qsv_dm_kraus_launch(const DmLaunch& l, const DmKraus& s);
+// A MEASURE record with its outcome fixed or forgotten: B' = diag(w0 B00, w1 B11) on every 2 x 2 block over the ket and bra
+// bit of the measured qubit (n = 1 in DmPos), release != 0: B' = diag(w0 B00 + w1 B11, 0).  2 loads, 4 stores per block.
+hipError_t qsv_dm_measure_launch(const DmLaunch& l, int release, double w0, double w1);
+// Below this qubit the ket pair (v, v + 2^t) of a block shares one 128-byte line (8 amplitudes), so the entries k_dm_measure does
+// not load come in with their lines anyway: nothing is saved, and two half-used loads per line ran 0.5 to 0.9 times as fast as
+// k_dm_kraus (t = 0, 1, 2 at W = 13); from qubit 3 up k_dm_measure is 1.3 to 1.4 times faster (profiles/density_measure.log)
+#define QSV_DM_MEASURE_MIN_QUBIT 3
 // A KRAUS2 record: d_s = the 16 x 16 superoperator in device memory (512 doubles: too large for kernel arguments),
 // S[e][f] (row-major, (re, im)) = sum_k K_k[a][a'] conj(K_k[b][b']), e = a | b << 2, f = a' | b' << 2, with a, b, a', b' the
 // two-bit indices of the record's operators (bit j on error qubit j): block bits 0, 1 the ket bits, 2, 3 the bra bits (DmPos)

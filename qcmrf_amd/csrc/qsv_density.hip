@@ -10,9 +10,12 @@
 //                   superoperator S (built once per record on the host).
 //   k_dm_kraus2     the same on two qubits: 4 x 4 blocks of 16 amplitudes times the 16 x 16 superoperator, which comes
 //                   through device memory.
+//   k_dm_measure    an accepted (or forgotten) measurement of one qubit taken in place: of every 2 x 2 block only the two
+//                   entries diagonal in the qubit survive, weighted; with RELEASE both land on the |0><0| entry.
 // A thread owns whole blocks: the 4^N amplitudes that differ only in the ket and bra bits of the error qubits.  For a low
 // error qubit q its loads are adjacent 16-byte pieces of one line (q = 0: v and v + 1); the bra bit q + W is a far stride
-// for every W that matters.  Each amplitude is read once and written once: 32 B per amplitude, a pure stream.
+// for every W that matters.  Each amplitude is read once and written once: 32 B per amplitude, a pure stream
+// (k_dm_measure: two of four read, all four written, 24 B per amplitude).
 // Every array index is a compile-time constant after unrolling: no scratch.
 #include "qsv_density.h"
 #include "qsv_common.h"
@@ -77,6 +80,30 @@ __global__ __launch_bounds__(QSV_TPB) void k_dm_kraus(cplx* __restrict__ amp, ui
 #pragma unroll
       for (int f = 1; f < 4; ++f) acc = cmad(make_double2(s.s[8 * e + 2 * f], s.s[8 * e + 2 * f + 1]), in[f], acc);
       if (NT) st_nt(b + off[e], acc); else st(b + off[e], acc);
+    }
+  }
+}
+
+// A MEASURE record on qubit t whose outcome is fixed (or forgotten): B = the 2 x 2 block over (ket bit t, bra bit t + W),
+// B' = diag(w0 B00, w1 B11), with RELEASE B' = diag(w0 B00 + w1 B11, 0).  The off-diagonal entries are never read and the
+// zeros are stored as zeros (not as 0 x input: an inf or nan there must not survive): 2 loads and 4 stores per block.
+template <bool NT, bool RELEASE>
+__global__ __launch_bounds__(QSV_TPB) void k_dm_measure(cplx* __restrict__ amp, uint64_t nblocks, DmPos p, double w0, double w1) {
+  const uint64_t o1 = 1ull << p.pos[0], o2 = 1ull << p.pos[1];
+  const cplx zero = make_double2(0.0, 0.0);
+  for (uint64_t t = (uint64_t)blockIdx.x * QSV_TPB + threadIdx.x; t < nblocks; t += (uint64_t)gridDim.x * QSV_TPB) {
+    cplx* b = amp + dm_base<2>(t, p);
+    const cplx b00 = NT ? ld_nt(b) : ld(b);
+    const cplx b11 = NT ? ld_nt(b + (o1 | o2)) : ld(b + (o1 | o2));
+    cplx out[4] = {make_double2(w0 * b00.x, w0 * b00.y), zero, zero, make_double2(w1 * b11.x, w1 * b11.y)};
+    if (RELEASE) {
+      out[0] = make_double2(fma(w1, b11.x, out[0].x), fma(w1, b11.y, out[0].y));
+      out[3] = zero;
+    }
+    const uint64_t off[4] = {0, o1, o2, o1 | o2};
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+      if (NT) st_nt(b + off[e], out[e]); else st(b + off[e], out[e]);
     }
   }
 }
@@ -151,6 +178,17 @@ hipError_t qsv_dm_pauli_launch(const DmLaunch& l, int n, const DmPauli& c) {
 hipError_t qsv_dm_kraus_launch(const DmLaunch& l, const DmKraus& s) {
   if (l.nt) hipLaunchKernelGGL((k_dm_kraus<true>), dim3(l.grid), dim3(QSV_TPB), 0, l.stream, l.amp, l.nblocks, l.pos, s);
   else hipLaunchKernelGGL((k_dm_kraus<false>), dim3(l.grid), dim3(QSV_TPB), 0, l.stream, l.amp, l.nblocks, l.pos, s);
+  return hipGetLastError();
+}
+
+hipError_t qsv_dm_measure_launch(const DmLaunch& l, int release, double w0, double w1) {
+  if (release) {
+    if (l.nt) hipLaunchKernelGGL((k_dm_measure<true, true>), dim3(l.grid), dim3(QSV_TPB), 0, l.stream, l.amp, l.nblocks, l.pos, w0, w1);
+    else hipLaunchKernelGGL((k_dm_measure<false, true>), dim3(l.grid), dim3(QSV_TPB), 0, l.stream, l.amp, l.nblocks, l.pos, w0, w1);
+  } else {
+    if (l.nt) hipLaunchKernelGGL((k_dm_measure<true, false>), dim3(l.grid), dim3(QSV_TPB), 0, l.stream, l.amp, l.nblocks, l.pos, w0, w1);
+    else hipLaunchKernelGGL((k_dm_measure<false, false>), dim3(l.grid), dim3(QSV_TPB), 0, l.stream, l.amp, l.nblocks, l.pos, w0, w1);
+  }
   return hipGetLastError();
 }
 

@@ -3,7 +3,8 @@
 // rho of W qubits in the shard of a 2W-qubit handle, rho[i, j] at v = i | (j << W).  The program is the record stream of
 // qsv_noisy_sample.  A unitary record runs as itself on the ket bits and as its mirror on the bra bits (qubits + W,
 // matrix and table conjugated, angle negated); every maximal run of them is ONE qsv_exec program, so ket and bra gates share
-// k_multi passes like any other gates.  PAULI, KRAUS and KRAUS2 records close the run and have kernels of their own.
+// k_multi passes like any other gates.  PAULI, KRAUS and KRAUS2 records close the run and have kernels of their own; so do the
+// MEASURE records of qsv_density_exec_accept (an outcome fixed by the caller, or forgotten: one linear map on rho).
 // ------------------------------------------------------------------------------------------
 static int dm_check_handle(const qsv_handle* h) {
   if (!h) return fail(QSV_E_BADARG, "NULL handle");
@@ -39,7 +40,9 @@ extern "C" int qsv_density_pauli_table(int n, const double* cum, double* out) {
 // implied zeros written first; launch() drops the cached sums
 // kraus2: the 512 doubles of a KRAUS2 record's superoperator on the host; they are staged in the shard's noisy buffer, in stream
 // order behind the kernel of an earlier record that may still read its own
-static int dm_channel(qsv_handle* h, int n, const int* qubits, const DmPauli* pauli, const DmKraus* kraus, const double* kraus2 = nullptr) {
+// measure: {release, w0, w1} of a MEASURE record (k_dm_measure: 2 loads and 4 stores per block, 24 B per amplitude)
+static int dm_channel(qsv_handle* h, int n, const int* qubits, const DmPauli* pauli, const DmKraus* kraus, const double* kraus2 = nullptr,
+                      const double* measure = nullptr) {
   CHK(materialize_all(h));
   Shard& s = h->shards[0];
   CHK(shard_set(s));
@@ -59,6 +62,11 @@ static int dm_channel(qsv_handle* h, int n, const int* qubits, const DmPauli* pa
   for (int k = 0; k < 2 * n; ++k) l.pos.ins[k] = l.pos.pos[k];
   std::sort(l.pos.ins, l.pos.ins + 2 * n);
   hipError_t e = hipSuccess;
+  if (measure) {
+    CHK(launch(h, s, QSV_K_KQ, 24.0 * (double)N, [&] { e = qsv_dm_measure_launch(l, measure[0] != 0.0, measure[1], measure[2]); }));
+    HIPCHK(e);
+    return QSV_OK;
+  }
   if (kraus2) {
     const size_t bytes = QSV_DM_KRAUS2_DOUBLES * sizeof(double);
     if (s.noisy_cap < bytes) {
@@ -78,11 +86,18 @@ static int dm_channel(qsv_handle* h, int n, const int* qubits, const DmPauli* pa
   return QSV_OK;
 }
 
-extern "C" int qsv_density_exec(qsv_handle* h, const qsv_op* ops, int n_ops, const double* data, uint64_t n_data) {
+// the body of qsv_density_exec and qsv_density_exec_accept; `accept`: MEASURE records are taken (fix_mask, fix_val: the bits
+// whose last write conditions), otherwise refused
+static int dm_exec(qsv_handle* h, const qsv_op* ops, int n_ops, const double* data, uint64_t n_data, bool accept,
+                   uint64_t fix_mask, uint64_t fix_val) {
   CHK(dm_check_handle(h));
   if (n_ops < 0 || (n_ops && !ops)) return fail(QSV_E_BADARG, "NULL argument");
   const int W = h->W / 2;
   if (W > QSV_DENSITY_MAX_QUBITS) return fail(QSV_E_BADARG, "a density matrix of %d qubits exceeds the %d this method holds", W, QSV_DENSITY_MAX_QUBITS);
+  if (fix_val & ~fix_mask)
+    return fail(QSV_E_BADARG, "fix_val sets bit %d, which fix_mask does not fix", __builtin_ctzll(fix_val & ~fix_mask));
+  int last_write[64];                                      // the MEASURE record that writes a bit last: the one that conditions
+  for (int c = 0; c < 64; ++c) last_write[c] = -1;
   auto need = [&](int i, const qsv_op& o, uint64_t cnt) -> int {
     if (!data || o.data_off + cnt > n_data) return fail(QSV_E_BADARG, "op %d: data range [%llu,+%llu) outside pool of %llu", i,
                                                         (unsigned long long)o.data_off, (unsigned long long)cnt, (unsigned long long)n_data);
@@ -143,8 +158,22 @@ extern "C" int qsv_density_exec(qsv_handle* h, const qsv_op* ops, int n_ops, con
           if (!std::isfinite(data[o.data_off + j])) return fail(QSV_E_BADARG, "op %d: QSV_OP_KRAUS2 entry %d is not finite", i, j);
         break;
       }
-      case QSV_OP_MEASURE:
-        return fail(QSV_E_UNSUPPORTED, "op %d: QSV_OP_MEASURE (a measurement taken in place) runs in qsv_noisy_sample only; the density-matrix method defers every measurement", i);
+      case QSV_OP_MEASURE: {
+        if (!accept)
+          return fail(QSV_E_UNSUPPORTED, "op %d: QSV_OP_MEASURE (a measurement taken in place) runs in qsv_noisy_sample only; the density-matrix method defers every measurement", i);
+        if (o.n != 1) return fail(QSV_E_BADARG, "op %d: QSV_OP_MEASURE measures 1 qubit, not %d", i, o.n);
+        if (o.qubits[0] < 0 || o.qubits[0] >= W)
+          return fail(QSV_E_BADARG, "op %d: QSV_OP_MEASURE qubit %d not in [0,%d) of the density matrix", i, o.qubits[0], W);
+        if (o.vals[0] < 0 || o.vals[0] >= 64) return fail(QSV_E_BADARG, "op %d: QSV_OP_MEASURE writes classical bit %d, not in [0,64)", i, o.vals[0]);
+        if (o.vals[1] != 0 && o.vals[1] != 1) return fail(QSV_E_BADARG, "op %d: QSV_OP_MEASURE release flag %d is not 0 or 1", i, o.vals[1]);
+        CHK(need(i, o, 2));
+        for (int b = 0; b < 2; ++b) {
+          const double f = data[o.data_off + b];
+          if (!(f >= 0.0 && f <= 1.0)) return fail(QSV_E_BADARG, "op %d: QSV_OP_MEASURE flip probability P(flip | %d) = %g not in [0, 1]", i, b, f);
+        }
+        last_write[o.vals[0]] = i;
+        break;
+      }
       case QSV_OP_MUX: case QSV_OP_KQ: case QSV_OP_SWAP:
         return fail(QSV_E_UNSUPPORTED, "op %d: kind %d is not supported by the density-matrix method (INIT, 1Q, MCX, DIAG, MCPHASE, PAULI, KRAUS, KRAUS2 only)", i, o.kind);
       default:
@@ -235,11 +264,42 @@ extern "C" int qsv_density_exec(qsv_handle* h, const qsv_op* ops, int n_ops, con
         CHK(dm_channel(h, 2, o.qubits, nullptr, nullptr, s.data()));
         break;
       }
+      case QSV_OP_MEASURE: {
+        CHK(flush_run());
+        const int c = o.vals[0];
+        double m[3] = {(double)o.vals[1], 1.0, 1.0};      // an outcome nobody fixes, or one overwritten later: forgotten
+        if (((fix_mask >> c) & 1ull) && last_write[c] == i) {
+          const int v = (int)((fix_val >> c) & 1ull);      // acceptance is on the bit as read: w_b = P(read v | true b)
+          m[1] = v == 0 ? 1.0 - d[0] : d[0];
+          m[2] = v == 1 ? 1.0 - d[1] : d[1];
+        }
+        const int own = h->opt_density_measure_kernel;
+        if (own > 0 || (own < 0 && o.qubits[0] >= QSV_DM_MEASURE_MIN_QUBIT)) {
+          CHK(dm_channel(h, 1, o.qubits, nullptr, nullptr, nullptr, m));
+        } else {
+          // a low qubit: the same map as the superoperator of sqrt(w0) |0><0| and sqrt(w1) |1><1| (release: sqrt(w1) |0><1|)
+          DmKraus s;
+          memset(&s, 0, sizeof s);
+          s.s[0] = m[1];                                   // S[0][0]: B00 -> B00
+          s.s[o.vals[1] ? 6 : 30] = m[2];                  // release: S[0][3], B11 -> B00; else S[3][3]
+          CHK(dm_channel(h, 1, o.qubits, nullptr, &s));
+        }
+        break;
+      }
       default: break;
     }
   }
   CHK(flush_run());
   return QSV_OK;
+}
+
+extern "C" int qsv_density_exec(qsv_handle* h, const qsv_op* ops, int n_ops, const double* data, uint64_t n_data) {
+  return dm_exec(h, ops, n_ops, data, n_data, false, 0, 0);
+}
+
+extern "C" int qsv_density_exec_accept(qsv_handle* h, const qsv_op* ops, int n_ops, const double* data, uint64_t n_data,
+                                       uint64_t fix_mask, uint64_t fix_val) {
+  return dm_exec(h, ops, n_ops, data, n_data, true, fix_mask, fix_val);
 }
 
 // Re rho_ii for every i, on the host: one strided read on the device, 2^W doubles (1 MiB at W = 17) across

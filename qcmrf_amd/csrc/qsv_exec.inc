@@ -757,6 +757,7 @@ extern "C" int qsv_set_option(qsv_handle* h, const char* name, int value) {
   else if (!strcmp(name, "sums_factored")) { if (value < -1 || value > 1) return fail(QSV_E_BADARG, "sums_factored must be -1 (auto), 0 or 1"); h->opt_sums_factored = value; }
   else if (!strcmp(name, "defer_state")) { if (value < -1 || value > 1) return fail(QSV_E_BADARG, "defer_state must be -1 (auto), 0 or 1"); h->opt_defer_state = value; }
   else if (!strcmp(name, "sample_chain")) { if (value < 0 || value > 1) return fail(QSV_E_BADARG, "sample_chain must be 0 or 1"); h->opt_sample_chain = value; }
+  else if (!strcmp(name, "density_measure_kernel")) { if (value < -1 || value > 1) return fail(QSV_E_BADARG, "density_measure_kernel must be -1 (auto), 0 or 1"); h->opt_density_measure_kernel = value; }
   else if (!strcmp(name, "post_select_list")) { if (value < -1 || value > 1) return fail(QSV_E_BADARG, "post_select_list must be -1 (auto), 0 or 1"); h->opt_post_select_list = value; }
   else if (!strcmp(name, "init_prod_group")) { if (value < -1 || value > QSV_PROD_MAXG) return fail(QSV_E_BADARG, "init_prod_group must be -1 (auto) or 0..4"); h->opt_init_prod_group = value; }
   else if (!strcmp(name, "pass_max_ops")) { if (value < 1 || value > 512) return fail(QSV_E_BADARG, "pass_max_ops out of range"); h->opt_pass_max_ops = value; }

@@ -2,7 +2,7 @@
 
     python -m qcmrf_amd.run_experiment [--scale 0.5] [--shots 10000] [--reps 10] [--outdir .]
                                        [--depolarizing P1,P2] [--readout P] [--t1 US --t2 US --gate-time NS1,NS2]
-                                       [--method density_matrix] [--post-select]
+                                       [--method density_matrix] [--density-measure auto] [--post-select]
 
 Same steps, same files: seed numpy with 1984, draw theta = -halfnorm.rvs(scale) for the 7
 hard-coded graphs x REPS, dump ``models_<SCALE>.json``, build the 70 ``QCMRF`` circuits, run them
@@ -26,7 +26,9 @@ the other noise options build; with no other noise option it is the only error.
 
 ``--method density_matrix`` evolves every circuit exactly as a density matrix (noisy or not): the counts are drawn from the
 exact distributions, and those are written as well, one ``{bitstring: p}`` per circuit, to ``probs_simulation_<SCALE>.json``
-(``probs_simulation_noisy_<SCALE>.json`` for a noisy run).
+(``probs_simulation_noisy_<SCALE>.json`` for a noisy run).  With ``--post-select``, ``--density-measure in_place`` (or ``auto``)
+applies every clique ancilla's accepted measurement where it occurs and recycles the qubit: rho of n + 2 live qubits instead of
+n + m + 1, the same exact numbers.
 
 ``--post-select`` draws every shot from the branch in which all clique ancillas read 0 (``QCMRF.post_selection()``): the
 counts, SHOTS Gibbs samples per circuit with full-width keys, go to ``result_simulation_postselected_<SCALE>.json`` and the
@@ -68,6 +70,9 @@ def main(argv=None):
     ap.add_argument("--noisy-measure", default=None, choices=["deferred", "in_place", "auto"],
                     help="noisy run: take every measurement at the end (deferred, the default) or mid-circuit ones when they occur, "
                          "their qubits recycled (in_place; auto: in place iff that makes the per-shot state narrower)")
+    ap.add_argument("--density-measure", default=None, choices=["deferred", "auto", "in_place"],
+                    help="--method density_matrix: take every measurement at the end (deferred, the default) or apply the mid-circuit ones "
+                         "that --post-select fixes where they occur, their qubits recycled (in_place; auto: where possible and narrower)")
     ap.add_argument("--post-select", action="store_true",
                     help="every shot from the branch in which all clique ancillas read 0; also writes the success probabilities "
                          "(exact; estimated from the attempts made when the run is noisy)")
@@ -105,6 +110,8 @@ def main(argv=None):
         extra["method"] = args.method
     if args.noisy_measure is not None:
         extra["noisy_measure"] = args.noisy_measure
+    if args.density_measure is not None:
+        extra["density_measure"] = args.density_measure
     if POST is not None:
         extra["accept" if ACCEPT else "post_select"] = POST
     result = simulator.run(CIRCS, shots=args.shots, seed_simulator=args.seed_simulator, **extra).result()

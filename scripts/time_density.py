@@ -2,6 +2,7 @@
 
     python scripts/time_density.py graphs   [--reps 2] [--shots 10000] [--passes 2]
     python scripts/time_density.py kernels  [--W 13] [--rounds 2]
+    python scripts/time_density.py measure  [--W 13] [--windows 5] [--targets 0 5 12] [--kernel 1]
 
 graphs   per graph of the reference experiment: the lowered circuits under the ``--depolarizing 0.001,0.01 --readout 0.02``
          model; ``density_exec`` of each against the 10 000-shot ``noisy_sample`` call of the same program, same build, same
@@ -10,6 +11,13 @@ kernels  at W qubits (a vector of 4^W amplitudes): the PAULI kernel for n = 1 an
          qubits, each against the same superoperator handed as a dense matrix to ``apply_kq`` (k = 2, 4) on the same bits,
          alternating.  A record's time is the difference between programs of 18 and of 2 equal records, over 16 (the
          program's init pass cancels); 32 B per amplitude over that time, against the 8 TB/s peak.
+measure  at W qubits: a MEASURE record through ``density_exec_accept`` (k_dm_measure: 24 B per amplitude) against the same map
+         as a KRAUS record of the two operators |0><0| and |1><1| (release: |0><1|) through ``density_exec`` (k_dm_kraus: 32 B),
+         on t = 0, 5 and W - 1, with and without release.  A window is one record time as above (18 records minus 2, over
+         16); the two routes alternate window by window in one process; the median of the windows is reported with their
+         spread.  The outcome is forgotten (weights 1, 1) so that 18 records leave a state: the kernels' work does not
+         depend on the weights.  ``--kernel 1`` times k_dm_measure itself on every qubit; without it the record runs as the
+         library routes it (below qubit 3 through k_dm_kraus: the two columns then time the same kernel).
 One JSON line per measurement."""
 import argparse
 import json
@@ -138,18 +146,59 @@ def kernels(args):
     eng.close()
 
 
+def measure(args):
+    W = args.W
+    eng = _lib.Engine(2 * W)
+    if args.nontemporal is not None:
+        eng.set_option("nontemporal", args.nontemporal)
+    if args.kernel is not None:
+        eng.set_option("density_measure_kernel", args.kernel)
+    head = [ir.op_init((1 << W) - 1)]
+
+    def window(run, op):
+        out = []
+        for n in (2, 18):
+            rec, data = program.encode(head + [op] * n)
+            run(rec, data)                                               # warm-up of this shape
+            eng.timer_begin()
+            run(rec, data)
+            out.append(eng.timer_end())
+        return (out[1] - out[0]) / 16.0
+
+    for t in (args.targets or (0, 5, W - 1)):
+        for release in (0, 1):
+            k1 = np.zeros((2, 2), dtype=np.complex128)
+            k1[0 if release else 1, 1] = 1.0
+            twin = ir.Op("kraus", qubits=(t,), table=np.array([np.diag([1.0 + 0j, 0.0]), k1]))
+            own = ir.Op("measure", target=t, mask=0, vals=(release,), table=(0.0, 0.0))
+            a, b = [], []
+            for _ in range(args.windows):
+                a.append(window(eng.density_exec_accept, own))
+                b.append(window(eng.density_exec, twin))
+            ma, mb = float(np.median(a)), float(np.median(b))
+            print(json.dumps({"part": "measure", "W": W, "t": t, "release": release, "windows": args.windows, "density_measure_kernel": -1 if args.kernel is None else args.kernel,
+                              "measure_record_ms": round(ma, 4), "measure_record_min_max": [round(min(a), 4), round(max(a), 4)],
+                              "measure_record_of_peak_at_24B": round(24.0 * 4 ** W / (ma * 1e-3) / PEAK, 3),
+                              "kraus_twin_ms": round(mb, 4), "kraus_twin_min_max": [round(min(b), 4), round(max(b), 4)],
+                              "kraus_twin_of_peak_at_32B": round(32.0 * 4 ** W / (mb * 1e-3) / PEAK, 3), "ratio": round(mb / ma, 3)}), flush=True)
+    eng.close()
+
+
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("part", choices=("graphs", "kernels"))
+    ap.add_argument("part", choices=("graphs", "kernels", "measure"))
     ap.add_argument("--reps", type=int, default=2)
     ap.add_argument("--shots", type=int, default=10000)
     ap.add_argument("--passes", type=int, default=2)
     ap.add_argument("--W", type=int, default=13)
     ap.add_argument("--rounds", type=int, default=2)
+    ap.add_argument("--windows", type=int, default=5)
+    ap.add_argument("--kernel", type=int, default=None, help="measure: engine option density_measure_kernel (1: k_dm_measure on every qubit; default: as the library routes the record)")
+    ap.add_argument("--targets", type=int, nargs="*", default=None, help="measure: the measured qubits (default 0, 5, W - 1)")
     ap.add_argument("--nontemporal", type=int, default=None, help="engine option of the same name (-1, 0, 1)")
     args = ap.parse_args()
     t0 = time.perf_counter()
-    (graphs if args.part == "graphs" else kernels)(args)
+    {"graphs": graphs, "kernels": kernels, "measure": measure}[args.part](args)
     print(json.dumps({"part": args.part, "wall_s": round(time.perf_counter() - t0, 1)}), flush=True)
 
 
