@@ -291,11 +291,17 @@ enum {
                        bit c it writes (0 <= c < 64), vals[1] = release (0 or 1: hand the qubit back in |0>), data_off points
                        to 2 doubles, P(flip | 0) and P(flip | 1) (always present; zeros: no readout error).  The contract
                        is below, next to the one of QSV_OP_KRAUS. */
-  QSV_OP_KRAUS2 = 12 /* two-qubit Kraus channel of m = vals[0] operators (1 <= m <= 16) on the distinct qubits qubits[0] and
+  QSV_OP_KRAUS2 = 12,/* two-qubit Kraus channel of m = vals[0] operators (1 <= m <= 16) on the distinct qubits qubits[0] and
                        qubits[1] (n = 2), qsv_noisy_sample only: data_off points to m x 32 doubles, each K_k (4 x 4) row-major
                        with (re, im) pairs, matrix index bit j on qubits[j], followed by m x 16 doubles, E_k = K_k^dg K_k packed
                        as its 4 real diagonal entries E00 E11 E22 E33, then its 6 upper off-diagonal entries (0,1) (0,2) (0,3)
                        (1,2) (1,3) (2,3) as (re, im).  The contract is below, behind the one of QSV_OP_KRAUS. */
+  QSV_OP_IF = 13,   /* guard over the next `span` records on the shot's classical word, qsv_noisy_sample only: n = span (>= 1; NOT a
+                       number of listed qubits, and not bounded by QSV_MAX_CTRL), mask = the classical bits compared, vals[0] and
+                       vals[1] = the low and the high 32 bits of the value they must read, target = negate (0 or 1).  qubits,
+                       data_off and angle are not read.  The contract is below, behind the one of QSV_OP_MEASURE. */
+  QSV_OP_RESET = 14 /* reset of qubits[0] (n = 1) to |0>, qsv_noisy_sample only: a MEASURE record with release = 1 that writes no
+                       classical bit and takes no readout draw.  vals and data_off are not read.  The contract is below. */
 };
 
 /* scheduling hint from the planner: close the current multi-gate pass before this gate (the
@@ -314,7 +320,8 @@ typedef struct {
   double   angle;                  /* MCPHASE                                              */
 } qsv_op;
 
-/* run a whole program in one call (one ctypes crossing per circuit); QSV_OP_PAULI, QSV_OP_KRAUS, QSV_OP_KRAUS2 and QSV_OP_MEASURE are refused */
+/* run a whole program in one call (one ctypes crossing per circuit); QSV_OP_PAULI, QSV_OP_KRAUS, QSV_OP_KRAUS2, QSV_OP_MEASURE,
+ * QSV_OP_IF and QSV_OP_RESET are refused */
 int qsv_exec(qsv_handle* h, const qsv_op* ops, int n_ops, const double* data, uint64_t n_data);
 
 /* ---- noisy shots: one trajectory per shot ------------------------------------------------ */
@@ -327,7 +334,8 @@ int qsv_exec(qsv_handle* h, const qsv_op* ops, int n_ops, const double* data, ui
  * state from |amp|^2, and records it as qsv_sample does:
  * out_bits[s] bit j = the value of qubit meas_qubits[j] (-1: bit j stays 0; NULL: the full basis index), each
  * measured bit flipped with probability readout[2j + value] (NULL: no readout error).
- * Kinds: INIT_ZERO, INIT_UNIFORM, 1Q, MCX, DIAG, MCPHASE, PAULI, KRAUS, KRAUS2, MEASURE; anything else returns QSV_E_UNSUPPORTED.
+ * Kinds: INIT_ZERO, INIT_UNIFORM, 1Q, MCX, DIAG, MCPHASE, PAULI, KRAUS, KRAUS2, MEASURE, IF, RESET; anything else returns
+ * QSV_E_UNSUPPORTED.
  * A KRAUS record on qubit t: u = the next draw of stream 0 (PAULI and KRAUS records share one draw counter, which
  * advances at every such record, m = 1 included); r00 = sum |a_i0|^2, r11 = sum |a_i1|^2, r10 = sum a_i1 conj(a_i0) over
  * the pairs (a_i0, a_i1) of t, total = r00 + r11; w_k = E00_k r00 + E11_k r11 + 2 Re(E01_k r10); the first k with w_k > 0
@@ -356,6 +364,21 @@ int qsv_exec(qsv_handle* h, const qsv_op* ops, int n_ops, const double* data, ui
  * again.  The final word is the word of the final draw ORed with these bits.  QSV_E_BADARG, with a message that names the
  * op: meas_qubits == NULL (full-index words) together with a MEASURE record, c >= n_meas, meas_qubits[c] >= 0 for a bit a
  * MEASURE record writes, a flip outside [0, 1], a release flag other than 0 or 1.
+ * An IF record with span, mask, value and negate: when the record is reached, hit = ((word & mask) == value) != negate, where
+ * word holds the bits that MEASURE records have written so far in this shot, as read (readout flip included: what a classical
+ * register of the device would hold); bits not yet written read 0, the bits of the final draw included.  If !hit, the next
+ * span records do nothing and take no draw: the draw counter of stream 0 does not advance, a skipped MEASURE record writes no
+ * bit, and the stream-3 ordinals of MEASURE and RESET records are positions in the program, which a skip cannot shift.  So a
+ * shot's draws behind the span depend on whether the span ran -- as they do on a device, where an error of a gate occurs only
+ * when the gate does.  QSV_E_BADARG, with a message that names the op: span < 1 or reaching past the last record, mask == 0,
+ * a value bit outside mask, a mask bit at or above n_meas, meas_qubits == NULL, negate other than 0 or 1, an IF or an INIT
+ * record inside a span (guards do not nest).  All of it is checked before the first launch.
+ * A RESET record on qubit t is the MEASURE contract with release = 1, except that no classical bit is written and no readout
+ * draw is taken: u = the draw (seed, shot, stream 3, d), d = the ordinal of the record among the MEASURE AND RESET records of
+ * the program (for every program without a RESET record that is the ordinal of MEASURE as it was); outcome, projection,
+ * rescaling and the move of the 1 half to the 0 half as there.  QSV_E_BADARG: n != 1, t at or above the width.
+ * Programs with an IF or a RESET record run kernels of their own (qsv_noise_dynamic.hip); with the diagnostic option
+ * noisy_dynamic_kernels every program does, and no word depends on that.
  * Random numbers are Philox-4x32-10 draws keyed by the seed and counted by (shot, stream, draw): shot s of a call
  * is the same whatever the number of shots or the grid.  Runs on the handle's stream (qsv_timer_* bracket it).
  * Replaces: simulator.run(T, shots=SHOTS, noise_model=...) of an Aer noise model of Pauli, one- and two-qubit Kraus errors. */
@@ -393,7 +416,9 @@ int qsv_noisy_sample_hbm(qsv_handle* h, const qsv_op* ops, int n_ops, const doub
  * (a bit may be written twice; only its last write may end a shot), if the bit it left in the word -- after the readout flip:
  * acceptance is on what was read -- differs from fix_val, the remaining records and the final draw of that shot are skipped.
  * Attempts that fail only on bits the final draw writes run to their end and are filtered.  The word of an abandoned shot is
- * never returned.
+ * never returned.  The decisive record is the last one in program order that writes the fixed bit, wherever it stands: the
+ * check sits behind an EXECUTED record, so where the span of an IF record skips that last writer nothing is abandoned, the
+ * shot runs to its end, and the predicate above, which the host applies to every word, decides.
  * `round` = attempts per launch, 0 = chosen by the library (about `shots` at first, later rounds from the acceptance seen so
  * far, at most 2^20).  Nothing the call returns depends on `round`, on the noisy_grid option or on whether a rejected
  * trajectory was abandoned.  With fix_mask = 0 and first_shot = 0, out_bits is the output of qsv_noisy_sample(_hbm) word for
@@ -423,7 +448,7 @@ int qsv_noisy_sample_accept(qsv_handle* h, const qsv_op* ops, int n_ops, const d
  * record's cumulative table, QSV_OP_KRAUS and QSV_OP_KRAUS2 as sum_k K_k rho K_k^dg (their E tables are not read; the
  * 16 x 16 superoperator of a KRAUS2 record is built once per record on the host and read from device memory).
  * Kinds: INIT_ZERO, INIT_UNIFORM, 1Q, MCX, DIAG, MCPHASE, PAULI (n = 1, 2), KRAUS (n = 1, 1..4 operators), KRAUS2 (n = 2, 1..16
- * operators); MUX, KQ, SWAP, MEASURE and
+ * operators); MUX, KQ, SWAP, MEASURE, IF, RESET and
  * handles of several shards or ranks return QSV_E_UNSUPPORTED; an odd n_qubits or a record qubit >= W QSV_E_BADARG.  Every
  * record is checked before the first one runs.
  * Replaces: simulator.run(T, noise_model=..., method="density_matrix") of Qiskit Aer. */
@@ -446,7 +471,9 @@ int qsv_density_exec(qsv_handle* h, const qsv_op* ops, int n_ops, const double* 
  * superoperator of sqrt(w0) |0><0| and sqrt(w1) |1><1| (release: |0><1|) -- option density_measure_kernel.
  * QSV_E_BADARG, with a message that names the op or the bit: t >= W, c >= 64, release not 0 or 1, a flip outside [0, 1] or
  * not finite, the data range outside the pool, a bit of fix_val outside fix_mask.  Every record is checked before the first
- * one runs.  With fix_mask = 0 and no MEASURE record the vector is bit for bit that of qsv_density_exec. */
+ * one runs.  With fix_mask = 0 and no MEASURE record the vector is bit for bit that of qsv_density_exec.
+ * QSV_OP_IF is refused (QSV_E_UNSUPPORTED: it would need branching), and so is QSV_OP_RESET as a kind: a reset comes as the
+ * MEASURE record above with release = 1 and a classical bit outside fix_mask, which is the reset channel exactly. */
 int qsv_density_exec_accept(qsv_handle* h, const qsv_op* ops, int n_ops, const double* data, uint64_t n_data,
                             uint64_t fix_mask, uint64_t fix_val);
 
@@ -544,6 +571,8 @@ int qsv_timer_end(qsv_handle* h, double* ms);
  *                                  1 from 2^26 amplitudes per shard, 2 from 2^14, 0 never        lane_map_min_l [26]  same for k_multi tiles other than bits 6..10
  *   noisy       noisy_grid [0]     workgroups of qsv_noisy_sample, qsv_noisy_sample_hbm and each round of qsv_noisy_sample_accept: 0 = as many as the
  *                                  chip holds at once, else at most this many
+ *               noisy_dynamic_kernels [0]  diagnostic: 1 sends every per-shot stream through the kernels of qsv_noise_dynamic.hip, which
+ *                                  streams with an IF or a RESET record run anyway; no word depends on it
  *   density     density_measure_kernel [-1]  a MEASURE record of qsv_density_exec_accept: -1 its own kernel (24 bytes per amplitude) from
  *                                  qubit 3 up, below that -- where the entries it skips share the lines of those it loads -- the same map as
  *                                  a two-operator superoperator through the KRAUS kernel (32); 0 always the latter; 1 always its own.

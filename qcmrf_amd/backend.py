@@ -208,8 +208,8 @@ class QsvBackend:
     noisy_measure  when a noisy shot measures: 'deferred' (default: every measurement at the end, one qubit per clique ancilla,
                 W = n + m + 1 for a QCMRF circuit) | 'in_place' (a mid-circuit measurement is taken when it occurs, as one
                 QSV_OP_MEASURE record, and its qubit recycled: n + 2 live qubits for any number of cliques; the trailing
-                measurements stay one joint final draw; same limits: <= 64 classical bits, no reset, no gate after a
-                measure, no classical conditions) | 'auto' (in place iff that makes the state narrower).  A shot's Pauli,
+                measurements stay one joint final draw; same limits: <= 64 classical bits; reset, gates after a measure and
+                classical conditions need ``dynamic``) | 'auto' (in place iff that makes the state narrower).  A shot's Pauli,
                 Kraus and readout draws are the same in both; 'density_matrix' has ``density_measure`` instead
     density_measure  (method 'density_matrix' only) when rho is measured: 'deferred' (default: every measurement at the end,
                 W = n + m + 1 for a QCMRF circuit, W <= 17 and <= 20 written classical bits) | 'in_place' (a mid-circuit
@@ -235,6 +235,17 @@ class QsvBackend:
     accept_max_attempts  attempts examined at most (default max(2^20, 1000 shots)); a RuntimeError names the rate seen if they
                 run out
     accept_round  attempts per launch (default 0: chosen by the library); no result depends on it
+    dynamic     False (default: every run as it is without the option) | True: a circuit that holds a ``reset``, a classically
+                conditioned instruction (``c_if``, ``if_test`` / ``if_else`` with an optional else body; equality of a bit or a
+                register with an integer) or a gate on a qubit measured earlier runs shot by shot on the device, under
+                ``noise_model`` or under an empty model when none is given (``QSV_OP_IF``, ``QSV_OP_RESET``; the noise ops of a
+                conditioned gate lie inside its guard, so its error occurs only when the gate does).  Measurements are taken in
+                place (metadata ``noisy_measure`` 'in_place'), ``noisy_state`` resolves on the live width (13 on chip, 24 in
+                slots), ``accept`` works as on any noisy run; metadata gains ``dynamic``, ``n_if_ops`` and ``n_reset_ops``.  A
+                circuit without any of it runs as without the option.  method 'density_matrix' runs resets exactly (conditions
+                and a measured qubit used again without a reset would need branching: ValueError).  Still refused, by a
+                ValueError that says why: ``post_select``, method 'trajectory', ``comm`` of several ranks, more than one
+                device, more than 64 classical bits, nested conditions, loops and ``switch``
     """
 
     def __init__(self, name="qasm_simulator", **options):
@@ -352,6 +363,11 @@ class QsvBackend:
             raise ValueError("unknown density_measure %r; a density matrix takes its measurements %s" % (dmeasure, ", ".join(_DENSITY_MEASURES)))
         if dmeasure is not None and method != "density_matrix":
             raise ValueError("density_measure belongs to method='density_matrix', not method=%r (noisy shots have noisy_measure)" % (method,))
+        if opts.get("dynamic"):
+            feats = [_ingest.ingest(c, dynamic=True) for c in circs]
+            if any(f.n_if or f.n_reset or f.n_reuse for f in feats):
+                return Job(Result(self._run_dynamic(circs, feats, int(shots), int(seed_simulator), opts, run_options, method, state,
+                                                    dmeasure), self._name))
         accept = self._accept_of(opts, len(circs), method)      # (first: it is the one that refuses the two together)
         post = self._post_select_of(opts, len(circs), method)
         if method == "density_matrix":
@@ -609,6 +625,171 @@ class QsvBackend:
         self.last_plan = None
         self._last_comm = None
         return {"name": getattr(circuit, "name", "circuit"), "shots": shots, "counts": counts, "metadata": meta}
+
+    # ---- dynamic=True: reset, classical conditions, measured qubits used again ---------------------------
+    def _run_dynamic(self, circs, feats, shots, seed, opts, run_options, method, state, dmeasure):
+        """the experiments of a ``run(dynamic=True)`` in which some circuit holds a reset, a condition or a gate on a measured
+        qubit (``feats``: its dynamic ingest without noise).  Such a circuit runs shot by shot through ``_run_noisy`` under the
+        given model or an empty one (method 'density_matrix': a circuit whose only dynamic feature is ``reset`` runs exactly,
+        the reset as the record ``qsv_density_exec_accept`` documents as the reset channel); a circuit of the batch without any
+        of it runs as without the option, under its own seed"""
+        if opts.get("post_select") is not None:
+            raise ValueError("post_select conditions the exact state vector of an ideal run; a dynamic circuit (dynamic=True: reset, "
+                             "classical conditions, measured qubits used again) runs shot by shot and has none: use accept")
+        if method == "trajectory":
+            raise ValueError("method='trajectory' follows the outcomes of a circuit without reset and conditions; a dynamic circuit "
+                             "(dynamic=True) runs shot by shot: method='statevector', or 'density_matrix' for resets alone")
+        comm = opts["comm"] or SingleProcess()
+        if comm.world > 1:
+            raise ValueError("dynamic circuits take one process (a process group of %d ranks was given; limit 1)" % comm.world)
+        if len(tuple(opts["devices"])) > 1:
+            raise ValueError("dynamic circuits take one device (%d were given; limit 1)" % len(tuple(opts["devices"])))
+        model = opts.get("noise_model")
+        if model is not None and not isinstance(model, _noise.NoiseModel):
+            raise TypeError("noise_model must be a qcmrf_amd.noise.NoiseModel, not %s" % type(model).__name__)
+        model = model if model is not None else _noise.NoiseModel()
+        accept = opts.get("accept")
+        if accept is not None:
+            if isinstance(accept, dict):
+                accept = [accept] * len(circs)
+            accept = list(accept)
+            if len(accept) != len(circs) or not all(isinstance(d, dict) for d in accept):
+                raise ValueError("accept is one {classical bit: 0 | 1} dict, or a list of %d of them (one per circuit)" % len(circs))
+        exps = []
+        for i, (c, f) in enumerate(zip(circs, feats)):
+            extra = {"dynamic": True, "n_if_ops": f.n_if, "n_reset_ops": f.n_reset}
+            if not (f.n_if or f.n_reset or f.n_reuse):
+                sub = dict(run_options, dynamic=False)
+                if accept is not None:
+                    sub["accept"] = accept[i]
+                exps.append(self.run(c, shots=shots, seed_simulator=seed + i, **sub).result().results[0])
+                continue
+            if f.num_clbits > 64:
+                raise ValueError("dynamic circuits record at most 64 classical bits, the circuit has %d" % f.num_clbits)
+            if method == "density_matrix":
+                prepared, place = self._prepare_density_dynamic(c, model, accept and accept[i])
+                exp = self._run_density(c, shots, seed + i, opts, prepared, accept=accept and accept[i], place=place)
+                extra["n_reset_ops"] = place["n_reset"]
+            else:
+                prepared = self._prepare_noisy_dynamic(c, model, state)
+                exp = self._run_noisy(c, shots, seed + i, opts, prepared, accept=accept and accept[i])
+                extra.update(n_if_ops=prepared[0].n_if, n_reset_ops=prepared[0].n_reset)
+            exp["metadata"].update(extra)
+            exps.append(exp)
+        return exps
+
+    @staticmethod
+    def _prepare_noisy_dynamic(circuit, model, state):
+        """``_prepare_noisy_in_place`` for a dynamic circuit: the ops of ``ingest(dynamic=True)`` under the model, remapped to
+        live slots by ``trajectory.plan_slots_dynamic``; every measure that is not part of the joint final draw is one
+        QSV_OP_MEASURE record, every reset that stays one QSV_OP_RESET record, every guard one QSV_OP_IF record.  There is no
+        deferred form, so the measurements are in place whatever noisy_measure says"""
+        from . import ir, trajectory
+        t0 = time.perf_counter()
+        ing = _ingest.ingest(circuit, noise=model, dynamic=True)
+        if ing.num_clbits > 64:
+            raise ValueError("dynamic circuits record at most 64 classical bits, the circuit has %d" % ing.num_clbits)
+        items, width, finals = trajectory.plan_slots_dynamic(ing.ops)
+        width = max(width, 1)
+        state = QsvBackend._resolve_noisy_state(state, width, " live at once with its measurements taken in place")
+        early = {item[2] for item in items if isinstance(item, tuple) and item[0] == "measure"}
+        late = [(s, c) for s, c in finals if c in early]    # a bit written earlier and again at the end: a record as well, so
+        finals = [(s, c) for s, c in finals if c not in early]   # that the last write wins
+        ops, n_measure, n_reset = [], 0, 0
+        for item in items:
+            if not isinstance(item, tuple):
+                ops.append(item)
+            elif item[0] == "measure":
+                _, s, c, release, q = item
+                ops.append(ir.Op("measure", target=s, mask=c, vals=(int(release),), table=model.readout_flips(q)))
+                n_measure += 1
+            else:
+                ops.append(ir.Op("reset", target=item[1]))
+                n_reset += 1
+        for s, c in late:
+            ops.append(ir.Op("measure", target=s, mask=c, vals=(0,), table=ing.readout.get(c)))
+            n_measure += 1
+        ing.ops = ops
+        ing.n_reset = n_reset                                # (a trailing reset is dropped)
+        clist = sorted(ing.measure)
+        meas = [-1] * (clist[-1] + 1) if clist else []
+        rec, data = program.encode(ops, n_meas=len(meas))
+        readout = np.zeros((len(meas), 2))
+        for s, c in finals:
+            meas[c] = s
+            readout[c] = ing.readout.get(c, (0.0, 0.0))
+        return ing, rec, data, clist, meas, readout, time.perf_counter() - t0, state, ("in_place", width, n_measure)
+
+    @staticmethod
+    def _prepare_density_dynamic(circuit, model, accept):
+        """(the tuple of ``_prepare_density``, place) for a dynamic circuit under method 'density_matrix': resets only.  A reset
+        becomes the MEASURE record with release = 1 whose classical bit no ``fix_mask`` holds (``qsv_density_exec_accept``: the
+        reset channel), the plan is ``trajectory.plan_slots_dynamic``; a mid-circuit measure follows the rule of
+        ``density_measure='in_place'`` (fixed by ``accept`` and written once).  Conditions, and a measured qubit used again
+        without a reset in between, would need branching and are refused"""
+        from . import ir, trajectory
+        t0 = time.perf_counter()
+        ing = _ingest.ingest(circuit, noise=model, dynamic=True)
+        if ing.n_if:
+            raise ValueError("method='density_matrix' runs the resets of a dynamic circuit, not its classical conditions (%d here): a "
+                             "density matrix cannot follow a measured bit without branching; run it shot by shot "
+                             "(method='statevector', dynamic=True)" % ing.n_if)
+        if ing.n_reuse:
+            raise ValueError("method='density_matrix': a measured qubit is used again without a reset in between (%d times); a density "
+                             "matrix cannot follow the measured bit without branching; run it shot by shot (method='statevector', "
+                             "dynamic=True)" % ing.n_reuse)
+        items, width, finals = trajectory.plan_slots_dynamic(ing.ops)
+        width = max(width, 1)
+        if width > _lib.DENSITY_MAX_QUBITS:
+            raise ValueError("method='density_matrix' holds rho of at most %d qubits (16 * 4^W bytes), the circuit has %d live at once "
+                             "with its measurements taken in place" % (_lib.DENSITY_MAX_QUBITS, width))
+        early = [item for item in items if isinstance(item, tuple) and item[0] == "measure"]
+        written = {}
+        for c in [item[2] for item in early] + [c for _, c in finals]:
+            written[c] = written.get(c, 0) + 1
+        for _, s, c, release, q in early:
+            if accept is not None and c in accept and accept[c] not in (0, 1):
+                raise ValueError("accept fixes classical bit %r to %r; a bit reads 0 or 1" % (c, accept[c]))
+            if accept is not None and c in accept and written[c] == 1:
+                continue
+            why = "is written %d times" % written[c] if accept is not None and c in accept else "is not fixed by accept"
+            raise ValueError("method='density_matrix', dynamic=True: classical bit %d is measured mid-circuit (qubit %d) and %s; a "
+                             "density matrix follows a measurement taken in place only where its outcome is fixed and written "
+                             "once: pass accept={%d: 0 or 1}" % (c, q, why, c))
+        final = dict((c, s) for s, c in finals)
+        clist = sorted(final)
+        if len(clist) > DENSITY_MAX_CLBITS:
+            raise ValueError("method='density_matrix' returns the distribution over at most %d written classical bits, the "
+                             "circuit's trailing measurements write %d" % (DENSITY_MAX_CLBITS, len(clist)))
+        every = sorted(ing.measure)
+        if every and every[-1] >= 64:
+            raise ValueError("method='density_matrix' records at most 64 classical bits, the circuit writes bit %d" % every[-1])
+        fm = fv = n_reset = 0
+        for _, s, c, release, q in early:
+            fm |= 1 << int(c)
+            fv |= int(accept[c]) << int(c)
+        free_bit = next((b for b in range(64) if not (fm >> b) & 1), None)
+        if free_bit is None and any(isinstance(item, tuple) and item[0] == "reset" for item in items):
+            raise ValueError("method='density_matrix': accept fixes all 64 classical bits, a reset needs one that is not fixed")
+        ops = []
+        for item in items:
+            if not isinstance(item, tuple):
+                ops.append(item)
+            elif item[0] == "measure":
+                _, s, c, release, q = item
+                ops.append(ir.Op("measure", target=s, mask=c, vals=(int(release),), table=model.readout_flips(q)))
+            else:                                            # the reset channel: outcome forgotten, the 1 half moved to 0
+                ops.append(ir.Op("measure", target=item[1], mask=free_bit, vals=(1,), table=None))
+                n_reset += 1
+        ing.ops = ops
+        rec, data = program.encode(ops)
+        meas = [-1] * (every[-1] + 1) if every else []
+        readout = np.zeros((len(meas), 2))
+        for c in clist:
+            meas[c] = final[c]
+            readout[c] = ing.readout.get(c, (0.0, 0.0))
+        place = {"mode": "in_place", "width": width, "n_measure": len(early), "fix": (fm, fv), "n_reset": n_reset}
+        return (ing, rec, data, clist, meas, readout, time.perf_counter() - t0), place
 
     # ---- method="density_matrix": rho of W qubits in a vector of 2W ---------------------------------
     @staticmethod

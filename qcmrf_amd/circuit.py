@@ -72,6 +72,16 @@ class Instruction:
         self.definition = definition
         self.condition = None
 
+    def c_if(self, classical, val):
+        """condition the instruction on ``classical`` (a Clbit or a classical register) reading the integer ``val``, as
+        qiskit.circuit.Instruction.c_if did before Qiskit 2.0: sets ``condition`` and returns the instruction"""
+        if not isinstance(classical, (Clbit, Register)):
+            raise TypeError("c_if takes a Clbit or a classical register, not %s" % type(classical).__name__)
+        if int(val) < 0:
+            raise ValueError("c_if compares with a non-negative integer, not %r" % (val,))
+        self.condition = (classical, int(val))
+        return self
+
     def inverse(self):
         if self.definition is not None:
             name = self.name[:-3] if self.name.endswith("_dg") else self.name + "_dg"
@@ -98,6 +108,73 @@ class Instruction:
 
     def __repr__(self):
         return "Instruction(name=%r, num_qubits=%d, params=%r)" % (self.name, self.num_qubits, self.params)
+
+
+class InstructionSet:
+    """what a gate method returns: the instructions it just added, so that ``qc.x(0).c_if(c, 1)`` reaches them
+    (counterpart of qiskit.circuit.InstructionSet)"""
+
+    def __init__(self, instructions):
+        self.instructions = list(instructions)
+
+    def c_if(self, classical, val):
+        for ci in self.instructions:
+            ci.operation.c_if(classical, val)
+        return self
+
+    def __len__(self):
+        return len(self.instructions)
+
+    def __getitem__(self, i):
+        return self.instructions[i]
+
+
+class IfElseOp(Instruction):
+    """``if_else`` on all qubits and clbits of the circuit it was opened in: ``condition`` = (Clbit or register, value),
+    ``blocks`` = (true body, else body or None), each a circuit over the same bits in the same order (counterpart of
+    qiskit.circuit.IfElseOp)"""
+
+    def __init__(self, condition, true_body, false_body=None):
+        super().__init__("if_else", true_body.num_qubits, true_body.num_clbits)
+        self.condition = condition
+        self.blocks = (true_body, false_body)
+
+
+class _ElseContext:
+    def __init__(self, circuit, op):
+        self._circuit, self._op = circuit, op
+
+    def __enter__(self):
+        if self._op.blocks[1] is not None:
+            raise ValueError("this if_test has an else body already")
+        self._circuit._open_body()
+        return None
+
+    def __exit__(self, exc_type, exc, tb):
+        body = self._circuit._close_body()
+        if exc_type is None:
+            self._op.blocks = (self._op.blocks[0], body)
+        return False
+
+
+class _IfContext:
+    """``with qc.if_test((c, 1)) as else_:`` -- the gates added inside go to the true body; ``with else_:`` opens the else body"""
+
+    def __init__(self, circuit, condition):
+        self._circuit, self._condition = circuit, condition
+
+    def __enter__(self):
+        self._circuit._open_body()
+        self._else = _ElseContext(self._circuit, None)
+        return self._else
+
+    def __exit__(self, exc_type, exc, tb):
+        body = self._circuit._close_body()
+        if exc_type is None:
+            op = IfElseOp(self._condition, body)
+            self._else._op = op
+            self._circuit._add(op, list(self._circuit.qubits), list(self._circuit.clbits))
+        return False
 
 
 class CircuitInstruction:
@@ -129,6 +206,7 @@ class QuantumCircuit:
         self._qindex = {id(b): i for i, b in enumerate(self.qubits)}
         self._cindex = {id(b): i for i, b in enumerate(self.clbits)}
         self.data = []
+        self._bodies = []                # open if_test bodies, innermost last: gates added meanwhile go there
 
     # ---- structure queries ---------------------------------------------------------
     @property
@@ -177,61 +255,83 @@ class QuantumCircuit:
     def _add(self, op, qubits, clbits=()):
         if len(set(id(q) for q in qubits)) != len(qubits):
             raise ValueError("duplicate qubit arguments in %s" % op.name)
-        self.data.append(CircuitInstruction(op, qubits, clbits))
-        return self.data[-1]
+        ci = CircuitInstruction(op, qubits, clbits)
+        (self._bodies[-1].data if self._bodies else self.data).append(ci)
+        return ci
+
+    def _open_body(self):
+        body = QuantumCircuit.__new__(QuantumCircuit)          # the same bit objects in the same order: a view, not a copy
+        body.name, body.global_phase = "if_body", 0.0
+        body._qreg, body._creg, body.qregs, body.cregs = self._qreg, self._creg, self.qregs, self.cregs
+        body.qubits, body.clbits, body._qindex, body._cindex = self.qubits, self.clbits, self._qindex, self._cindex
+        body.data, body._bodies = [], []
+        self._bodies.append(body)
+
+    def _close_body(self):
+        return self._bodies.pop()
 
     def _broadcast_1q(self, name, qubit, params=()):
-        for q in self._q(qubit):
-            self._add(Instruction(name, 1, 0, params), [q])
+        return InstructionSet([self._add(Instruction(name, 1, 0, params), [q]) for q in self._q(qubit)])
 
     # ---- gates -----------------------------------------------------------------------
-    def h(self, qubit): self._broadcast_1q("h", qubit)
-    def x(self, qubit): self._broadcast_1q("x", qubit)
-    def y(self, qubit): self._broadcast_1q("y", qubit)
-    def z(self, qubit): self._broadcast_1q("z", qubit)
-    def s(self, qubit): self._broadcast_1q("s", qubit)
-    def sdg(self, qubit): self._broadcast_1q("sdg", qubit)
-    def t(self, qubit): self._broadcast_1q("t", qubit)
-    def tdg(self, qubit): self._broadcast_1q("tdg", qubit)
-    def sx(self, qubit): self._broadcast_1q("sx", qubit)
-    def sxdg(self, qubit): self._broadcast_1q("sxdg", qubit)
-    def id(self, qubit): self._broadcast_1q("id", qubit)
-    def rx(self, theta, qubit): self._broadcast_1q("rx", qubit, [theta])
-    def ry(self, theta, qubit): self._broadcast_1q("ry", qubit, [theta])
-    def rz(self, phi, qubit): self._broadcast_1q("rz", qubit, [phi])
-    def p(self, lam, qubit): self._broadcast_1q("p", qubit, [lam])
-    def u(self, theta, phi, lam, qubit): self._broadcast_1q("u", qubit, [theta, phi, lam])
+    def h(self, qubit): return self._broadcast_1q("h", qubit)
+    def x(self, qubit): return self._broadcast_1q("x", qubit)
+    def y(self, qubit): return self._broadcast_1q("y", qubit)
+    def z(self, qubit): return self._broadcast_1q("z", qubit)
+    def s(self, qubit): return self._broadcast_1q("s", qubit)
+    def sdg(self, qubit): return self._broadcast_1q("sdg", qubit)
+    def t(self, qubit): return self._broadcast_1q("t", qubit)
+    def tdg(self, qubit): return self._broadcast_1q("tdg", qubit)
+    def sx(self, qubit): return self._broadcast_1q("sx", qubit)
+    def sxdg(self, qubit): return self._broadcast_1q("sxdg", qubit)
+    def id(self, qubit): return self._broadcast_1q("id", qubit)
+    def rx(self, theta, qubit): return self._broadcast_1q("rx", qubit, [theta])
+    def ry(self, theta, qubit): return self._broadcast_1q("ry", qubit, [theta])
+    def rz(self, phi, qubit): return self._broadcast_1q("rz", qubit, [phi])
+    def p(self, lam, qubit): return self._broadcast_1q("p", qubit, [lam])
+    def u(self, theta, phi, lam, qubit): return self._broadcast_1q("u", qubit, [theta, phi, lam])
 
     def cx(self, control, target):
-        self._add(Instruction("cx", 2), self._q(control) + self._q(target))
+        return InstructionSet([self._add(Instruction("cx", 2), self._q(control) + self._q(target))])
 
     def cz(self, control, target):
-        self._add(Instruction("cz", 2), self._q(control) + self._q(target))
+        return InstructionSet([self._add(Instruction("cz", 2), self._q(control) + self._q(target))])
 
     def swap(self, a, b):
-        self._add(Instruction("swap", 2), self._q(a) + self._q(b))
+        return InstructionSet([self._add(Instruction("swap", 2), self._q(a) + self._q(b))])
 
     def cp(self, theta, control, target):
-        self._add(Instruction("cp", 2, 0, [theta]), self._q(control) + self._q(target))
+        return InstructionSet([self._add(Instruction("cp", 2, 0, [theta]), self._q(control) + self._q(target))])
 
     def crz(self, theta, control, target):
-        self._add(Instruction("crz", 2, 0, [theta]), self._q(control) + self._q(target))
+        return InstructionSet([self._add(Instruction("crz", 2, 0, [theta]), self._q(control) + self._q(target))])
 
     def ccx(self, c1, c2, target):
-        self._add(Instruction("ccx", 3), self._q(c1) + self._q(c2) + self._q(target))
+        return InstructionSet([self._add(Instruction("ccx", 3), self._q(c1) + self._q(c2) + self._q(target))])
 
     def mcx(self, control_qubits, target_qubit):
         ctrls = self._q(control_qubits)
         tgt = self._q(target_qubit)
         name = {0: "x", 1: "cx", 2: "ccx"}.get(len(ctrls), "mcx")
-        self._add(Instruction(name, len(ctrls) + 1), ctrls + tgt)
+        return InstructionSet([self._add(Instruction(name, len(ctrls) + 1), ctrls + tgt)])
 
     def measure(self, qubit, cbit):
         qs, cs = self._q(qubit), self._c(cbit)
         if len(qs) != len(cs):
             raise ValueError("measure: %d qubits but %d clbits" % (len(qs), len(cs)))
-        for q, c in zip(qs, cs):
-            self._add(Instruction("measure", 1, 1), [q], [c])
+        return InstructionSet([self._add(Instruction("measure", 1, 1), [q], [c]) for q, c in zip(qs, cs)])
+
+    def reset(self, qubit):
+        """put ``qubit`` (or each of several) back in |0>"""
+        return InstructionSet([self._add(Instruction("reset", 1), [q]) for q in self._q(qubit)])
+
+    def if_test(self, condition):
+        """``with qc.if_test((clbit or register, value)) as else_:`` -- the gates added inside run only in the shots in which
+        the classical bit (or the register, as an integer) reads ``value``; ``with else_:`` afterwards holds what runs in the
+        others.  One ``if_else`` operation (IfElseOp) is appended when the block closes."""
+        if not (isinstance(condition, tuple) and len(condition) == 2):
+            raise TypeError("if_test takes a (Clbit or classical register, value) pair")
+        return _IfContext(self, condition)
 
     def barrier(self, *qargs):
         qs = self._q(qargs) if qargs else list(self.qubits)

@@ -268,6 +268,7 @@ struct qsv_handle {
   int opt_trace_passes = 0;           // 1: one stderr line per k_multi pass (R, mode, ops by update shape) -- a diagnostic
   int opt_pass_budget = 0;            // opt-in cap on the arithmetic of a general pass, percent of one read+write of the shard (0: none)
   int opt_noisy_grid = 0;             // qsv_noisy_sample: workgroups at most (0: as many as the chip holds at once)
+  int opt_noisy_dynamic_kernels = 0;  // diagnostic: 1 sends every per-shot stream through the kernels of qsv_noise_dynamic.hip (no result depends on it)
   uint64_t opt_xchunk = 1ull << 24;   // amplitudes per exchange chunk (256 MiB)
 };
 

@@ -110,6 +110,10 @@ static int dm_exec(qsv_handle* h, const qsv_op* ops, int n_ops, const double* da
   // every record is checked before anything runs: a refused program leaves the state as it was
   for (int i = 0; i < n_ops; ++i) {
     const qsv_op& o = ops[i];
+    if (o.kind == QSV_OP_IF)
+      return fail(QSV_E_UNSUPPORTED, "op %d: QSV_OP_IF (a guard on the shot's classical bits) runs in qsv_noisy_sample only; a density matrix cannot follow a measured bit without branching", i);
+    if (o.kind == QSV_OP_RESET)
+      return fail(QSV_E_UNSUPPORTED, "op %d: QSV_OP_RESET runs in qsv_noisy_sample only; qsv_density_exec_accept takes a reset as a QSV_OP_MEASURE record with release = 1 whose bit is outside fix_mask", i);
     if (o.n < 0 || o.n > QSV_MAX_CTRL) return fail(QSV_E_BADARG, "op %d: n=%d out of range", i, o.n);
     switch (o.kind) {
       case QSV_OP_INIT_ZERO: break;

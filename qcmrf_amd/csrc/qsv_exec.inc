@@ -31,7 +31,7 @@ extern "C" int qsv_exec(qsv_handle* h, const qsv_op* ops, int n_ops, const doubl
   for (int i = 0; i < n_ops; ++i) {
     const qsv_op& o = ops[i];
     h->exec_ops_left = n_ops - i;
-    if (o.n < 0 || o.n > QSV_MAX_CTRL) return fail(QSV_E_BADARG, "op %d: n=%d out of range", i, o.n);
+    if (o.kind != QSV_OP_IF && (o.n < 0 || o.n > QSV_MAX_CTRL)) return fail(QSV_E_BADARG, "op %d: n=%d out of range", i, o.n);   // an IF record's n is its span
     const double* d = data ? data + o.data_off : nullptr;
     auto need = [&](uint64_t cnt) -> int {
       if (!data || o.data_off + cnt > n_data) return fail(QSV_E_BADARG, "op %d: data range [%llu,+%llu) outside pool of %llu", i,
@@ -140,6 +140,10 @@ extern "C" int qsv_exec(qsv_handle* h, const qsv_op* ops, int n_ops, const doubl
         return fail(QSV_E_BADARG, "op %d: QSV_OP_KRAUS2 (a two-qubit Kraus channel) runs in qsv_noisy_sample only, not in qsv_exec", i);
       case QSV_OP_MEASURE:
         return fail(QSV_E_BADARG, "op %d: QSV_OP_MEASURE (a measurement taken in place) runs in qsv_noisy_sample only, not in qsv_exec", i);
+      case QSV_OP_IF:
+        return fail(QSV_E_BADARG, "op %d: QSV_OP_IF (a guard on the shot's classical bits) runs in qsv_noisy_sample only, not in qsv_exec", i);
+      case QSV_OP_RESET:
+        return fail(QSV_E_BADARG, "op %d: QSV_OP_RESET (a reset taken in place) runs in qsv_noisy_sample only, not in qsv_exec", i);
       default:
         return fail(QSV_E_BADARG, "op %d: unknown kind %d", i, o.kind);
     }
@@ -208,17 +212,48 @@ static int nz_check_meas(qsv_handle* h, const int* meas_qubits, int n_meas, cons
 // validates every record and appends its compact form to cops, its tables to pool; a MEASURE record is checked against the
 // measurement map it writes beside (meas_qubits, n_meas).  fix_mask (qsv_noisy_sample_accept; 0 elsewhere, and the stream is
 // then what it was without the parameter): the last MEASURE record to write a bit of it is marked NZ_DECISIVE -- a bit may be
-// written twice, and only its last write may end a shot.  *written (may be NULL): the bits MEASURE records write.
+// written twice, and only its last write may end a shot, wherever the record stands: one inside the span of an IF record may be
+// skipped, and then abandons nothing.  *written (may be NULL): the bits MEASURE records write.  *has_dynamic: the stream
+// holds an IF or a RESET record; every check of QSV_OP_IF is made here, before anything is staged or launched.
 static int nz_encode(qsv_handle* h, const qsv_op* ops, int n_ops, const double* data, uint64_t n_data, const int* meas_qubits,
                      int n_meas, std::vector<NzOp>& cops, NzPool& pool, bool* has_kraus, bool* has_measure, bool* has_kraus2,
-                     uint64_t fix_mask = 0, uint64_t* written = nullptr) {
+                     bool* has_dynamic, uint64_t fix_mask = 0, uint64_t* written = nullptr) {
   cops.reserve(n_ops);
   *has_kraus = false;
   *has_measure = false;
   *has_kraus2 = false;
-  uint32_t n_measure = 0;
+  *has_dynamic = false;
+  uint32_t n_measure = 0;                                  // MEASURE and RESET records so far: the draw numbers of stream 3
+  int span_end = 0, span_of = -1;                          // records below span_end lie in the span of IF record span_of
   for (int i = 0; i < n_ops; ++i) {
     const qsv_op& o = ops[i];
+    if (o.kind == QSV_OP_IF) {                             // n is the span, not a number of listed qubits
+      if (i < span_end) return fail(QSV_E_BADARG, "op %d: QSV_OP_IF inside the span of the QSV_OP_IF record %d (guards do not nest)", i, span_of);
+      if (o.n < 1) return fail(QSV_E_BADARG, "op %d: QSV_OP_IF guards a span of %d records, not at least 1", i, o.n);
+      if ((int64_t)i + o.n >= (int64_t)n_ops) return fail(QSV_E_BADARG, "op %d: QSV_OP_IF guards %d records, %d follow it", i, o.n, n_ops - 1 - i);
+      if (!meas_qubits) return fail(QSV_E_BADARG, "op %d: QSV_OP_IF reads classical bits and needs meas_qubits (full-index words have none)", i);
+      if (o.mask == 0) return fail(QSV_E_BADARG, "op %d: QSV_OP_IF compares no classical bit (mask = 0)", i);
+      const uint64_t value = (uint64_t)(uint32_t)o.vals[0] | ((uint64_t)(uint32_t)o.vals[1] << 32);
+      if (value & ~o.mask) return fail(QSV_E_BADARG, "op %d: QSV_OP_IF value %#llx has bits outside its mask %#llx", i, (unsigned long long)value, (unsigned long long)o.mask);
+      if (n_meas < 64 && (o.mask >> n_meas))
+        return fail(QSV_E_BADARG, "op %d: QSV_OP_IF mask %#llx reads a classical bit outside the %d bits of the call", i, (unsigned long long)o.mask, n_meas);
+      if (o.target != 0 && o.target != 1) return fail(QSV_E_BADARG, "op %d: QSV_OP_IF negate flag %d is not 0 or 1", i, o.target);
+      NzOp c;
+      memset(&c, 0, sizeof c);
+      c.kind = NZ_IF;
+      c.target = (uint8_t)o.target;
+      c.cmask = (uint32_t)o.n;
+      c.cval = (uint32_t)o.mask;
+      c.off = (uint32_t)(o.mask >> 32);
+      c.ql8 = value;
+      cops.push_back(c);
+      span_end = i + 1 + o.n;
+      span_of = i;
+      *has_dynamic = true;
+      continue;
+    }
+    if (i < span_end && (o.kind == QSV_OP_INIT_ZERO || o.kind == QSV_OP_INIT_UNIFORM))
+      return fail(QSV_E_BADARG, "op %d: an INIT record inside the span of the QSV_OP_IF record %d", i, span_of);
     if (o.n < 0 || o.n > QSV_MAX_CTRL) return fail(QSV_E_BADARG, "op %d: n=%d out of range", i, o.n);
     const double* d = data ? data + o.data_off : nullptr;
     auto need = [&](uint64_t cnt) -> int {
@@ -357,8 +392,18 @@ static int nz_encode(qsv_handle* h, const qsv_op* ops, int n_ops, const double* 
         *has_measure = true;
         break;
       }
+      case QSV_OP_RESET: {
+        if (o.n != 1) return fail(QSV_E_BADARG, "op %d: QSV_OP_RESET resets 1 qubit, not %d", i, o.n);
+        CHK(check_qubit(h, o.qubits[0], "QSV_OP_RESET"));
+        c.kind = NZ_RESET;
+        c.target = (uint8_t)o.qubits[0];
+        c.cmask = 1u << 8;                                 // release, where a MEASURE record has it
+        c.cval = n_measure++;                              // the draw number of stream NZ_STREAM_MEASURE
+        *has_dynamic = true;
+        break;
+      }
       default:
-        return fail(QSV_E_UNSUPPORTED, "op %d: kind %d is not supported by noisy shots (INIT, 1Q, MCX, DIAG, MCPHASE, PAULI, KRAUS, KRAUS2, MEASURE only)", i, o.kind);
+        return fail(QSV_E_UNSUPPORTED, "op %d: kind %d is not supported by noisy shots (INIT, 1Q, MCX, DIAG, MCPHASE, PAULI, KRAUS, KRAUS2, MEASURE, IF, RESET only)", i, o.kind);
     }
     cops.push_back(c);
   }
@@ -408,9 +453,9 @@ static int nz_stage(Shard& s, const std::vector<NzOp>& cops, const std::vector<d
 // records -> compact records, pool and measurement map of one call
 static int nz_prepare(qsv_handle* h, const qsv_op* ops, int n_ops, const double* data, uint64_t n_data, const int* meas_qubits,
                       int n_meas, const double* readout, std::vector<NzOp>& cops, NzPool& pool, bool* has_kraus, bool* has_measure,
-                      bool* has_kraus2, NzMeas* meas, uint64_t fix_mask = 0, uint64_t* written = nullptr) {
+                      bool* has_kraus2, bool* has_dynamic, NzMeas* meas, uint64_t fix_mask = 0, uint64_t* written = nullptr) {
   CHK(nz_check_meas(h, meas_qubits, n_meas, readout));
-  CHK(nz_encode(h, ops, n_ops, data, n_data, meas_qubits, n_meas, cops, pool, has_kraus, has_measure, has_kraus2, fix_mask, written));
+  CHK(nz_encode(h, ops, n_ops, data, n_data, meas_qubits, n_meas, cops, pool, has_kraus, has_measure, has_kraus2, has_dynamic, fix_mask, written));
   meas->n = meas_qubits ? n_meas : -1;
   meas->readout = -1;
   meas->pos = nullptr;
@@ -431,9 +476,9 @@ static int nz_run(qsv_handle* h, const qsv_op* ops, int n_ops, const double* dat
   if (h->W > max_w) return fail(QSV_E_BADARG, "noisy shots keep one %d-qubit state per trajectory in %s: at most %d qubits", h->W, where, max_w);
   std::vector<NzOp> cops;
   NzPool pool;
-  bool has_kraus = false, has_measure = false, has_kraus2 = false;
+  bool has_kraus = false, has_measure = false, has_kraus2 = false, has_dynamic = false;
   NzCall c;
-  CHK(nz_prepare(h, ops, n_ops, data, n_data, meas_qubits, n_meas, readout, cops, pool, &has_kraus, &has_measure, &has_kraus2, &c.meas));
+  CHK(nz_prepare(h, ops, n_ops, data, n_data, meas_qubits, n_meas, readout, cops, pool, &has_kraus, &has_measure, &has_kraus2, &has_dynamic, &c.meas));
   if (shots == 0) return QSV_OK;
   Shard& s = h->shards[0];
   CHK(shard_set(s));
@@ -450,6 +495,7 @@ static int nz_run(qsv_handle* h, const qsv_op* ops, int n_ops, const double* dat
   c.d_out = st.out;
   c.measure = has_measure;
   c.kraus2 = has_kraus2;
+  c.dynamic = has_dynamic || h->opt_noisy_dynamic_kernels;
   const int rc = launch(s, c, has_kraus);
   hipError_t e = hipSuccess;
   if (rc == QSV_OK) e = hipMemcpyAsync(out_bits, c.d_out, shots * sizeof(uint64_t), hipMemcpyDeviceToHost, s.stream);
@@ -576,10 +622,10 @@ extern "C" int qsv_noisy_sample_accept(qsv_handle* h, const qsv_op* ops, int n_o
                 hbm ? "a slot of device memory" : "LDS", max_w);
   std::vector<NzOp> cops;
   NzPool pool;
-  bool has_kraus = false, has_measure = false, has_kraus2 = false;
+  bool has_kraus = false, has_measure = false, has_kraus2 = false, has_dynamic = false;
   uint64_t written = 0;
   NzCall c;
-  CHK(nz_prepare(h, ops, n_ops, data, n_data, meas_qubits, n_meas, readout, cops, pool, &has_kraus, &has_measure, &has_kraus2, &c.meas,
+  CHK(nz_prepare(h, ops, n_ops, data, n_data, meas_qubits, n_meas, readout, cops, pool, &has_kraus, &has_measure, &has_kraus2, &has_dynamic, &c.meas,
                  fix_mask, &written));
   CHK(nz_check_accept(h, meas_qubits, n_meas, fix_mask, fix_val, written));
   if (shots == 0) return QSV_OK;
@@ -602,6 +648,7 @@ extern "C" int qsv_noisy_sample_accept(qsv_handle* h, const qsv_op* ops, int n_o
   c.d_out = st.out;
   c.measure = has_measure;
   c.kraus2 = has_kraus2;
+  c.dynamic = has_dynamic || h->opt_noisy_dynamic_kernels;
   // and the slots: as a plain call of max(64, 4 shots) shots would size them, so that a call for a few shots does not take the
   // memory of a full grid; a round of more attempts runs them in these
   NzSlots slots;
@@ -763,6 +810,7 @@ extern "C" int qsv_set_option(qsv_handle* h, const char* name, int value) {
   else if (!strcmp(name, "pass_max_ops")) { if (value < 1 || value > 512) return fail(QSV_E_BADARG, "pass_max_ops out of range"); h->opt_pass_max_ops = value; }
   else if (!strcmp(name, "single_shortcut")) h->opt_single_shortcut = value != 0;
   else if (!strcmp(name, "trace_passes")) h->opt_trace_passes = value != 0;
+  else if (!strcmp(name, "noisy_dynamic_kernels")) { if (value < 0 || value > 1) return fail(QSV_E_BADARG, "noisy_dynamic_kernels not 0 or 1"); h->opt_noisy_dynamic_kernels = value; }
   else if (!strcmp(name, "noisy_grid")) { if (value < 0) return fail(QSV_E_BADARG, "noisy_grid < 0"); h->opt_noisy_grid = value; }
   else if (!strcmp(name, "pass_budget")) { if (value < 0) return fail(QSV_E_BADARG, "pass_budget < 0"); h->opt_pass_budget = value; }
   else if (!strcmp(name, "fold_init_h")) h->opt_fold_init_h = value != 0;

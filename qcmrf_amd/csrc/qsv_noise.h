@@ -9,7 +9,7 @@
 #define QSV_NZ_WAVE_MAXW 10       // up to here one wavefront per trajectory (no workgroup barriers)
 #define QSV_NZ_KRAUS_1PAIR_MAXW 7 // up to here a lane owns at most one pair of a Kraus op's target (2^6 pairs, 64 lanes)
 
-enum { NZ_INIT = 0, NZ_1Q, NZ_MCX, NZ_DIAG, NZ_MCPHASE, NZ_PAULI, NZ_KRAUS, NZ_MEASURE, NZ_KRAUS2 };
+enum { NZ_INIT = 0, NZ_1Q, NZ_MCX, NZ_DIAG, NZ_MCPHASE, NZ_PAULI, NZ_KRAUS, NZ_MEASURE, NZ_KRAUS2, NZ_IF, NZ_RESET };
 
 // One op of the compact stream, 32 bytes: every trajectory reads the whole list, so a record is a quarter of an
 // L2 line instead of the 168 bytes of a qsv_op.  Both paths read this record: qubits < 256, masks of 32 bits (the slot path
@@ -25,11 +25,15 @@ struct NzOp {
                        // MEASURE: cmask = classical bit | release << 8 | decisive << 9 (NZ_DECISIVE, set for
                        // qsv_noisy_sample_accept only), cval = the record's ordinal among the MEASURE records
                        // KRAUS2: cmask = its qubit 1 (matrix index bit 1)
+                       // RESET: a MEASURE record that writes no bit: cmask = release << 8 (always set), cval = the record's
+                       // ordinal among the MEASURE and RESET records; off is not read
+                       // IF: target = negate, cmask = span, (cval, off) = the low and high half of the 64-bit mask -- span
+                       // and mask, what the branch waits for, in the first 16 bytes --, ql8 = the 64-bit value
   uint32_t off;        // into the pool (doubles): 1Q 8 = m00 m01 m10 m11; DIAG 2^n complex; MCPHASE (cos, sin);
                        // INIT the amplitude value; PAULI 4^n cumulative probabilities; KRAUS n x 8 = the K_k as 1Q, then
                        // n x 4 = (E00, E11, Re E01, Im E01) of E_k = K_k^dg K_k; MEASURE 2 = P(flip | 0), P(flip | 1);
                        // KRAUS2 n x 32 = the K_k (4 x 4, row-major, re / im), then n x 16 = the packed E_k of QSV_OP_KRAUS2
-  uint64_t ql8;        // DIAG: listed qubit b = 8..15 in bits [8 (b - 8), 8 (b - 8) + 8)
+  uint64_t ql8;        // DIAG: listed qubit b = 8..15 in bits [8 (b - 8), 8 (b - 8) + 8); IF: the value compared
   uint64_t pad2;
 };
 static_assert(sizeof(NzOp) == 32, "NzOp is 32 bytes");
@@ -83,6 +87,8 @@ struct NzCall {
   uint64_t* d_out;
   bool measure;             // the stream holds an NZ_MEASURE op: a kernel instantiation that knows the kind is launched
   bool kraus2;              // the stream holds an NZ_KRAUS2 op: the kernels of qsv_noise_kraus2.hip, which know every kind
+  bool dynamic;             // the stream holds an NZ_IF or NZ_RESET op (or the option noisy_dynamic_kernels is set): the kernels
+                            // of qsv_noise_dynamic.hip, which know those two besides every other kind
 };
 
 // what an accept-aware launch takes besides: it runs the shots first_shot + [0, shots) and writes shot first_shot + i to
@@ -107,3 +113,7 @@ hipError_t qsv_noise_launch_accept(const NzLaunch& l, const NzAccept& a, unsigne
 // the same two for a stream that holds an NZ_KRAUS2 op (qsv_noise_kraus2.hip); the launchers above come here by themselves
 hipError_t qsv_noise_launch_kraus2(const NzLaunch& l, unsigned* grid);
 hipError_t qsv_noise_launch_accept_kraus2(const NzLaunch& l, const NzAccept& a, unsigned* grid);
+// the same two for a stream with l.dynamic (qsv_noise_dynamic.hip); qsv_noise_launch and qsv_noise_launch_accept come here by
+// themselves, before they look at l.kraus2
+hipError_t qsv_noise_launch_dynamic(const NzLaunch& l, unsigned* grid);
+hipError_t qsv_noise_launch_accept_dynamic(const NzLaunch& l, const NzAccept& a, unsigned* grid);

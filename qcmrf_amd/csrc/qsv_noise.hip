@@ -25,6 +25,7 @@ hipError_t qsv_noise_launch(const NzLaunch& l, unsigned* grid) {
   *grid = 0;
   if (l.W < 1 || l.W > QSV_NZ_MAXW) return hipErrorInvalidValue;
   if (l.shots == 0) return hipSuccess;
+  if (l.dynamic) return qsv_noise_launch_dynamic(l, grid);         // kernels of their own (qsv_noise_dynamic.hip)
   if (l.kraus2) return qsv_noise_launch_kraus2(l, grid);           // kernels of their own (qsv_noise_kraus2.hip)
   if (l.measure) return qsv_noise_launch_measure(l, grid);         // kernels of their own (qsv_noise_measure.hip)
   if (l.kraus) {

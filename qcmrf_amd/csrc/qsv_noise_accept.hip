@@ -16,6 +16,7 @@ hipError_t qsv_noise_launch_accept(const NzLaunch& l, const NzAccept& a, unsigne
   *grid = 0;
   if (l.W < 1 || l.W > QSV_NZ_MAXW) return hipErrorInvalidValue;
   if (l.shots == 0) return hipSuccess;
+  if (l.dynamic) return qsv_noise_launch_accept_dynamic(l, a, grid); // kernels of their own (qsv_noise_dynamic.hip)
   if (l.kraus2) return qsv_noise_launch_accept_kraus2(l, a, grid);  // kernels of their own (qsv_noise_kraus2.hip)
   if (l.W <= QSV_NZ_KRAUS_1PAIR_MAXW) return nz_lds_launch(k_noisy_accept<64, 1>, 64, l, grid, a);
   return l.W <= QSV_NZ_WAVE_MAXW ? nz_lds_launch(k_noisy_accept<64, 8>, 64, l, grid, a) : nz_lds_launch(k_noisy_accept<256, 1>, 256, l, grid, a);
@@ -25,6 +26,7 @@ hipError_t qsv_noise_hbm_launch_accept(const NzHbmLaunch& l, const NzAccept& a) 
   if (l.W < 1 || l.W > QSV_NZ_HBM_MAXW || !l.d_slots) return hipErrorInvalidValue;
   if (l.shots == 0) return hipSuccess;
   if (l.grid < 1 || (uint64_t)l.grid > l.shots) return hipErrorInvalidValue;
+  if (l.dynamic) return qsv_noise_hbm_launch_accept_dynamic(l, a);  // a kernel of its own (qsv_noise_dynamic.hip)
   if (l.kraus2) return qsv_noise_hbm_launch_accept_kraus2(l, a);   // a kernel of its own (qsv_noise_kraus2.hip)
   hipLaunchKernelGGL((k_noisy_hbm_accept<QSV_NZ_HBM_TPB>), dim3(l.grid), dim3(QSV_NZ_HBM_TPB), 0, l.stream, l.d_ops, l.n_ops,
                      l.d_pool, l.W, l.shots, l.seed, l.meas, l.d_slots, l.d_out, a);

@@ -24,3 +24,6 @@ hipError_t qsv_noise_hbm_launch_accept(const NzHbmLaunch& l, const NzAccept& a);
 // themselves
 hipError_t qsv_noise_hbm_launch_kraus2(const NzHbmLaunch& l);
 hipError_t qsv_noise_hbm_launch_accept_kraus2(const NzHbmLaunch& l, const NzAccept& a);
+// the same two for a stream with l.dynamic (qsv_noise_dynamic.hip), after their checks and before l.kraus2 is looked at
+hipError_t qsv_noise_hbm_launch_dynamic(const NzHbmLaunch& l);
+hipError_t qsv_noise_hbm_launch_accept_dynamic(const NzHbmLaunch& l, const NzAccept& a);

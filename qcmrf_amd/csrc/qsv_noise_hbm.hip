@@ -29,6 +29,7 @@ hipError_t qsv_noise_hbm_launch(const NzHbmLaunch& l) {
   if (l.W < 1 || l.W > QSV_NZ_HBM_MAXW || !l.d_slots) return hipErrorInvalidValue;
   if (l.shots == 0) return hipSuccess;
   if (l.grid < 1 || (uint64_t)l.grid > l.shots) return hipErrorInvalidValue;
+  if (l.dynamic) return qsv_noise_hbm_launch_dynamic(l);          // a kernel of its own (qsv_noise_dynamic.hip)
   if (l.kraus2) return qsv_noise_hbm_launch_kraus2(l);            // a kernel of its own (qsv_noise_kraus2.hip)
   if (l.measure) return qsv_noise_hbm_launch_measure(l);          // a kernel of its own (qsv_noise_measure.hip)
   hipLaunchKernelGGL((k_noisy_hbm<QSV_NZ_HBM_TPB, false>), dim3(l.grid), dim3(QSV_NZ_HBM_TPB), 0, l.stream, l.d_ops, l.n_ops, l.d_pool,

@@ -11,7 +11,7 @@ template <int TPB, bool MEAS>
 __global__ __launch_bounds__(TPB) void k_noisy_hbm(const NzOp* __restrict__ ops, int n_ops, const double* __restrict__ pool,
                                                    int W, uint64_t shots, uint64_t seed, NzMeas meas, char* slots,
                                                    uint64_t* __restrict__ out) {
-  constexpr bool ACC = false, K2 = false;
+  constexpr bool ACC = false, K2 = false, DYN = false;
   constexpr uint64_t first = 0, fix_val = 0;
 #include "qsv_noise_hbm_shots.inc"
 }
@@ -21,7 +21,7 @@ template <int TPB>
 __global__ __launch_bounds__(TPB) void k_noisy_hbm_accept(const NzOp* __restrict__ ops, int n_ops, const double* __restrict__ pool,
                                                           int W, uint64_t shots, uint64_t seed, NzMeas meas, char* slots,
                                                           uint64_t* __restrict__ out, NzAccept a) {
-  constexpr bool MEAS = true, ACC = true, K2 = false;
+  constexpr bool MEAS = true, ACC = true, K2 = false, DYN = false;
   const uint64_t first = a.first_shot, fix_val = a.fix_val;
 #include "qsv_noise_hbm_shots.inc"
 }

@@ -7,6 +7,7 @@
 // sits right behind the barrier in which nz_apply ends, which also orders the workgroup's loads of the slot before the stores
 // of the next |0..0>.  The scratch of the final draw (fd_*) is touched by the final draw alone, and a shot that runs it leaves
 // it behind its own closing barrier, so a shot that skips it finds and leaves nothing pending there.
+// DYN (the including kernel has it in scope too): IF records skip as qsv_noise_lds_shots.inc skips them.
   static_assert(TPB % 64 == 0 && TPB >= 64, "whole waves");
   constexpr int NW = TPB / 64;
   __shared__ double fd_wsum[NW];
@@ -24,7 +25,15 @@
     bool dead = false;
     for (int k = 0; k < n_ops; ++k) {
       const NzOp o = nz_fetch(ops, k);
-      nz_apply<TPB, QSV_NZ_HBM_B, 1, MEAS, K2>(st, N, o, pool, tid, seed, shot, draw, mword);
+      if constexpr (DYN) {
+        if (o.kind == NZ_IF) {                                       // span and mask are in the record's first 16 bytes
+          const uint64_t mask = (uint64_t)o.cval | ((uint64_t)o.off << 32);
+          const bool hit = ((mword & mask) == o.ql8) != (o.target != 0u);
+          k += (int)__builtin_amdgcn_readfirstlane(hit ? 0u : o.cmask);   // every thread holds mword alike: say so, k stays scalar
+          continue;
+        }
+      }
+      nz_apply<TPB, QSV_NZ_HBM_B, 1, MEAS, K2, DYN>(st, N, o, pool, tid, seed, shot, draw, mword);
       if constexpr (ACC) {
         if (o.kind == NZ_MEASURE && (o.cmask & NZ_DECISIVE) && (((mword ^ fix_val) >> (o.cmask & 63u)) & 1ull)) {
           dead = true;

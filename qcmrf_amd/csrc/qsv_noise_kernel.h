@@ -10,7 +10,7 @@ template <int TPB, int KRAUS, bool MEAS>
 __global__ __launch_bounds__(TPB) void k_noisy(const NzOp* __restrict__ ops, int n_ops, const double* __restrict__ pool,
                                                int W, uint64_t shots, uint64_t seed, NzMeas meas,
                                                uint64_t* __restrict__ out) {
-  constexpr bool ACC = false, K2 = false;
+  constexpr bool ACC = false, K2 = false, DYN = false;
   constexpr uint64_t first = 0, fix_val = 0;
 #include "qsv_noise_lds_shots.inc"
 }
@@ -20,7 +20,7 @@ template <int TPB, int KRAUS>
 __global__ __launch_bounds__(TPB) void k_noisy_accept(const NzOp* __restrict__ ops, int n_ops, const double* __restrict__ pool,
                                                       int W, uint64_t shots, uint64_t seed, NzMeas meas,
                                                       uint64_t* __restrict__ out, NzAccept a) {
-  constexpr bool MEAS = true, ACC = true, K2 = false;
+  constexpr bool MEAS = true, ACC = true, K2 = false, DYN = false;
   const uint64_t first = a.first_shot, fix_val = a.fix_val;
 #include "qsv_noise_lds_shots.inc"
 }

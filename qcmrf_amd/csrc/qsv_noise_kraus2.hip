@@ -12,7 +12,7 @@ template <int TPB, int KRAUS>
 __global__ __launch_bounds__(TPB) void k_noisy_k2(const NzOp* __restrict__ ops, int n_ops, const double* __restrict__ pool,
                                                   int W, uint64_t shots, uint64_t seed, NzMeas meas,
                                                   uint64_t* __restrict__ out) {
-  constexpr bool MEAS = true, ACC = false, K2 = true;
+  constexpr bool MEAS = true, ACC = false, K2 = true, DYN = false;
   constexpr uint64_t first = 0, fix_val = 0;
 #include "qsv_noise_lds_shots.inc"
 }
@@ -21,7 +21,7 @@ template <int TPB, int KRAUS>
 __global__ __launch_bounds__(TPB) void k_noisy_k2_accept(const NzOp* __restrict__ ops, int n_ops, const double* __restrict__ pool,
                                                          int W, uint64_t shots, uint64_t seed, NzMeas meas,
                                                          uint64_t* __restrict__ out, NzAccept a) {
-  constexpr bool MEAS = true, ACC = true, K2 = true;
+  constexpr bool MEAS = true, ACC = true, K2 = true, DYN = false;
   const uint64_t first = a.first_shot, fix_val = a.fix_val;
 #include "qsv_noise_lds_shots.inc"
 }
@@ -30,7 +30,7 @@ template <int TPB>
 __global__ __launch_bounds__(TPB) void k_noisy_hbm_k2(const NzOp* __restrict__ ops, int n_ops, const double* __restrict__ pool,
                                                       int W, uint64_t shots, uint64_t seed, NzMeas meas, char* slots,
                                                       uint64_t* __restrict__ out) {
-  constexpr bool MEAS = true, ACC = false, K2 = true;
+  constexpr bool MEAS = true, ACC = false, K2 = true, DYN = false;
   constexpr uint64_t first = 0, fix_val = 0;
 #include "qsv_noise_hbm_shots.inc"
 }
@@ -39,7 +39,7 @@ template <int TPB>
 __global__ __launch_bounds__(TPB) void k_noisy_hbm_k2_accept(const NzOp* __restrict__ ops, int n_ops,
                                                              const double* __restrict__ pool, int W, uint64_t shots, uint64_t seed,
                                                              NzMeas meas, char* slots, uint64_t* __restrict__ out, NzAccept a) {
-  constexpr bool MEAS = true, ACC = true, K2 = true;
+  constexpr bool MEAS = true, ACC = true, K2 = true, DYN = false;
   const uint64_t first = a.first_shot, fix_val = a.fix_val;
 #include "qsv_noise_hbm_shots.inc"
 }

@@ -10,6 +10,11 @@
 // which nz_apply ends, so everything the abandoned shot read of the state (and, at TPB > 64, of kraus_op's scratch) is read
 // before any thread writes the next |0..0>.  With one wave per workgroup that barrier is a wait for the wave's own LDS
 // accesses, which the LDS serves in order.
+// DYN (qsv_noise_dynamic.hip; the including kernel has it in scope too): an IF record (QSV_OP_IF, include/qsv.h) compares the
+// word as it stands and, on a miss, adds its span to the record index: the skipped records are not fetched, so they take no
+// draw and write no bit, and the ordinals of stream 3 are in the records, which a skip cannot shift.  Every thread holds the
+// word alike, so the branch is uniform, and it needs no barrier because nothing of the state is touched.  The abandonment
+// check sits behind an executed record, so a decisive record that was skipped abandons nothing.
   static_assert(MEAS || !ACC, "only a MEASURE record ends a shot early");
   extern __shared__ __attribute__((aligned(16))) char nz_lds[];
   cplx* st = reinterpret_cast<cplx*>(nz_lds);              // 2^W amplitudes, nothing else
@@ -24,7 +29,15 @@
     bool dead = false;
     for (int k = 0; k < n_ops; ++k) {
       const NzOp o = nz_fetch(ops, k);
-      nz_apply<TPB, 1, KRAUS, MEAS, K2>(st, N, o, pool, tid, seed, shot, draw, mword);
+      if constexpr (DYN) {
+        if (o.kind == NZ_IF) {                                       // span and mask are in the record's first 16 bytes
+          const uint64_t mask = (uint64_t)o.cval | ((uint64_t)o.off << 32);
+          const bool hit = ((mword & mask) == o.ql8) != (o.target != 0u);
+          k += (int)__builtin_amdgcn_readfirstlane(hit ? 0u : o.cmask);   // every thread holds mword alike: say so, k stays scalar
+          continue;
+        }
+      }
+      nz_apply<TPB, 1, KRAUS, MEAS, K2, DYN>(st, N, o, pool, tid, seed, shot, draw, mword);
       if constexpr (ACC) {
         if (o.kind == NZ_MEASURE && (o.cmask & NZ_DECISIVE) && (((mword ^ fix_val) >> (o.cmask & 63u)) & 1ull)) {
           dead = true;

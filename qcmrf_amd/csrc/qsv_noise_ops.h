@@ -184,7 +184,8 @@ __device__ __forceinline__ int measure_pick(double r00, double r11, double u, bo
 // thread adds them in wave order.  The caller's barrier after the op also fences that scratch.
 // MEAS: the record may also be a MEASURE record, which shares everything but the pick (measure_pick).  Returns the outcome of
 // a MEASURE record (0 for a KRAUS record), -1 for a state without mass.
-template <int TPB, int B, int R, bool MEAS = false>
+// DYN (with MEAS): a RESET record (QSV_OP_RESET, include/qsv.h) takes the pick of a MEASURE record too; its release flag is set.
+template <int TPB, int B, int R, bool MEAS = false, bool DYN = false>
 __device__ __forceinline__ int kraus_op(cplx* st, const NzOp& o, const double* __restrict__ pool, uint32_t half, uint32_t tid,
                                         double u) {
   const uint32_t tb = 1u << o.target, lo = tb - 1u;
@@ -242,7 +243,7 @@ __device__ __forceinline__ int kraus_op(cplx* st, const NzOp& o, const double* _
   }
   cplx m00, m01, m10, m11;
   int b = 0;
-  if (MEAS && o.kind == NZ_MEASURE) {
+  if (MEAS && (o.kind == NZ_MEASURE || (DYN && o.kind == NZ_RESET))) {
     b = measure_pick(r00, r11, u, (o.cmask >> 8) & 1u, m00, m01, m10, m11);
     if (b < 0) return -1;
   } else if (!kraus_pick(r00, r11, rre, rim, u, o, pool, m00, m01, m10, m11)) return -1;
@@ -448,12 +449,16 @@ __device__ __forceinline__ bool kraus2_op(cplx* st, const NzOp& o, const double*
 // it writes its bit, flipped by the readout draw nz_word would take for it, into `word`, which every thread holds alike.
 // K2: KRAUS2 records are known too (only with MEAS: the kernels that know the kind know every kind).  The record takes the next
 // draw of stream NZ_STREAM_PAULI, like a KRAUS record; at TPB 64 a lane holds 1 quad where it holds 1 pair, else 4 (kraus2_op).
-template <int TPB, int B, int KRAUS, bool MEAS = false, bool K2 = false>
+// DYN: RESET records are known too (only with K2: the kernels of qsv_noise_dynamic.hip know every kind).  A RESET record is a
+// MEASURE record with release set that draws as one -- stream NZ_STREAM_MEASURE, numbered by the record's ordinal among both
+// kinds -- and leaves `word` alone.  An IF record never comes here: the shot loops take it, it touches nothing of the state.
+template <int TPB, int B, int KRAUS, bool MEAS = false, bool K2 = false, bool DYN = false>
 __device__ __forceinline__ void nz_apply(cplx* st, uint32_t N, const NzOp& o, const double* __restrict__ pool, uint32_t tid,
                                          uint64_t seed, uint64_t shot, uint32_t& draw, uint64_t& word) {
   const uint32_t half = N >> 1;
   if constexpr (K2) {
     static_assert(MEAS, "a kernel that knows KRAUS2 records knows MEASURE and KRAUS records");
+    static_assert(K2 || !DYN, "a kernel that knows IF and RESET records knows every kind");
     if (o.kind == NZ_KRAUS2) {
       kraus2_op<TPB, B, KRAUS == 1 ? 1 : 4>(st, o, pool, N, tid, philox_u01(seed, shot, NZ_STREAM_PAULI, draw++));
       __syncthreads();
@@ -462,11 +467,13 @@ __device__ __forceinline__ void nz_apply(cplx* st, uint32_t N, const NzOp& o, co
   }
   if constexpr (MEAS) {
     static_assert(KRAUS > 0, "a kernel that knows MEASURE records knows KRAUS records");
-    if (o.kind == NZ_MEASURE || o.kind == NZ_KRAUS) {
+    const bool reset = DYN && o.kind == NZ_RESET;
+    if (o.kind == NZ_MEASURE || o.kind == NZ_KRAUS || reset) {
       const bool meas = o.kind == NZ_MEASURE;
-      const double u = philox_u01(seed, shot, meas ? NZ_STREAM_MEASURE : NZ_STREAM_PAULI, meas ? o.cval : draw);
-      if (!meas) ++draw;
-      const int k = kraus_op<TPB, B, KRAUS, true>(st, o, pool, half, tid, u);
+      const bool own = meas || reset;                              // a draw of its own stream, not the next of stream 0
+      const double u = philox_u01(seed, shot, own ? NZ_STREAM_MEASURE : NZ_STREAM_PAULI, own ? o.cval : draw);
+      if (!own) ++draw;
+      const int k = kraus_op<TPB, B, KRAUS, true, DYN>(st, o, pool, half, tid, u);
       if (meas) {
         const uint32_t c = o.cmask & 63u;
         uint32_t bit = k > 0 ? 1u : 0u;

@@ -11,7 +11,9 @@ Composite instructions (``cU_C<ii>``, ``cU_C<ii>_dg``, ``and``, ... -- QCMRF.py:
 are expanded through ``operation.definition``; an operation that is neither primitive nor has a
 definition raises ``ValueError`` naming it.  Measurements are deferred to the end of the circuit
 (exact here: QCMRF.py never conditions on a classical bit and never touches a measured qubit
-again, QCMRF.py:239); a circuit that does either is rejected.
+again, QCMRF.py:239); a circuit that does either is rejected, unless it is read with
+``ingest(dynamic=True)``, which keeps every measure where it occurs and turns ``reset`` and conditions into ops
+of their own (``_walk_dynamic``).
 """
 from __future__ import annotations
 
@@ -40,6 +42,10 @@ class Ingested:
         self.n_pauli = 0              # "pauli" ops the noise model added
         self.n_kraus = 0              # "kraus" ops the noise model added
         self.n_kraus2 = 0             # "kraus2" ops the noise model added
+        self.dynamic = False          # read with dynamic=True: "reset" and "if" ops may occur, measured qubits may be used again
+        self.n_if = 0                 # "if" ops (guards over the next ops; an if_else with an else body counts two)
+        self.n_reset = 0              # "reset" ops
+        self.n_reuse = 0              # gates, measures or conditions that touch a qubit measured earlier and not reset since
         self.ingest_path = "python"   # what read this process's clique blocks: "native" (all of them), "python" (all, or there were none), "mixed"
 
 
@@ -588,6 +594,142 @@ def _walk(circuit, qmap, cmap, out, depth):
                          "carries no definition" % (name, len(q)))
 
 
+def _condition_of(circuit, condition, name, ci_map, cmap, cache):
+    """(mask, value) over the classical word for the condition of instruction ``name``: (bit or register, integer).  A register
+    compares its integer value: the mask is the register's bits, bit j of the value stands at the position of its bit j"""
+    if not (isinstance(condition, tuple) and len(condition) == 2):
+        raise ValueError("the condition of %r is not a (classical bit or register, integer) pair: %r" % (name, condition))
+    what, val = condition
+    if isinstance(val, bool):
+        val = int(val)
+    if not isinstance(val, (int, np.integer)):
+        raise ValueError("the condition of %r compares with %r; only equality with an integer is supported" % (name, val))
+    val = int(val)
+    try:
+        bits = list(what)                                    # a register: its bits, least significant first
+    except TypeError:
+        bits = None
+    if bits is None:
+        try:
+            bits = [what]
+            pos = [cmap[_cbit(circuit, ci_map, what, cache)]]
+        except Exception:
+            raise ValueError("the condition of %r is on %r, which is neither a classical bit nor a register of the circuit" % (name, what))
+    else:
+        try:
+            pos = [cmap[_cbit(circuit, ci_map, b, cache)] for b in bits]
+        except Exception:
+            raise ValueError("the condition of %r is on a register with bits that are not the circuit's" % (name,))
+        if not pos:
+            raise ValueError("the condition of %r is on an empty register" % (name,))
+    if val < 0 or val >> len(pos):
+        raise ValueError("the condition of %r compares %d classical bit(s) with %d, which does not fit" % (name, len(pos), val))
+    if max(pos) >= 64:
+        raise ValueError("the condition of %r reads classical bit %d; a shot holds bits 0..63" % (name, max(pos)))
+    mask = value = 0
+    for j, c in enumerate(pos):
+        mask |= 1 << c
+        value |= ((val >> j) & 1) << c
+    return mask, value
+
+
+def _walk_dynamic(circuit, qmap, cmap, out, depth, guarded):
+    """``_walk`` for ingest(dynamic=True): "reset" becomes a "reset" op, a measured qubit may be used again, and a conditioned
+    instruction becomes an "if" op (target = span, mask, a = (value,), vals = (negate,)) in front of everything it lowers to --
+    the ops of a composite definition and the noise ops the model attaches included, so that the error of a conditioned gate
+    occurs only when the gate does.  ``guarded``: the name of the conditioned instruction the walk is inside of, or None."""
+    if depth > 32:
+        raise ValueError("instruction definitions nest deeper than 32 levels")
+    cache = {}
+    out.global_phase += float(getattr(circuit, "global_phase", 0.0) or 0.0)
+    qi, ci_map = _bit_maps(circuit)
+    for entry in circuit.data:
+        op, qargs, cargs = _unpack(entry)
+        try:
+            q = [qmap[qi[id(b)]] for b in qargs]
+        except (KeyError, TypeError):
+            q = [qmap[_index_of(circuit, b, cache)] for b in qargs]
+        name = op.name
+        condition = getattr(op, "condition", None)
+        if name in ("while_loop", "for_loop", "switch_case"):
+            raise ValueError("control-flow operation %r is not supported (if_else and c_if only)" % name)
+        if condition is not None or name == "if_else":
+            if guarded is not None:
+                raise ValueError("conditioned operation %r inside the conditioned operation %r: nested conditions are not supported"
+                                 % (name, guarded))
+            if condition is None:
+                raise ValueError("if_else operation without a condition")
+            mask, value = _condition_of(circuit, condition, name, ci_map, cmap, cache)
+            c = [cmap[_cbit(circuit, ci_map, b, cache)] for b in cargs]
+            bodies = list(getattr(op, "blocks", ()) or ()) if name == "if_else" else [None]
+            if name == "if_else" and not 1 <= len(bodies) <= 2:
+                raise ValueError("if_else operation with %d blocks" % len(bodies))
+            for negate, body in enumerate(bodies):
+                if name == "if_else" and body is None:
+                    continue
+                guard = ir.Op("if", target=0, mask=mask, a=(value,), vals=(negate,))
+                out.ops.append(guard)
+                n0 = len(out.ops)
+                if body is None:
+                    _emit_dynamic(circuit, op, name, q, c, out, depth, name)
+                else:
+                    _walk_dynamic(body, q, c, out, depth + 1, name)
+                guard.target = len(out.ops) - n0
+                if guard.target == 0:                        # nothing to guard (a conditioned barrier, an empty body)
+                    out.ops.pop()
+                else:
+                    out.n_if += 1
+            if name == "if_else":
+                out.n_source_ops += 1
+            continue
+        c = [cmap[_cbit(circuit, ci_map, b, cache)] for b in cargs]
+        _emit_dynamic(circuit, op, name, q, c, out, depth, guarded)
+
+
+def _emit_dynamic(circuit, op, name, q, c, out, depth, guarded):
+    """one instruction of ``_walk_dynamic``, its condition (if any) already turned into the guard in front of it"""
+    if name == "measure":
+        if q[0] in out._measured:
+            out.n_reuse += 1
+        out.measure[c[0]] = q[0]
+        out._measured.add(q[0])
+        out.n_source_ops += 1
+        flips = out.noise.readout_flips(q[0]) if out.noise is not None else None
+        if flips is not None:
+            out.readout[c[0]] = flips
+        else:
+            out.readout.pop(c[0], None)
+        out.ops.append(ir.Op("measure", target=q[0], mask=c[0]))
+        return
+    if name in ("barrier", "delay"):
+        return
+    if name == "reset":
+        out.ops.append(ir.Op("reset", target=q[0]))
+        out._measured.discard(q[0])
+        out.n_reset += 1
+        out.n_source_ops += 1
+        return
+    if out._measured and out._measured.intersection(q):
+        out.n_reuse += 1
+        out._measured.difference_update(q)
+    handler = _PRIMITIVES.get(name)
+    if handler is None and "_o" in name:
+        m = _OPEN_CTRL.match(name)
+        handler = _PRIMITIVES.get(m.group(1)) if m else None
+    if handler is not None:
+        handler(out.ops, op, q)
+        out.n_source_ops += 1
+        if out.noise is not None:
+            _noise_after(out, name, q)
+        return
+    definition = getattr(op, "definition", None)
+    if definition is not None:
+        _walk_dynamic(definition, q, c, out, depth + 1, guarded)
+        return
+    raise ValueError("unsupported operation %r on %d qubit(s): not a primitive of this engine and it "
+                     "carries no definition" % (name, len(q)))
+
+
 _FLAT_NAMES = frozenset(("rz", "sx", "x", "cx", "id", "measure", "barrier", "delay"))
 class _NotCompact(Exception):
     """the flat walk met something it has no compact record for: redo it with ir.Op objects"""
@@ -808,7 +950,7 @@ def _walk_flat(circuit, out, compact=False):
     return True
 
 
-def ingest(circuit, peephole=False, keep_measures=False, comm=None, compact=False, noise=None):
+def ingest(circuit, peephole=False, keep_measures=False, comm=None, compact=False, noise=None, dynamic=False):
     """peephole=True additionally folds X..X . MCX . X..X definitions (Qiskit's AND with negative
     flags) into one MCX with negated controls while walking -- exact, and 5x fewer ops to fuse.
     comm (a process group of world > 1, every rank calling with the same circuit): the composite top-level blocks are
@@ -817,9 +959,15 @@ def ingest(circuit, peephole=False, keep_measures=False, comm=None, compact=Fals
     ``passes.optimise(..., flat=)`` at level 3 understands them.
     noise (a ``qcmrf_amd.noise.NoiseModel``): the gate-by-gate walk with every composite unrolled to primitives (peephole,
     compact and comm are ignored); behind each primitive the model names for its qubits come the "pauli" and "kraus" ops of its error, and the readout
-    errors of the measured qubits land in ``readout`` (per classical bit)."""
-    if noise is not None:
+    errors of the measured qubits land in ``readout`` (per classical bit).
+    dynamic: the gate-by-gate walk of the Python reader with every measure kept where it occurs (peephole, compact and comm are
+    ignored, keep_measures is implied); ``reset`` becomes a "reset" op, a measured qubit may be used again, a conditioned
+    instruction (``c_if``) or an ``if_else`` becomes an "if" op over everything it lowers to (``_walk_dynamic``).  Without it
+    every such circuit is refused, as ever."""
+    if noise is not None or dynamic:
         peephole, compact, comm = False, False, None
+    if dynamic:
+        keep_measures = True
     nq = int(circuit.num_qubits)
     nc = int(getattr(circuit, "num_clbits", 0))
     out = Ingested(nq, nc)
@@ -840,7 +988,10 @@ def ingest(circuit, peephole=False, keep_measures=False, comm=None, compact=Fals
             flat = _walk_flat(circuit, out, compact=False)
         except KeyError:                     # bits that are equal to, but not, the circuit's own objects: take the general walk
             out.ops, out.measure, out._measured, out.global_phase, out.n_source_ops, out.flat = [], {}, set(), 0.0, 0, None
-    if not flat:
+    if dynamic:
+        out.dynamic = True
+        _walk_dynamic(circuit, list(range(nq)), list(range(nc)), out, 0, None)
+    elif not flat:
         try:
             _walk(circuit, list(range(nq)), list(range(nc)), out, 0)
         except Exception:

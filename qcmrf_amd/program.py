@@ -9,12 +9,14 @@ from . import _lib
 _X = np.array([[0, 1], [1, 0]], dtype=np.complex128)
 
 
-def encode(ops):
-    """list of ir.Op (physical qubits) -> (records: ndarray[OP_DTYPE], data: float64 pool)"""
+def encode(ops, n_meas=None):
+    """list of ir.Op (physical qubits) -> (records: ndarray[OP_DTYPE], data: float64 pool).  n_meas: the classical bits of the
+    call the records go to (needed by "if" ops, which read them: QSV_OP_IF, include/qsv.h)"""
     rec = np.zeros(len(ops), dtype=_lib.OP_DTYPE)
     pool = []
     top = 0
     kraus_seen = {}
+    span_end, span_of = 0, -1                  # ops below span_end lie in the span of the 'if' op span_of
 
     def put(arr):
         nonlocal top
@@ -41,7 +43,7 @@ def encode(ops):
         if vals is not None:
             r["vals"][:n] = vals
 
-    for r, op in zip(rec, ops):
+    for i, (r, op) in enumerate(zip(rec, ops)):
         k = op.kind
         if op.new_pass:
             r["flags"] = _lib.OPF_NEW_PASS
@@ -111,8 +113,36 @@ def encode(ops):
             fill(r, [op.target], [c])
             r["vals"][1] = release
             r["data_off"] = put_real(measure_flips(op.table))
+        elif k == "reset":
+            r["kind"] = _lib.OP_RESET
+            fill(r, [op.target])
+        elif k == "if":
+            span, mask, negate = int(op.target), int(op.mask), int(op.vals[0]) if len(op.vals) else 0
+            value = int(op.a[0]) if len(op.a) else 0
+            if i < span_end:
+                raise ValueError("op %d: an 'if' op inside the span of the 'if' op %d (guards do not nest)" % (i, span_of))
+            if span < 1 or i + span > len(ops) - 1:
+                raise ValueError("op %d: an 'if' op guards %d ops, %d follow it" % (i, span, len(ops) - 1 - i))
+            if n_meas is None:
+                raise ValueError("op %d: an 'if' op reads classical bits and needs the measurement map of the call (n_meas)" % i)
+            if mask == 0:
+                raise ValueError("op %d: an 'if' op compares no classical bit (mask 0)" % i)
+            if mask < 0 or mask >> min(64, int(n_meas)):
+                raise ValueError("op %d: an 'if' op reads classical bits %#x, outside the %d bits of the call" % (i, mask, min(64, int(n_meas))))
+            if value & ~mask or value < 0:
+                raise ValueError("op %d: the value %#x of an 'if' op has bits outside its mask %#x" % (i, value, mask))
+            if negate not in (0, 1):
+                raise ValueError("op %d: the negate flag of an 'if' op is 0 or 1, not %r" % (i, negate))
+            span_end, span_of = i + 1 + span, i
+            r["kind"] = _lib.OP_IF
+            r["n"] = span
+            r["target"] = negate
+            r["mask"] = mask
+            r["vals"][:2] = np.array([value & 0xFFFFFFFF, value >> 32], dtype=np.uint32).view(np.int32)
         else:
             raise ValueError("cannot encode op kind %r" % k)
+        if k == "init" and i < span_end:
+            raise ValueError("op %d: an 'init' op inside the span of the 'if' op %d" % (i, span_of))
     data = np.concatenate(pool) if pool else np.zeros(0, dtype=np.float64)
     return rec, data
 

@@ -98,6 +98,84 @@ def plan_slots(ops):
     return staged, width, final_measures
 
 
+def plan_slots_dynamic(ops):
+    """The slot plan of a gate list read with ``ingest(dynamic=True)``: "measure", "reset" and "if" ops among the gates, qubits
+    used again after a measure.  ``plan_slots`` stays what it is for every list without those.
+
+    Every logical qubit gets a slot at its first use and the lowest freed slot is handed out again first.  A measure releases
+    its slot iff it is the last thing that happens to its qubit AND it stands outside every span: inside one it may not run,
+    and then the qubit is not back in |0>.  A measure followed by further use of the qubit keeps the slot (release 0).  A reset
+    that is the last thing on its qubit, outside every span, frees its slot, and is dropped unless the slot is handed out
+    again (its next owner has to find |0> there); nothing inside a span is dropped, so the span of an "if" op counts the same
+    ops before and after.  Returns (items, width, final_measures): ``items`` is the flat
+    stream in order -- ir.Op remapped to slots ("if" ops copied, their span in ``target``), ("measure", slot, clbit, release,
+    logical qubit) and ("reset", slot) --, the trailing measures outside every span are taken out of it and listed as
+    ``final_measures`` [(slot, clbit)], to be sampled jointly from the final state; ``width`` is the number of slots in use
+    at once."""
+    last = {}
+    for k, op in enumerate(ops):
+        for q in ((op.target,) if op.kind in ("measure", "reset") else () if op.kind == "if" else op.support()):
+            last[q] = k
+    slot_of, free, next_slot, width = {}, [], 0, 0
+
+    droppable = {}                             # slot -> index in items of the trailing reset that freed it, while nobody took it
+
+    def slot(q):
+        nonlocal next_slot, width
+        if q not in slot_of:
+            if free:
+                slot_of[q] = free.pop(0)
+                droppable.pop(slot_of[q], None)    # handed out again: that reset has to run
+            else:
+                slot_of[q] = next_slot
+                next_slot += 1
+            width = max(width, next_slot)
+        return slot_of[q]
+
+    def give_back(q):
+        free.append(slot_of.pop(q))
+        free.sort()
+
+    items, guarded = [], []                    # guarded[i]: items[i] lies in the span of an "if" op
+    span_end = 0
+    for k, op in enumerate(ops):
+        inside = k < span_end
+        if op.kind == "if":
+            if inside:
+                raise ValueError("an 'if' op inside the span of another: nested conditions are not supported")
+            if op.target < 1 or k + op.target > len(ops) - 1:
+                raise ValueError("an 'if' op guards %d ops, %d follow it" % (op.target, len(ops) - 1 - k))
+            span_end = k + 1 + op.target
+            items.append(ir.Op("if", target=op.target, mask=op.mask, a=op.a, vals=op.vals))
+        elif op.kind == "measure":
+            release = last[op.target] == k and not inside
+            items.append(("measure", slot(op.target), op.mask, release, op.target))
+            if release:
+                give_back(op.target)
+        elif op.kind == "reset":
+            if last[op.target] == k and not inside:
+                if op.target not in slot_of:
+                    continue                       # the qubit was never touched: nothing to reset, no slot to free
+                droppable[slot_of[op.target]] = len(items)
+                items.append(("reset", slot_of[op.target]))
+                give_back(op.target)
+            else:
+                items.append(("reset", slot(op.target)))
+        else:
+            lay = {q: slot(q) for q in op.support()}
+            items.append(ir.Op(op.kind, target=lay.get(op.target), ctrls=tuple(lay[c] for c in op.ctrls), vals=op.vals,
+                               qubits=tuple(lay[q] for q in op.qubits), mat=op.mat, table=op.table, mats=op.mats,
+                               angle=op.angle, label=op.label))
+        guarded.append(inside)
+    drop = set(droppable.values())                 # outside every span, so no span changes
+    items, guarded = [x for i, x in enumerate(items) if i not in drop], [g for i, g in enumerate(guarded) if i not in drop]
+    final_measures = []
+    while items and isinstance(items[-1], tuple) and items[-1][0] == "measure" and not guarded[len(items) - 1]:
+        _, s, c, _, _ = items.pop()
+        final_measures.insert(0, (s, c))
+    return items, width, final_measures
+
+
 def compile_trajectory(circuit, fusion=3):
     """-> (segments, width, final_measures [(slot, clbit)], num_clbits, creg_sizes, n_source_ops)"""
     ing = _ingest.ingest(circuit, peephole=fusion >= 1, keep_measures=True)
