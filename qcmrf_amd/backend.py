@@ -19,7 +19,7 @@ import time
 
 import numpy as np
 
-from . import _lib, ingest as _ingest, noise as _noise, passes, planner, program
+from . import _lib, frontend, ingest as _ingest, noise as _noise, passes, planner, program
 from .comm import SingleProcess
 
 _METHODS = ("statevector", "trajectory", "density_matrix")
@@ -1014,12 +1014,25 @@ class QsvBackend:
             applied[k] = v
 
     def _prepare(self, circuit, opts):
-        """host half of a run: ingest + passes + plan + encode (no device work)"""
+        """host half of a run: ingest + passes + plan + encode (no device work).  A circuit of the reference's construction is
+        compiled by the native front end instead of ingest + passes where that applies (``frontend.compile_blocks``; the
+        same program): ``compile_path`` "blocks", else "passes"."""
         t0 = time.perf_counter()
         comm = opts["comm"] or SingleProcess()
         n_shards = comm.world if comm.world > 1 else len(opts["devices"])
-        ing, pl = self.compile(circuit, n_shards, ingest_comm=comm if (comm.world > 1 and opts.get("spmd_ingest", False) and not opts.get("_batch")) else None,
-                               **{k: opts[k] for k in ("fusion", "layout", "engine_options", "fold_fresh")})
+        spmd = comm.world > 1 and opts.get("spmd_ingest", False) and not opts.get("_batch")
+        copts = {k: opts[k] for k in ("fusion", "layout", "engine_options", "fold_fresh")}
+        fast = None
+        if (copts["fusion"] == 3 and copts["fold_fresh"] and not spmd and not opts.get("dynamic")
+                and opts.get("method", "statevector") == "statevector"):
+            g = max(1, int(n_shards)).bit_length() - 1
+            fast = frontend.compile_blocks(circuit, dense_kmax=max(1, min(5, int(circuit.num_qubits) - g)))
+        if fast is not None:
+            ing = fast[0]
+            pl = self._plan(ing, fast[1], n_shards, dict(self.options, **copts))
+            ing.compile_path = "blocks"
+        else:
+            ing, pl = self.compile(circuit, n_shards, ingest_comm=comm if spmd else None, **copts)
         rec, data = program.encode(pl.ops)
         return ing, pl, rec, data, n_shards, time.perf_counter() - t0
 
@@ -1032,6 +1045,11 @@ class QsvBackend:
         g = max(1, int(n_shards)).bit_length() - 1
         ops = passes.optimise(ing.ops, level=opts["fusion"], fresh=bool(opts.get("fold_fresh", True)),
                               dense_kmax=max(1, min(5, ing.num_qubits - g)), flat=ing.flat)
+        return ing, self._plan(ing, ops, n_shards, opts)
+
+    @staticmethod
+    def _plan(ing, ops, n_shards, opts):
+        """the fused ops with the circuit's global phase put in, planned onto the shards"""
         if ing.global_phase and opts.get("apply_global_phase", True):
             from . import ir
             ph = np.exp(1j * ing.global_phase)
@@ -1042,9 +1060,8 @@ class QsvBackend:
                 ops.append(ir.op_diag([0], [ph, ph]))
         eo = opts.get("engine_options") or {}
         lane = bool(eo.get("lane_targets", 1)) and not eo.get("zero_tracking", 0)   # lane targets need a fully populated vector
-        pl = planner.plan(ops, ing.num_qubits, n_shards, opts["layout"], lane_targets=lane,
-                          dyn_lanes=int(eo.get("dyn_lanes", planner.DYN_LANES)))
-        return ing, pl
+        return planner.plan(ops, ing.num_qubits, n_shards, opts["layout"], lane_targets=lane,
+                            dyn_lanes=int(eo.get("dyn_lanes", planner.DYN_LANES)))
 
     def _run_trajectory(self, circuit, shots, seed, opts):
         from . import trajectory
@@ -1173,7 +1190,7 @@ class QsvBackend:
                 "n_exchanges": pl.n_exchanges, "n_shards": n_shards, "layout": list(pl.layout),
                 "fusion": opts["fusion"], "time_compile": t1 - t0, "time_evolve": t2 - t1,
                 "time_sample": t3 - t2, "time_taken": t3 - t0, "seed_simulator": seed, "ingest_path": ing.ingest_path,
-                "counts_path": counts_path}
+                "compile_path": ing.compile_path, "counts_path": counts_path}
         meta.update(post_meta)
         if comm.world > 1 and opts.get("gather_counts", "root") != "all":
             meta["counts_on_rank"] = 0

@@ -18,7 +18,7 @@ CFLAGS = ["-O3", "--offload-arch=gfx950", "-std=c++17", "-fPIC", "-munsafe-fp-at
 OBJDIR = os.path.join(CSRC, "_obj")
 # host-only CPython modules next to libqsv.so (host C++ against Python's own headers, no HIP in them):
 # (module, sources, what Python does in its place where the module cannot be built)
-EXT_MODULES = [("_ingest_native", ["ingest_native.cpp"], "ingest reads blocks in Python"),         # reader of clique-block signatures (qcmrf_amd.ingest)
+EXT_MODULES = [("_ingest_native", ["ingest_native.cpp"], "ingest reads blocks in Python"),         # reader of clique-block signatures (qcmrf_amd.ingest) and the front end's walk (qcmrf_amd.frontend)
                ("_counts_native", ["counts_native.cpp"], "counts are sorted and formatted in Python")]   # sampled words -> count dict (qcmrf_amd.backend)
 EXT_CFLAGS = ["-O2", "-std=c++17", "-fPIC", "-fvisibility=hidden", "-fno-exceptions", "-fno-rtti", "-Wall"]
 

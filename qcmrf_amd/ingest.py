@@ -46,6 +46,7 @@ class Ingested:
         self.n_if = 0                 # "if" ops (guards over the next ops; an if_else with an else body counts two)
         self.n_reset = 0              # "reset" ops
         self.n_reuse = 0              # gates, measures or conditions that touch a qubit measured earlier and not reset since
+        self.compile_path = "passes"  # what made the fused ops of a run: "passes" (ingest + passes.optimise), "blocks" (qcmrf_amd.frontend)
         self.ingest_path = "python"   # what read this process's clique blocks: "native" (all of them), "python" (all, or there were none), "mixed"
 
 
@@ -353,9 +354,11 @@ def _block_of_key(key):
 try:
     from . import _ingest_native          # built by qcmrf_amd.build next to libqsv.so; absent where Python's headers are missing
     _ingest_native.set_primitives(_PRIMITIVES)
+    _ingest_native.set_block_of_key(_block_of_key)
 except Exception:                         # not built, or does not load here: the blocks are read in Python (same result)
     _ingest_native = None
 _native_read = _ingest_native.read_block if _ingest_native is not None else None
+_native_frontend = _ingest_native is not None      # the front end (qcmrf_amd.frontend) is tried; it needs the reader on as well
 
 
 def native_available():
@@ -365,13 +368,31 @@ def native_available():
 
 def use_native(on=True):
     """force the switch: blocks are read by the native reader (``on``; RuntimeError where it is not available) or by
-    the Python code.  Returns the previous setting.  The default is on wherever the module imports."""
+    the Python code.  Returns the previous setting.  The default is on wherever the module imports.  Off also keeps
+    the native front end (``use_native_frontend``) from being tried: it is built on the reader."""
     global _native_read
     was = _native_read is not None
     if on and _ingest_native is None:
         raise RuntimeError("qcmrf_amd._ingest_native is not built or does not import (python -m qcmrf_amd.build)")
     _native_read = _ingest_native.read_block if on else None
     return was
+
+
+def use_native_frontend(on=True):
+    """force the switch: the run path tries the native front end (``qcmrf_amd.frontend.compile_blocks``) before ingest +
+    passes (``on``; RuntimeError where the module is not available), or never does.  Returns the previous setting.  The
+    default is on wherever the module imports; the front end is tried only while ``use_native`` is on too."""
+    global _native_frontend
+    was = _native_frontend
+    if on and _ingest_native is None:
+        raise RuntimeError("qcmrf_amd._ingest_native is not built or does not import (python -m qcmrf_amd.build)")
+    _native_frontend = bool(on)
+    return was
+
+
+def native_frontend_on():
+    """the native front end is tried by the run path: its own switch and the reader's are both on"""
+    return _native_frontend and _native_read is not None
 
 
 def _read_block(definition):

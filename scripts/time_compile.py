@@ -1,5 +1,6 @@
 """host compile time of the 34-qubit circuit by stage (ingest, passes, plan, encode), no GPU needed, for both settings
-of the ingest switch (native block reader on / off; a tree without the reader reports the Python path alone):
+of the ingest switch (native block reader on / off; a tree without the reader reports the Python path alone), and the
+native front end that stands in for ingest + passes on the run path (qcmrf_amd/frontend.py) as a stage of its own:
     python scripts/time_compile.py            in-tree circuit container
     python scripts/time_compile.py --strict   the strict Qiskit double of tests/strict_qiskit (HAVE_QISKIT branch)
     python scripts/time_compile.py --walk     also: what the top-level loop of the walk costs next to the block reads
@@ -71,6 +72,39 @@ for on in settings:
     print("ingest_path=%s  device ops: %s ... total %d  source gates %d" % (getattr(ing, "ingest_path", "python (no switch in this tree)"),
           [o.kind for o in pl.ops][:6], len(pl.ops), ing.n_source_ops))
     print("  best of %d [ms]:" % REPS, {k: round(v * 1e3, 3) for k, v in best.items()})
+
+
+def front_end(reps):
+    """the fast path of QsvBackend._prepare by stage: the native walk alone, walk + numpy half (= ingest + passes of the other
+    path), and _prepare as a whole (front end + plan + encode) with the front end on and off"""
+    from qcmrf_amd import frontend
+    best = {}
+    opts = dict(be.options)
+    for rep in range(reps):
+        t0 = time.perf_counter()
+        got = frontend._describe(qc)
+        t1 = time.perf_counter()
+        fast = frontend.compile_blocks(qc)
+        t2 = time.perf_counter()
+        prepared = be._prepare(qc, opts)
+        t3 = time.perf_counter()
+        was = ing_mod.use_native_frontend(False)
+        t4 = time.perf_counter()
+        be._prepare(qc, opts)
+        t5 = time.perf_counter()
+        ing_mod.use_native_frontend(was)
+        for k, v in (("read_circuit (native walk)", t1 - t0), ("compile_blocks (walk + numpy half)", t2 - t1),
+                     ("_prepare, front end on", t3 - t2), ("_prepare, front end off", t5 - t4)):
+            best[k] = min(best.get(k, 1e9), v)
+    assert got is not None and fast is not None and prepared[0].compile_path == "blocks"
+    print("front end: compile_path=%s, %d groups, %d fused ops" % (prepared[0].compile_path, len(got[3]), len(fast[1])))
+    print("  best of %d [ms]:" % reps, {k: round(v * 1e3, 3) for k, v in best.items()})
+
+
+if hasattr(ing_mod, "use_native_frontend") and ing_mod.native_available():
+    ing_mod.use_native(True)
+    front_end(REPS)
+
 
 def per_instruction_part():
     """the part of the top-level loop of ingest._walk that native code could take over: the tuple reads, the qi[id(b)]
