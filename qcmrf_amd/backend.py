@@ -1016,21 +1016,26 @@ class QsvBackend:
     def _prepare(self, circuit, opts):
         """host half of a run: ingest + passes + plan + encode (no device work).  A circuit of the reference's construction is
         compiled by the native front end instead of ingest + passes where that applies (``frontend.compile_blocks``; the
-        same program): ``compile_path`` "blocks", else "passes"."""
+        same program): ``compile_path`` "blocks", else "passes".  Such a circuit is also planned and encoded in native code
+        where that applies (``frontend.build_program``; the same records): ``plan_path`` "native", else "python"."""
         t0 = time.perf_counter()
         comm = opts["comm"] or SingleProcess()
         n_shards = comm.world if comm.world > 1 else len(opts["devices"])
         spmd = comm.world > 1 and opts.get("spmd_ingest", False) and not opts.get("_batch")
         copts = {k: opts[k] for k in ("fusion", "layout", "engine_options", "fold_fresh")}
-        fast = None
+        front = None
         if (copts["fusion"] == 3 and copts["fold_fresh"] and not spmd and not opts.get("dynamic")
                 and opts.get("method", "statevector") == "statevector"):
             g = max(1, int(n_shards)).bit_length() - 1
-            fast = frontend.compile_blocks(circuit, dense_kmax=max(1, min(5, int(circuit.num_qubits) - g)))
-        if fast is not None:
-            ing = fast[0]
-            pl = self._plan(ing, fast[1], n_shards, dict(self.options, **copts))
+            front = frontend.front_half(circuit, max(1, min(5, int(circuit.num_qubits) - g)))
+        if front is not None:
+            ing = front[0]
             ing.compile_path = "blocks"
+            done = frontend.build_program(front, n_shards, copts["layout"])
+            if done is not None:
+                ing.plan_path = "native"
+                return (ing,) + done + (n_shards, time.perf_counter() - t0)
+            pl = self._plan(ing, frontend.fold_ops(*front[1:]), n_shards, dict(self.options, **copts))
         else:
             ing, pl = self.compile(circuit, n_shards, ingest_comm=comm if spmd else None, **copts)
         rec, data = program.encode(pl.ops)
@@ -1190,7 +1195,7 @@ class QsvBackend:
                 "n_exchanges": pl.n_exchanges, "n_shards": n_shards, "layout": list(pl.layout),
                 "fusion": opts["fusion"], "time_compile": t1 - t0, "time_evolve": t2 - t1,
                 "time_sample": t3 - t2, "time_taken": t3 - t0, "seed_simulator": seed, "ingest_path": ing.ingest_path,
-                "compile_path": ing.compile_path, "counts_path": counts_path}
+                "compile_path": ing.compile_path, "plan_path": ing.plan_path, "counts_path": counts_path}
         meta.update(post_meta)
         if comm.world > 1 and opts.get("gather_counts", "root") != "all":
             meta["counts_on_rank"] = 0

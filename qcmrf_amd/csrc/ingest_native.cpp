@@ -17,9 +17,11 @@
 //
 // read_circuit(circuit), further down, is the front end's walk over a whole circuit of the reference's construction
 // (qcmrf_amd/frontend.py): it calls the reader's code directly for every composite and follows the same contract.
+// build_program(...), below it, is the back half of that front end: the fold's indexing, the layout and the encoded records.
 #define PY_SSIZE_T_CLEAN
 #include <Python.h>
 
+#include <algorithm>
 #include <cstdint>
 #include <cstring>
 #include <vector>
@@ -643,6 +645,328 @@ PyObject *read_circuit(PyObject *, PyObject *circuit)
     Py_RETURN_NONE;
 }
 
+// ---- the back half: fold + plan + encode of a front-end circuit (qcmrf_amd/frontend.py, planner.py, program.py) -------------
+//
+//     build_program(num_qubits, opened, groups, shapes, n_shards, layout, global_phase)
+//         -> (layout, records: bytearray of qsv_op, pool: bytearray of doubles, populated, n_ops)   or   None
+//
+// ``opened`` and ``groups`` are read_circuit's; ``shapes`` is a sequence of (k, m, c0), one entry per table shape: m the
+// sandwiched 2x2 stack of the groups on k qubits in program order, complex128 (groups, 2^(k-1), 2, 2), and c0 its column 0
+// times sqrt 2, complex128 (groups, 2^(k-1), 2).  No floating-point arithmetic happens here: entries are compared with 0 and
+// 1 and copied.  What is done is the indexing of frontend.compile_blocks' fold, planner.plan for an op list of one init and
+// diagonal factors (no dense target: no swap, no pass head, one layout) and program.encode for those ops.  The same
+// contract as the walk: None means "not mine", and no exception leaves.
+
+const int REC_MAX_CTRL = 16;                  // QSV_MAX_CTRL (include/qsv.h), _lib.MAX_CTRL
+const int REC_OP_INIT_ZERO = 0, REC_OP_INIT_UNIFORM = 1, REC_OP_DIAG = 4;
+const int PLAN_MULTI_R = 5, PLAN_LANE_BITS = 6, PLAN_GEN_TOP_MIN_L = 33, PLAN_REG_MIN_L = 14;   // planner.py
+
+struct Record {                               // qsv_op (include/qsv.h), _lib.OP_DTYPE
+    int32_t kind, target, n, flags;
+    int32_t qubits[REC_MAX_CTRL], vals[REC_MAX_CTRL];
+    uint64_t data_off, mask;
+    double angle;
+};
+static_assert(sizeof(Record) == 168, "qsv_op is 168 bytes");
+static_assert(MAX_GROUP_BITS <= REC_MAX_CTRL, "a factor of more qubits than a record holds is declined with its table shape");
+
+struct Buf {                                  // a C-contiguous complex128 buffer of a given shape
+    Py_buffer v;
+    bool held = false;
+    ~Buf()
+    {
+        if (held)
+            PyBuffer_Release(&v);
+    }
+    Buf() {}
+    Buf(const Buf &) = delete;
+    Buf &operator=(const Buf &) = delete;
+    bool get(PyObject *o, int ndim, const Py_ssize_t *shape)
+    {
+        if (!PyObject_CheckBuffer(o) || PyObject_GetBuffer(o, &v, PyBUF_C_CONTIGUOUS | PyBUF_FORMAT) < 0)
+            return false;
+        held = true;
+        if (!v.format || strcmp(v.format, "Zd") || v.itemsize != 16 || v.ndim != ndim || !v.shape || !v.buf)
+            return false;
+        for (int i = 0; i < ndim; i++)
+            if (v.shape[i] != shape[i])
+                return false;
+        return true;
+    }
+    const double *at(Py_ssize_t element) const { return (const double *)v.buf + 2 * element; }
+};
+
+struct Factor {
+    int n;                                    // qubits: the surviving selects, then the target
+    int q[MAX_GROUP_BITS];
+    int shape, row;                           // where its table is read: entry ``shape`` of shapes, group ``row`` of it
+    int kept[MAX_GROUP_BITS];                 // the select index bits that survive
+};
+
+bool exact_index(PyObject *x, long limit, int &out)
+{
+    if (!PyLong_CheckExact(x))
+        return false;
+    long v = PyLong_AsLong(x);
+    if (v < 0 || v >= limit)
+        return false;                         // (-1 with an error set included: the caller clears it)
+    out = (int)v;
+    return true;
+}
+
+bool build_program_impl(PyObject *args, Ref &result)
+{
+    if (!PyTuple_CheckExact(args) || PyTuple_GET_SIZE(args) != 7)
+        return false;
+    PyObject *a_nq = PyTuple_GET_ITEM(args, 0), *a_opened = PyTuple_GET_ITEM(args, 1), *a_groups = PyTuple_GET_ITEM(args, 2);
+    PyObject *a_shapes = PyTuple_GET_ITEM(args, 3), *a_shards = PyTuple_GET_ITEM(args, 4), *a_layout = PyTuple_GET_ITEM(args, 5);
+    PyObject *a_phase = PyTuple_GET_ITEM(args, 6);
+
+    if (!PyFloat_CheckExact(a_phase) || PyFloat_AS_DOUBLE(a_phase) != 0.0)
+        return false;                         // a global phase rides in the first diagonal: backend._plan multiplies it in
+    if (!PyUnicode_CheckExact(a_layout))
+        return false;
+    bool reference = is_name(a_layout, "reference");
+    if (!reference && !is_name(a_layout, "auto"))
+        return false;
+    int nq = 0;
+    if (!exact_index(a_nq, 65, nq) || nq < 1)
+        return false;                         // the init mask is one 64-bit word
+    if (!PyLong_CheckExact(a_shards))
+        return false;
+    long n_shards = PyLong_AsLong(a_shards);
+    if (n_shards < 1 || (n_shards & (n_shards - 1)))
+        return false;
+    int g = 0;
+    while ((1L << g) < n_shards)
+        g++;
+    int L = nq - g;
+    if (L < 1)
+        return false;
+
+    // ---- the fold: which selects survive, which factors are the identity, what is populated afterwards ------------------
+    if (!PyTuple_CheckExact(a_opened) || !PyList_CheckExact(a_groups))
+        return false;
+    uint64_t populated = 0;
+    for (Py_ssize_t i = 0; i < PyTuple_GET_SIZE(a_opened); i++) {
+        int q;
+        if (!exact_index(PyTuple_GET_ITEM(a_opened, i), nq, q))
+            return false;
+        populated |= (uint64_t)1 << q;
+    }
+    Ref shapes(PySequence_Fast(a_shapes, "shapes"));
+    if (!shapes.p)
+        return false;
+    Py_ssize_t n_shapes = PySequence_Fast_GET_SIZE(shapes.p), n_groups = PyList_GET_SIZE(a_groups);
+    if (n_shapes > MAX_GROUP_BITS || n_groups < 1)
+        return false;
+    for (Py_ssize_t i = 0; i < n_groups; i++) {
+        PyObject *grp = PyList_GET_ITEM(a_groups, i);
+        if (!PyTuple_CheckExact(grp) || PyTuple_GET_SIZE(grp) != 6 || !PyTuple_CheckExact(PyTuple_GET_ITEM(grp, 1)))
+            return false;
+    }
+    int shape_k[MAX_GROUP_BITS], shape_rows[MAX_GROUP_BITS], shape_seen[MAX_GROUP_BITS];
+    Buf mats[MAX_GROUP_BITS], col0[MAX_GROUP_BITS];
+    for (Py_ssize_t s = 0; s < n_shapes; s++) {
+        PyObject *e = PySequence_Fast_GET_ITEM(shapes.p, s);
+        if (!PyTuple_CheckExact(e) || PyTuple_GET_SIZE(e) != 3 || !exact_index(PyTuple_GET_ITEM(e, 0), MAX_GROUP_BITS + 1, shape_k[s]) ||
+            shape_k[s] < 2)
+            return false;
+        for (Py_ssize_t t = 0; t < s; t++)
+            if (shape_k[t] == shape_k[s])
+                return false;
+        Py_ssize_t rows = 0;
+        for (Py_ssize_t i = 0; i < n_groups; i++)
+            rows += PyTuple_GET_SIZE(PyTuple_GET_ITEM(PyList_GET_ITEM(a_groups, i), 1)) == shape_k[s];
+        Py_ssize_t sm[4] = {rows, (Py_ssize_t)1 << (shape_k[s] - 1), 2, 2};
+        if (rows < 1 || !mats[s].get(PyTuple_GET_ITEM(e, 1), 4, sm) || !col0[s].get(PyTuple_GET_ITEM(e, 2), 3, sm))
+            return false;
+        shape_rows[s] = (int)rows;
+        shape_seen[s] = 0;
+    }
+
+    std::vector<Factor> factors;
+    factors.reserve((size_t)n_groups);
+    size_t pool_doubles = 0;
+    for (Py_ssize_t i = 0; i < n_groups; i++) {
+        PyObject *grp = PyList_GET_ITEM(a_groups, i), *glob = PyTuple_GET_ITEM(grp, 1);
+        int k = (int)PyTuple_GET_SIZE(glob), s = 0, anc, sel[MAX_GROUP_BITS];
+        while (s < n_shapes && shape_k[s] != k)
+            s++;
+        if (s == n_shapes || shape_seen[s] >= shape_rows[s] || !exact_index(PyTuple_GET_ITEM(grp, 0), nq, anc))
+            return false;
+        for (int j = 0; j < k; j++) {
+            if (!exact_index(PyTuple_GET_ITEM(glob, j), nq, sel[j]))
+                return false;
+            for (int t = 0; t < j; t++)
+                if (sel[t] == sel[j])
+                    return false;
+        }
+        if (sel[k - 1] != anc)
+            return false;                     // the target is the last qubit of its blocks
+        Factor f;
+        f.n = 0;
+        f.shape = s;
+        f.row = shape_seen[s]++;
+        for (int e = 0; e + 1 < k; e++)
+            if ((populated >> sel[e]) & 1) {  // a select on a qubit still |0> reads 0: its index bit is sliced away
+                f.kept[f.n] = e;
+                f.q[f.n++] = sel[e];
+            }
+        int ns = f.n;
+        f.q[f.n++] = anc;
+        // the identity writes nothing: an exact comparison of every surviving 2x2 with [[1, 0], [0, 1]]
+        const double *m = mats[s].at((Py_ssize_t)f.row << (k + 1));
+        bool identity = true;
+        for (int j = 0; j < (1 << ns) && identity; j++) {
+            int at = 0;
+            for (int b = 0; b < ns; b++)
+                at |= ((j >> b) & 1) << f.kept[b];
+            const double *x = m + 8 * at;
+            identity = x[0] == 1.0 && x[1] == 0.0 && x[2] == 0.0 && x[3] == 0.0 && x[4] == 0.0 && x[5] == 0.0 && x[6] == 1.0 && x[7] == 0.0;
+        }
+        if (identity)
+            continue;
+        pool_doubles += (size_t)4 << ns;
+        factors.push_back(f);
+        populated |= (uint64_t)1 << anc;
+    }
+
+    // ---- planner.choose_layout: no op has a dense target, so no qubit is ever exchanged and one layout holds throughout -----
+    int lay[64];
+    if (reference) {
+        for (int q = 0; q < nq; q++)
+            lay[q] = q;
+    } else {
+        auto uniform = [&](int q) { return (int)((populated >> q) & 1); };
+        // shard bits: never-dense qubits in uniform superposition first, the highest index first among equals
+        bool shard[64] = {false};
+        int rank[64];
+        for (int q = 0; q < nq; q++)
+            rank[q] = q;
+        std::stable_sort(rank, rank + nq, [&](int a, int b) {
+            if (uniform(a) != uniform(b))
+                return uniform(a) > uniform(b);
+            return a > b;
+        });
+        for (int i = 0; i < g; i++)
+            shard[rank[i]] = true;
+        std::vector<int> quiet_u, quiet_z;
+        for (int q = 0; q < nq; q++)
+            if (!shard[q])
+                (uniform(q) ? quiet_u : quiet_z).push_back(q);
+        if (L >= PLAN_REG_MIN_L) {
+            // the generator's register bits go to the qubits the fewest factors touch
+            int uses[64] = {0};
+            for (const Factor &f : factors)
+                for (int j = 0; j < f.n; j++)
+                    uses[f.q[j]]++;           // (shard qubits are counted and never looked at)
+            std::vector<int> cand(quiet_u);
+            cand.insert(cand.end(), quiet_z.begin(), quiet_z.end());
+            std::stable_sort(cand.begin(), cand.end(), [&](int a, int b) {
+                if (uses[a] != uses[b])
+                    return uses[a] < uses[b];
+                return a > b;
+            });
+            std::vector<int> regq(cand.begin(), cand.begin() + (cand.size() < (size_t)PLAN_MULTI_R ? cand.size() : (size_t)PLAN_MULTI_R));
+            std::stable_sort(regq.begin(), regq.end(), [&](int a, int b) {
+                if (uses[a] != uses[b])
+                    return uses[a] > uses[b];
+                return a < b;
+            });
+            if (cand.size() - regq.size() >= (size_t)PLAN_LANE_BITS) {
+                bool is_reg[64] = {false};
+                for (int q : regq)
+                    is_reg[q] = true;
+                std::vector<int> others, zeros;
+                for (int q : quiet_u)
+                    if (!is_reg[q])
+                        others.push_back(q);
+                for (int q : quiet_z)
+                    if (!is_reg[q])
+                        zeros.push_back(q);
+                if (L >= PLAN_GEN_TOP_MIN_L) {
+                    zeros.insert(zeros.end(), regq.begin(), regq.end());      // highest local positions, fewest uses on top
+                    quiet_u.swap(others);
+                } else {
+                    size_t low = others.size() < (size_t)PLAN_LANE_BITS ? others.size() : (size_t)PLAN_LANE_BITS;
+                    quiet_u.assign(others.begin(), others.begin() + low);
+                    quiet_u.insert(quiet_u.end(), regq.begin(), regq.end());
+                    quiet_u.insert(quiet_u.end(), others.begin() + low, others.end());
+                }
+                quiet_z.swap(zeros);
+            }
+        }
+        int p = 0;
+        for (int q : quiet_u)
+            lay[q] = p++;
+        for (int q : quiet_z)
+            lay[q] = p++;
+        if (p != L)
+            return false;
+        for (int q = 0; q < nq; q++)
+            if (shard[q])
+                lay[q] = p++;                 // shard qubits in ascending order on the bits above the local ones
+    }
+
+    // ---- program.encode of [init] + the remapped factors; the tables in op order, transposed to (target value, select) -----
+    size_t n_ops = 1 + factors.size();
+    Ref rec(PyByteArray_FromStringAndSize(nullptr, (Py_ssize_t)(n_ops * sizeof(Record))));
+    Ref pool(PyByteArray_FromStringAndSize(nullptr, (Py_ssize_t)(pool_doubles * sizeof(double))));
+    if (!rec.p || !pool.p)
+        return false;
+    char *rp = PyByteArray_AS_STRING(rec.p);
+    double *pp = (double *)PyByteArray_AS_STRING(pool.p);
+    memset(rp, 0, n_ops * sizeof(Record));
+    Record r;
+    memset(&r, 0, sizeof r);
+    for (int q = 0; q < nq; q++)
+        if ((populated >> q) & 1)
+            r.mask |= (uint64_t)1 << lay[q];
+    r.kind = r.mask ? REC_OP_INIT_UNIFORM : REC_OP_INIT_ZERO;
+    memcpy(rp, &r, sizeof r);
+    size_t top = 0;
+    for (size_t i = 0; i < factors.size(); i++) {
+        const Factor &f = factors[i];
+        int ns = f.n - 1, k = shape_k[f.shape];
+        memset(&r, 0, sizeof r);
+        r.kind = REC_OP_DIAG;
+        r.n = f.n;
+        for (int j = 0; j < f.n; j++)
+            r.qubits[j] = lay[f.q[j]];
+        r.data_off = top;
+        memcpy(rp + (i + 1) * sizeof(Record), &r, sizeof r);
+        const double *c = col0[f.shape].at((Py_ssize_t)f.row << k);
+        for (int row = 0; row < 2; row++)
+            for (int j = 0; j < (1 << ns); j++) {
+                int at = 0;
+                for (int b = 0; b < ns; b++)
+                    at |= ((j >> b) & 1) << f.kept[b];
+                memcpy(pp + top, c + 4 * at + 2 * row, 2 * sizeof(double));
+                top += 2;
+            }
+    }
+    if (top != pool_doubles)
+        return false;
+    Ref layout(int_tuple(lay, nq));
+    if (!layout.p)
+        return false;
+    Ref out(Py_BuildValue("(OOOKn)", layout.p, rec.p, pool.p, (unsigned long long)populated, (Py_ssize_t)n_ops));
+    if (!out.p)
+        return false;
+    result.take(out);
+    return true;
+}
+
+PyObject *build_program(PyObject *, PyObject *args)
+{
+    Ref result;
+    if (build_program_impl(args, result))
+        return result.release();
+    PyErr_Clear();
+    Py_RETURN_NONE;
+}
+
 PyObject *set_block_of_key(PyObject *, PyObject *fn)
 {
     if (!PyCallable_Check(fn)) {
@@ -682,6 +1006,9 @@ PyMethodDef methods[] = {
      "read_circuit(circuit) -> (num_qubits, num_clbits, opened wires, groups, [(clbit, qubit)], source gates) of a circuit of h openings and "
      "extraction groups, or None (not mine)"},
     {"set_block_of_key", set_block_of_key, METH_O, "set_block_of_key(callable): ingest._block_of_key"},
+    {"build_program", build_program, METH_VARARGS,
+     "build_program(num_qubits, opened, groups, shapes, n_shards, layout, global_phase) -> (layout, qsv_op records, data pool, populated, "
+     "number of ops) of a circuit read_circuit described, shapes being (k, 2x2 stack, its column 0 times sqrt 2) per table shape, or None (not mine)"},
     {nullptr, nullptr, 0, nullptr}};
 
 PyModuleDef module = {PyModuleDef_HEAD_INIT, "_ingest_native", "native reader of clique-block signatures (qcmrf_amd.ingest)", -1, methods,

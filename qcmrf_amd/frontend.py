@@ -13,13 +13,21 @@ operands in the same shapes, so the tables are the pipeline's bit for bit:
     column 0 of every 2x2 times sqrt 2, selects on |0> sliced    passes.fold_fresh, passes._slice_zero (here as indexing)
 
 None means "not mine": the caller runs the pipeline, which decides or raises its own error.  Declining is always correct.
+
+The run path (``QsvBackend._prepare``) takes the two halves apart: ``front_half`` is the walk, the facts and the floating-point
+calls; then ``build_program`` does the fold's indexing, ``planner.plan`` and ``program.encode`` for the resulting init +
+diagonal factors in one native call (``_ingest_native.build_program``: integers, comparisons with 0 and 1 and byte copies,
+the same records and pool byte for byte), or, where that declines, ``fold_ops`` builds the op list here as before.
 """
 from __future__ import annotations
 
 import numpy as np
 
+from . import _lib
 from . import ingest as _ingest
 from . import ir
+from . import planner
+from . import program
 from .passes import _SQRT2
 
 _KEEP = {}
@@ -60,9 +68,9 @@ def _describe(circuit):
     return _ingest._ingest_native.read_circuit(circuit)
 
 
-def compile_blocks(circuit, dense_kmax=5):
-    """(Ingested, fused ops) of ``circuit`` as ingest + passes.optimise(level=3, fresh=True, dense_kmax=) give them, or
-    None.  ``Ingested.ops`` stays empty: the ingested op list is never built (``QsvBackend.compile`` has it)."""
+def front_half(circuit, dense_kmax):
+    """what both back halves start from: (Ingested facts, opened wires, groups, [(k, group indices, 2x2 stack)] per table
+    shape), or None.  The native walk, the facts, and all floating-point arithmetic but the sqrt 2 of the fold."""
     if not _ingest.native_frontend_on():
         return None
     got = _describe(circuit)
@@ -85,7 +93,12 @@ def compile_blocks(circuit, dense_kmax=5):
     if cregs:
         out.creg_sizes = [(getattr(r, "name", "c"), len(r)) for r in cregs]
     out.ingest_path = "native"
+    return out, opened, groups, _tables(groups)
 
+
+def _tables(groups):
+    """the floating-point half: [(k, indices of the groups on k qubits, their multiplexed 2x2s as one (n, 2^(k-1), 2, 2)
+    stack)] in order of first occurrence"""
     # the tables of all blocks, B and B' of every group in program order: one exp (ingest._finish_phase_blocks)
     angs = []
     for _, _, blk1, lam1, blk2, lam2 in groups:
@@ -102,18 +115,24 @@ def compile_blocks(circuit, dense_kmax=5):
     batches = {}
     for i, g in enumerate(groups):
         batches.setdefault(len(g[1]), []).append(i)
-    mats = [None] * len(groups)
     h = ir.FIXED_1Q["h"]
+    shapes = []
     for k, idx in batches.items():
         n = len(idx)
         t1 = np.moveaxis(np.stack([tables[2 * i] for i in idx]).reshape((n,) + (2,) * k), 1, -1).reshape(n, -1, 2)
         t2 = np.moveaxis(np.stack([tables[2 * i + 1] for i in idx]).reshape((n,) + (2,) * k), 1, -1).reshape(n, -1, 2)
         u = np.stack([h] * n)
-        m = _sandwich(t1, t2, u, u)
+        shapes.append((k, idx, _sandwich(t1, t2, u, u)))
+    return shapes
+
+
+def fold_ops(opened, groups, shapes):
+    """[init] + the diagonal factors: every multiplexer acts on an ancilla still |0>, so it writes column 0 of its 2x2
+    (passes.fold_fresh)"""
+    mats = [None] * len(groups)
+    for _, idx, m in shapes:
         for b, i in enumerate(idx):
             mats[i] = m[b]
-
-    # every multiplexer acts on an ancilla still |0>: it writes column 0 of its 2x2 (passes.fold_fresh)
     populated = 0
     for q in opened:
         populated |= 1 << q
@@ -127,4 +146,36 @@ def compile_blocks(circuit, dense_kmax=5):
         np.multiply(st[:, :, 0].T, _SQRT2, out=t.reshape(2, -1))
         factors.append(ir.Op("diag", qubits=tuple(sq) + (tg,), table=t))
         populated |= 1 << tg
-    return out, [ir.op_init(populated)] + factors
+    return [ir.op_init(populated)] + factors
+
+
+def compile_blocks(circuit, dense_kmax=5):
+    """(Ingested, fused ops) of ``circuit`` as ingest + passes.optimise(level=3, fresh=True, dense_kmax=) give them, or
+    None.  ``Ingested.ops`` stays empty: the ingested op list is never built (``QsvBackend.compile`` has it)."""
+    front = front_half(circuit, dense_kmax)
+    if front is None:
+        return None
+    return front[0], fold_ops(*front[1:])
+
+
+def build_program(front, n_shards, layout):
+    """(Plan, records, data pool) of what ``front_half`` answered, as ``planner.plan`` and ``program.encode`` give them for
+    ``fold_ops``'s ops, or None: the fold's indexing, the layout and the records are made in one native call
+    (``_ingest_native.build_program``).  Only the sqrt 2 of column 0 is multiplied here, once per table shape -- an
+    element-wise product does not depend on how the array is cut.  None means "not mine", as everywhere in this module."""
+    if not _ingest.native_program_on():
+        return None
+    ing, opened, groups, shapes = front
+    got = _ingest._ingest_native.build_program(
+        ing.num_qubits, opened, groups, [(k, m, np.multiply(m[..., 0], _SQRT2)) for k, _, m in shapes], n_shards, layout,
+        ing.global_phase)
+    if got is None:
+        return None
+    lay, rec, pool = got[:3]
+    rec = np.frombuffer(rec, dtype=_lib.OP_DTYPE)
+    data = np.frombuffer(pool, dtype=np.float64) if len(pool) else np.zeros(0, dtype=np.float64)
+    pl = planner.Plan()
+    pl.n_qubits, pl.n_shards = ing.num_qubits, n_shards
+    pl.initial_layout, pl.layout = list(lay), list(lay)
+    pl.ops = program.DecodedOps(rec, data)
+    return pl, rec, data

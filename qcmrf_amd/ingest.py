@@ -47,6 +47,7 @@ class Ingested:
         self.n_reset = 0              # "reset" ops
         self.n_reuse = 0              # gates, measures or conditions that touch a qubit measured earlier and not reset since
         self.compile_path = "passes"  # what made the fused ops of a run: "passes" (ingest + passes.optimise), "blocks" (qcmrf_amd.frontend)
+        self.plan_path = "python"     # what planned and encoded the fused ops of a run: "python" (planner.plan + program.encode), "native" (frontend.build_program)
         self.ingest_path = "python"   # what read this process's clique blocks: "native" (all of them), "python" (all, or there were none), "mixed"
 
 
@@ -359,6 +360,7 @@ except Exception:                         # not built, or does not load here: th
     _ingest_native = None
 _native_read = _ingest_native.read_block if _ingest_native is not None else None
 _native_frontend = _ingest_native is not None      # the front end (qcmrf_amd.frontend) is tried; it needs the reader on as well
+_native_program = _ingest_native is not None       # the front end's native back half (fold + plan + encode) is tried; it needs the front end on
 
 
 def native_available():
@@ -393,6 +395,24 @@ def use_native_frontend(on=True):
 def native_frontend_on():
     """the native front end is tried by the run path: its own switch and the reader's are both on"""
     return _native_frontend and _native_read is not None
+
+
+def use_native_program(on=True):
+    """force the switch: a circuit the native front end takes is folded, planned and encoded in one native call
+    (``qcmrf_amd.frontend.build_program``; ``on``, RuntimeError where the module is not available), or by
+    ``planner.plan`` and ``program.encode``.  Returns the previous setting.  The default is on wherever the module imports;
+    it is tried only while ``use_native`` and ``use_native_frontend`` are on too."""
+    global _native_program
+    was = _native_program
+    if on and _ingest_native is None:
+        raise RuntimeError("qcmrf_amd._ingest_native is not built or does not import (python -m qcmrf_amd.build)")
+    _native_program = bool(on)
+    return was
+
+
+def native_program_on():
+    """the native back half is tried by the run path: its own switch, the front end's and the reader's are all on"""
+    return _native_program and native_frontend_on()
 
 
 def _read_block(definition):

@@ -147,6 +147,43 @@ def encode(ops, n_meas=None):
     return rec, data
 
 
+class DecodedOps:
+    """The op list of a program that was encoded without one (``frontend.build_program``): ``init`` and ``diag`` records and
+    their pool read back into ``ir.Op`` on first access.  ``len()`` builds nothing: the run path asks for it on every run."""
+
+    def __init__(self, rec, data):
+        self._rec, self._data, self._ops = rec, data, None
+
+    def _decoded(self):
+        if self._ops is None:
+            from . import ir
+            ops = []
+            for r in self._rec:
+                kind = int(r["kind"])
+                if kind in (_lib.OP_INIT_ZERO, _lib.OP_INIT_UNIFORM):
+                    ops.append(ir.op_init(int(r["mask"])))
+                elif kind == _lib.OP_DIAG:
+                    n, off = int(r["n"]), int(r["data_off"])
+                    ops.append(ir.Op("diag", qubits=tuple(int(q) for q in r["qubits"][:n]),
+                                     table=self._data[off:off + (2 << n)].view(np.complex128).copy()))
+                else:
+                    raise ValueError("cannot decode op kind %d" % kind)
+            self._ops = ops
+        return self._ops
+
+    def __len__(self):
+        return len(self._rec)
+
+    def __iter__(self):
+        return iter(self._decoded())
+
+    def __getitem__(self, i):
+        return self._decoded()[i]
+
+    def __repr__(self):
+        return repr(self._decoded())
+
+
 def pauli_cumulative(probs, n):
     """QSV_OP_PAULI data: the 4^n cumulative probabilities in Pauli index order (qcmrf_amd.noise), every entry
     from the last non-zero probability on exactly 1.0 -- a draw u in [0, 1) picks the first p with u < cum[p]"""

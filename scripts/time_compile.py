@@ -1,6 +1,7 @@
 """host compile time of the 34-qubit circuit by stage (ingest, passes, plan, encode), no GPU needed, for both settings
 of the ingest switch (native block reader on / off; a tree without the reader reports the Python path alone), and the
-native front end that stands in for ingest + passes on the run path (qcmrf_amd/frontend.py) as a stage of its own:
+native front end that stands in for ingest + passes on the run path (qcmrf_amd/frontend.py) as a stage of its own, with its
+native back half (fold + plan + encode in one call, frontend.build_program) on and off:
     python scripts/time_compile.py            in-tree circuit container
     python scripts/time_compile.py --strict   the strict Qiskit double of tests/strict_qiskit (HAVE_QISKIT branch)
     python scripts/time_compile.py --walk     also: what the top-level loop of the walk costs next to the block reads
@@ -76,10 +77,13 @@ for on in settings:
 
 def front_end(reps):
     """the fast path of QsvBackend._prepare by stage: the native walk alone, walk + numpy half (= ingest + passes of the other
-    path), and _prepare as a whole (front end + plan + encode) with the front end on and off"""
+    path), and _prepare as a whole (front end + plan + encode) with the front end on and off; where the tree has the native
+    back half, also the front half alone (walk + facts + floating point), the back half alone (one multiply per table shape
+    + the native call), and _prepare with the back half on and off"""
     from qcmrf_amd import frontend
     best = {}
     opts = dict(be.options)
+    back = hasattr(ing_mod, "use_native_program")
     for rep in range(reps):
         t0 = time.perf_counter()
         got = frontend._describe(qc)
@@ -93,11 +97,29 @@ def front_end(reps):
         be._prepare(qc, opts)
         t5 = time.perf_counter()
         ing_mod.use_native_frontend(was)
-        for k, v in (("read_circuit (native walk)", t1 - t0), ("compile_blocks (walk + numpy half)", t2 - t1),
-                     ("_prepare, front end on", t3 - t2), ("_prepare, front end off", t5 - t4)):
+        rows = [("read_circuit (native walk)", t1 - t0), ("compile_blocks (walk + numpy half)", t2 - t1),
+                ("_prepare, front end on", t3 - t2), ("_prepare, front end off", t5 - t4)]
+        if back:
+            t6 = time.perf_counter()
+            front = frontend.front_half(qc, 5)
+            t7 = time.perf_counter()
+            done = frontend.build_program(front, 1, opts["layout"])
+            t8 = time.perf_counter()
+            ops = frontend.fold_ops(*front[1:])
+            t9 = time.perf_counter()
+            was = ing_mod.use_native_program(False)
+            t10 = time.perf_counter()
+            slow = be._prepare(qc, opts)
+            t11 = time.perf_counter()
+            ing_mod.use_native_program(was)
+            assert done is not None and prepared[0].plan_path == "native" and slow[0].plan_path == "python" and len(ops) == len(done[0].ops)
+            rows += [("front_half (walk + facts + floating point)", t7 - t6), ("build_program (native fold + plan + encode)", t8 - t7),
+                     ("fold_ops (the fold in numpy)", t9 - t8), ("_prepare, native program off (fold_ops + plan + encode)", t11 - t10)]
+        for k, v in rows:
             best[k] = min(best.get(k, 1e9), v)
     assert got is not None and fast is not None and prepared[0].compile_path == "blocks"
-    print("front end: compile_path=%s, %d groups, %d fused ops" % (prepared[0].compile_path, len(got[3]), len(fast[1])))
+    print("front end: compile_path=%s plan_path=%s, %d groups, %d fused ops" % (prepared[0].compile_path, getattr(prepared[0], "plan_path", "python (no switch in this tree)"),
+                                                                                len(got[3]), len(fast[1])))
     print("  best of %d [ms]:" % reps, {k: round(v * 1e3, 3) for k, v in best.items()})
 
 
