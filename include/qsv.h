@@ -569,6 +569,8 @@ int qsv_timer_end(qsv_handle* h, double* ms);
  *   kernels     unroll [4], lowt_shuffle [1], pair_variant [0], kq_mfma [1], blocks_per_cu [65536]
  *               swizzle [1]        one-gate kernels: lane bit 5 of a wave access carries address bit 11 (two 512-byte runs 32 KiB apart);
  *                                  1 from 2^26 amplitudes per shard, 2 from 2^14, 0 never        lane_map_min_l [26]  same for k_multi tiles other than bits 6..10
+ *               kq_grid [0]        diagnostic: the matrix-core dense-gate launches (qsv_apply_kq, QSV_OP_KQ with k >= 3) take at most this
+ *                                  many workgroups, 0 = no cap; which wave computes a batch changes, no amplitude does
  *   noisy       noisy_grid [0]     workgroups of qsv_noisy_sample, qsv_noisy_sample_hbm and each round of qsv_noisy_sample_accept: 0 = as many as the
  *                                  chip holds at once, else at most this many
  *               noisy_dynamic_kernels [0]  diagnostic: 1 sends every per-shot stream through the kernels of qsv_noise_dynamic.hip, which

@@ -233,6 +233,7 @@ struct qsv_handle {
   int opt_fold_init_h = 1;            // qsv_exec: H on a still-|0> qubit right after an init is part of the init write
   int exec_ops_left = 1 << 30;            // qsv_exec: ops of the running program not yet consumed (group_fits lets the tail ride along)
   int opt_kq_blocks_per_cu = 0;       // k_kq_mfma grid: workgroups per CU (0: 64)
+  int opt_kq_grid = 0;                // matrix-core dense-gate launches (launch_kq_mfma): workgroups at most (0: no cap) -- a diagnostic, the walks of tests/_kq_cases.py
   int opt_kq3_tile = 1;               // dense 3-qubit gates on the vector units (k_kq_tile) instead of I (x) U on a 16 x 16 matrix-core tile
   int opt_kq_chunked = 0;             // k_kq_mfma: every wave walks a contiguous run of batches instead of a grid-stride loop (experiment)
   int opt_blocksum_variant = 6;       // access pattern of the read-only passes (qsv_measure.inc): 2 wave-contiguous, 4 no grid-stride loop, 1 index swizzle

@@ -11,7 +11,9 @@ template <int K>
 static void launch_kq_mfma(const qsv_handle* h, const Shard& s, uint64_t nbatch, const BitIns& ins,
                            const KqOffs& offs, const double* ur, const double* ui) {
   // every wave keeps U in registers; give each at least ~8 batches to amortise loading it
-  const uint64_t blocks = std::max<uint64_t>(1, std::min<uint64_t>((nbatch + 31) / 32, (uint64_t)s.n_cu * (h->opt_kq_blocks_per_cu > 0 ? h->opt_kq_blocks_per_cu : 64)));
+  // option kq_grid (a diagnostic, 0 = none): no launch below takes more workgroups than that -- which wave gets which batch changes, nothing else
+  const uint64_t cap = h->opt_kq_grid > 0 ? (uint64_t)h->opt_kq_grid : ~0ull;
+  const uint64_t blocks = std::min(cap, std::max<uint64_t>(1, std::min<uint64_t>((nbatch + 31) / 32, (uint64_t)s.n_cu * (h->opt_kq_blocks_per_cu > 0 ? h->opt_kq_blocks_per_cu : 64))));
   const bool nt = single_nt(h, ins.n ? ins.pos[0] : 0);     // lowest target bit: inside a 128-byte line it loses (kq5 on bits 0..4: 0.60 -> 0.54)
   const dim3 g((unsigned)blocks), b(QSV_TPB);
 #define QSV_KQ_GO(KERNEL) hipLaunchKernelGGL(KERNEL, g, b, 0, s.stream, s.amp, nbatch, ins, offs, ur, ui, h->opt_kq_chunked)
@@ -60,7 +62,7 @@ static void launch_kq_mfma(const qsv_handle* h, const Shard& s, uint64_t nbatch,
 #define QSV_KQ_LDS_GO(NW, DBG, PD) do { \
       const size_t shm = (DBG) == 3 ? 0 : (size_t)D / 16 * (D / 4) * 3 * 64 * sizeof(double) + (size_t)(NW) * D * QSV_KQ_LDS_RS; \
       const uint64_t want = (nbatch + (NW) * 16 - 1) / ((NW) * 16); \
-      const dim3 gl((unsigned)std::max<uint64_t>(1, std::min<uint64_t>(want, (uint64_t)s.n_cu * bpc))); \
+      const dim3 gl((unsigned)std::min(cap, std::max<uint64_t>(1, std::min<uint64_t>(want, (uint64_t)s.n_cu * bpc)))); \
       if (shm > 64 * 1024) { \
         hipFuncSetAttribute(reinterpret_cast<const void*>(&k_kq_lds<K, true, NW, DBG, PD>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm); \
         hipFuncSetAttribute(reinterpret_cast<const void*>(&k_kq_lds<K, false, NW, DBG, PD>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm); \
@@ -85,7 +87,7 @@ static void launch_kq_mfma(const qsv_handle* h, const Shard& s, uint64_t nbatch,
   if (variant == 5 && nbatch % 2 == 0) {                    // 5: two batches per step, 32 groups wide (two 512-byte runs per wave access)
     const size_t shm = (size_t)(1 << K) / 16 * ((1 << K) / 4) * 3 * 64 * sizeof(double);
     const uint64_t nsteps = nbatch / 2;
-    const dim3 gw((unsigned)std::max<uint64_t>(1, std::min<uint64_t>((nsteps + 15) / 16, (uint64_t)s.n_cu * (h->opt_kq_blocks_per_cu > 0 ? h->opt_kq_blocks_per_cu : 64))));
+    const dim3 gw((unsigned)std::min(cap, std::max<uint64_t>(1, std::min<uint64_t>((nsteps + 15) / 16, (uint64_t)s.n_cu * (h->opt_kq_blocks_per_cu > 0 ? h->opt_kq_blocks_per_cu : 64)))));
     if (nt) hipLaunchKernelGGL((k_kq_mfma3w<K, true>), gw, b, shm, s.stream, s.amp, nsteps, ins, offs, ur, ui);
     else    hipLaunchKernelGGL((k_kq_mfma3w<K, false>), gw, b, shm, s.stream, s.amp, nsteps, ins, offs, ur, ui);
     return;
