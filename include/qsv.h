@@ -239,6 +239,32 @@ int qsv_sample_unordered(qsv_handle* h, uint64_t shots, uint64_t seed, const int
 int qsv_sample_cond_unordered(qsv_handle* h, uint64_t shots, uint64_t seed, const int* meas_qubits, int n_meas,
                               uint64_t fix_mask, uint64_t fix_val, uint64_t* out_bits, double* mass);
 
+/* Many marginals of the conditioned state in one pass.  Group g lists group_k[g] distinct qubits (the lists concatenated
+ * in `qubits`; groups may overlap, group_k[g] == 0 is allowed); off_g = sum of 2^group_k over the groups before g.
+ *   out[off_g + j] = sum |amp[x]|^2 over the global indices x owned by this process with (x & fix_mask) == fix_val whose
+ *                    bits qubits_g[b] spell j (bit b of j <-> qubits_g[b], as in qsv_apply_diag);
+ *   *mass          = the same sum without the bin condition (mass may be NULL).
+ * Not normalised; the shards of a process are summed, handles of several ranks return this rank's part.  A group qubit
+ * may be a shard bit (its value is the shard's) or a fixed bit (the bins contradicting fix_val are exactly 0.0; a group
+ * without qubits has one bin, the mass); a fixed shard bit skips the shards that disagree, as in qsv_sample_cond.
+ * Cost: one pass over the compact index space of qsv_sample_cond, 2^(L-f) loads per shard for f fixed bits local to it
+ * (booked under QSV_K_PROB with 16 B each, one launch of that kind per shard); implied zeros are not loaded; nothing is
+ * cached between calls.  A deferred shard is prepared exactly as for qsv_sample_cond (the tiles holding the sub-cube
+ * listed and stored, one listed_launches, the shard still deferred -- or realised, by the same rule and option
+ * post_select_list); with fix_mask == 0 the sub-cube is the shard and a deferred shard is realised.
+ * Reproducible: out and *mass are a pure function of (shard contents, shard structure, groups, mask) -- the same bits
+ * from call to call, for every number of workgroups (option marginals_grid), for a stored and for a deferred-and-listed
+ * shard: a fixed tree of additions (spelled out in qsv_marginals.inc), no floating-point atomics.
+ * QSV_E_BADARG, checked before the first launch, with a message naming the group: a NULL argument, n_groups outside
+ * 1..QSV_MARG_MAX_GROUPS, a group_k outside 0..QSV_MARG_MAX_K, more than QSV_MARG_MAX_BINS bins, a qubit at or above
+ * n_qubits, a qubit repeated within a group, fix_val outside fix_mask, a mask bit at or above n_qubits.  More than 28
+ * fixed bits local to a shard: QSV_E_UNSUPPORTED. */
+#define QSV_MARG_MAX_GROUPS 64     /* groups of one call                         */
+#define QSV_MARG_MAX_K       8     /* qubits of one group                        */
+#define QSV_MARG_MAX_BINS 4096     /* sum over the groups of 2^k_g (32 KiB)      */
+int qsv_marginals_cond(qsv_handle* h, int n_groups, const int* group_k, const int* qubits,
+                       uint64_t fix_mask, uint64_t fix_val, double* out, double* mass);
+
 /* copy amplitudes [start, start+count) of the GLOBAL index space into out (2*count doubles);
  * the range must lie inside shards owned by this process. */
 int qsv_get_amplitudes(qsv_handle* h, uint64_t start, uint64_t count, double* out);
@@ -510,7 +536,9 @@ int qsv_get_stats(qsv_handle* h, qsv_stats* out);
  * ("realises" it; booked under QSV_K_INIT_PROD with the bytes stored).  Entries that realise: qsv_get_amplitudes,
  * qsv_set_amplitudes, qsv_copy_state (source), qsv_probabilities*, qsv_expect_diag, qsv_apply_*, qsv_swap_layout (and
  * its exchanges), qsv_ipc_export, qsv_density_*, a qsv_exec that does not start with an init, and qsv_norm / qsv_sample
- * when they cannot use the tile sums (cache_sums or fused_sums 0).  Entries that do not: qsv_sample on the tile path,
+ * when they cannot use the tile sums (cache_sums or fused_sums 0), qsv_sample_cond / qsv_marginals_cond when no block
+ * bit of the tile index is fixed (or by option post_select_list).  Entries that do not: qsv_sample on the tile path,
+ * qsv_sample_cond / qsv_marginals_cond when they list the tiles that hold the sub-cube,
  * qsv_norm from the cached sums, qsv_tile_sums, qsv_noisy_sample* (they keep their own states), stats, timers, options, qsv_sync.
  * Deferred state ends with realisation or with the next init that writes; a program refused before its init writes
  * leaves the deferred state, recipe included, as it was.
@@ -566,6 +594,8 @@ int qsv_timer_end(qsv_handle* h, double* ms);
  *               post_select_list [-1]  qsv_sample_cond on a deferred shard: -1 the tiles holding the matching amplitudes are listed and
  *                                  stored when they are at most 1/16 of the tiles and the list fits a quarter of the arena, else the
  *                                  state is realised; 0 always realised; 1 listed whenever a block bit is fixed and the list fits.  Same words.
+ *               marginals_grid [0] diagnostic: qsv_marginals_cond takes at most this many workgroups, 0 = as many as the chip holds;
+ *                                  which workgroup walks a chunk changes, no bit of the result does
  *   kernels     unroll [4], lowt_shuffle [1], pair_variant [0], kq_mfma [1], blocks_per_cu [65536]
  *               swizzle [1]        one-gate kernels: lane bit 5 of a wave access carries address bit 11 (two 512-byte runs 32 KiB apart);
  *                                  1 from 2^26 amplitudes per shard, 2 from 2^14, 0 never        lane_map_min_l [26]  same for k_multi tiles other than bits 6..10

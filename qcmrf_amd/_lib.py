@@ -87,6 +87,7 @@ SIGNATURES = {
     "qsv_sample_cond": (_i, [_vp, _u64, _u64, _ip, _i, _u64, _u64, _u64p, _dp]),
     "qsv_sample_unordered": (_i, [_vp, _u64, _u64, _ip, _i, _u64p]),
     "qsv_sample_cond_unordered": (_i, [_vp, _u64, _u64, _ip, _i, _u64, _u64, _u64p, _dp]),
+    "qsv_marginals_cond": (_i, [_vp, _i, _ip, _ip, _u64, _u64, _dp, _dp]),
     "qsv_get_amplitudes": (_i, [_vp, _u64, _u64, _dp]),
     "qsv_set_amplitudes": (_i, [_vp, _u64, _u64, _dp]),
     "qsv_copy_state": (_i, [_vp, _vp]),
@@ -517,6 +518,25 @@ class Engine:
     def sample_cond_unordered(self, shots, seed, meas_qubits=None, fix_mask=0, fix_val=0):
         """``sample_cond`` with the words in no particular order (qsv_sample_cond_unordered); the mass is the same"""
         return self._sample_cond(self._lib.qsv_sample_cond_unordered, shots, seed, meas_qubits, fix_mask, fix_val)
+
+    def marginals_cond(self, groups, fix_mask=0, fix_val=0):
+        """(list of float64 arrays, mass): for every group (a list of distinct qubits) the 2^k sums of |amp|^2 over the
+        basis states g with (g & fix_mask) == fix_val whose group bits spell the bin (bin bit b <-> group[b]), and the
+        sum without the bin condition; not normalised, this process's shards only.  One pass over the matching
+        amplitudes for all groups, the same bits on every call (qsv_marginals_cond)."""
+        groups = [[int(q) for q in g] for g in groups]
+        ka, kp = _ia([len(g) for g in groups])
+        qa, qp = _ia([q for g in groups for q in g] or [0])
+        # (a call with more bins than the entry point takes is refused there before anything is written)
+        out = np.zeros(max(1, min(4096, sum(1 << len(g) for g in groups))), dtype=np.float64)
+        mass = C.c_double(0.0)
+        _chk(self._lib.qsv_marginals_cond(self._h, len(groups), kp, qp, int(fix_mask), int(fix_val),
+                                          out.ctypes.data_as(_dp), C.byref(mass)))
+        res, off = [], 0
+        for g in groups:
+            res.append(out[off:off + (1 << len(g))].copy())
+            off += 1 << len(g)
+        return res, mass.value
 
     def amplitudes(self, start=0, count=None):
         if count is None:

@@ -325,6 +325,25 @@ class QsvBackend:
             s0, s1 = sum(p[0] for p in parts), sum(p[1] for p in parts)
         return s0, s1
 
+    def marginals(self, groups, fixed=None):
+        """(list of arrays, mass) on the state the LAST run left: for every group of logical qubits the 2^k sums of
+        |amp|^2 over the basis states in which every qubit of ``fixed`` ({logical qubit: 0/1}) has the given value and
+        the group's qubits spell the bin (bin bit b <-> group[b]); ``mass`` is the sum over all those states.  Not
+        normalised.  One pass over the matching amplitudes for all groups (qsv_marginals_cond); a deferred state whose
+        fixed bits select tiles stays deferred.  One process only, as post_select; virtual shards are fine."""
+        eng, pl = self.last_engine, self.last_plan
+        if eng is None or pl is None:
+            raise RuntimeError("marginals needs a state: run() a circuit on this backend first")
+        comm = self._last_comm
+        if comm is not None and comm.world > 1:
+            raise ValueError("marginals runs in one process; this state is spread over %d ranks" % comm.world)
+        phys = [[pl.layout[q] for q in g] for g in groups]
+        fm = fv = 0
+        for q, v in (fixed or {}).items():
+            fm |= 1 << pl.layout[q]
+            fv |= int(bool(v)) << pl.layout[q]
+        return eng.marginals_cond(phys, fm, fv)
+
     def close(self):
         if self._engine is not None:
             self._engine.close()

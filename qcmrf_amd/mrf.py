@@ -51,3 +51,44 @@ def success_probability(cliques, theta, beta=1.0):
     """probability that every real-part-extraction ancilla reads 0: Z / 2^n"""
     p, lnZ = gibbs_pmf(cliques, theta, beta)
     return float(np.exp(lnZ) / 2 ** num_vertices(cliques))
+
+
+def clique_index(cliques, x_or_xid):
+    """per clique the index of the clique state of every joint state, the first variable of C most significant (the
+    order of ``log_potentials``); joint states as xids (1-d) or as an (N, n) array of 0/1"""
+    n = num_vertices(cliques)
+    a = np.asarray(x_or_xid)
+    if a.ndim == 2:
+        if a.shape[1] != n:
+            raise ValueError("joint states have %d columns, the model has %d variables" % (a.shape[1], n))
+        bits = [a[:, v].astype(np.int64) & 1 for v in range(n)]
+    elif a.ndim == 1:
+        xid = a.astype(np.int64)
+        bits = [(xid >> (n - 1 - v)) & 1 for v in range(n)]
+    else:
+        raise ValueError("joint states are xids (1-d) or an (N, n) array of 0/1")
+    out = []
+    for C in cliques:
+        y = np.zeros(a.shape[0], dtype=np.int64)
+        for v in C:
+            y = (y << 1) | bits[v]
+        out.append(y)
+    return out
+
+
+def marginals(cliques, theta, beta=1.0):
+    """mu[offset(C) + y] = P(x_C = y) under the Gibbs distribution, in the order of ``theta``: the exact expectations of
+    the sufficient statistics (marginal inference), summed from ``gibbs_pmf``"""
+    p, _ = gibbs_pmf(cliques, theta, beta)
+    ys = clique_index(cliques, np.arange(p.size))
+    return np.concatenate([np.bincount(y, weights=p, minlength=2 ** len(C)) for C, y in zip(cliques, ys)])
+
+
+def empirical_marginals(cliques, samples):
+    """mu-hat: the relative frequency of every clique state in ``samples`` -- an (N, n) array of 0/1, or N xids in the
+    ``log_potentials`` convention -- in the order of ``theta``"""
+    ys = clique_index(cliques, samples)
+    N = np.asarray(samples).shape[0]
+    if N == 0:
+        raise ValueError("no samples")
+    return np.concatenate([np.bincount(y, minlength=2 ** len(C)) / float(N) for C, y in zip(cliques, ys)])

@@ -147,6 +147,32 @@ class QCMRF(QuantumCircuit):
         s0, s1 = backend.expectation_diagonal(tab, qs, fixed)
         return s0 / s1, s1
 
+    def marginals(self, backend, post_selected=True, circuit=None, **run_options):
+        """All clique marginals of the state this circuit prepares from ONE run and one conditioned device pass:
+        ``(mu, p_success)`` with ``mu[offset(C) + y] = P(x_C = y)``, a float64 vector of length ``dimension`` in the order
+        of ``theta`` (clique by clique, y as ``itertools.product([0, 1], repeat=len(C))`` counts, the first variable of C
+        most significant).  post_selected=True: in the state conditioned on every ancilla and the AND scratch qubit
+        reading 0 -- the Gibbs state -- and ``p_success`` is the probability of that condition; only the matching
+        amplitudes are read, and a state the engine left deferred stays deferred where the condition selects tiles.
+        post_selected=False: the marginals of the whole state (``p_success`` 1).  With the data marginals mu-hat,
+        beta (mu-hat - mu) is the gradient of the log-likelihood (``qcmrf_amd.learn``).  ``circuit``: a lowering of this
+        circuit (``transpile``) to run in its place."""
+        n, W = self._n, self._n + self._num_cliques + 1
+        run = self if circuit is None else circuit
+        if self._with_measurements and post_selected:
+            # a run that conditions leaves a deferrable state deferred (a plain run without shots has it written at once)
+            backend.run(run, shots=0, post_select=self.post_selection(), **run_options)
+        else:
+            backend.run(run, shots=0, **run_options)
+        fixed = {q: 0 for q in range(n, W)} if post_selected else None
+        # bin bit b <-> group[b]: the LAST variable of C on bit 0 makes the first one most significant
+        groups = [[n - 1 - v for v in reversed(C)] for C in self._cliques]
+        parts, mass = backend.marginals(groups, fixed)
+        norm = backend.last_engine.norm()
+        if not mass > 0:
+            raise ValueError("the post-selected outcome has zero probability")
+        return np.concatenate([np.asarray(p, dtype=np.float64) for p in parts]) / mass, mass / norm
+
     def post_selection(self):
         """``{classical bit: 0}`` for every clique ancilla: the branch in which the circuit prepares the Gibbs state
         (real part extraction succeeds when the ancilla reads 0, QCMRF.py:239).  For ``backend.run(self, shots,

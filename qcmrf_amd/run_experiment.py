@@ -76,7 +76,14 @@ def main(argv=None):
     ap.add_argument("--post-select", action="store_true",
                     help="every shot from the branch in which all clique ancillas read 0; also writes the success probabilities "
                          "(exact; estimated from the attempts made when the run is noisy)")
+    ap.add_argument("--marginals", action="store_true",
+                    help="also write every circuit's clique marginals and success probability (ideal state-vector run, one "
+                         "conditioned device pass per circuit) to marginals_simulation_<SCALE>.json")
     args = ap.parse_args(argv)
+    if args.marginals and (args.method is not None or any(x is not None for x in (args.depolarizing, args.readout, args.t1, args.t2,
+                                                                                  args.gate_time, args.coherent_cx))):
+        ap.error("--marginals reads the ideal state vector and takes no noise option or --method: the marginals of a noisy run "
+                 "are sums over the exact distribution that method=\"density_matrix\" returns (Result.get_probabilities())")
     model = ibm_like_model(args.depolarizing, args.readout, args.t1, args.t2, args.gate_time, args.coherent_cx)
 
     np.random.seed(1984)
@@ -94,6 +101,7 @@ def main(argv=None):
         f.write(json.dumps({"GRAPHS": GRAPHS, "THETAS": THETAS}, indent=4))
 
     CIRCS = [QCMRF(C, THETAS[j][i], with_measurements=True) for j, C in enumerate(GRAPHS) for i in range(args.reps)]
+    MODELS = list(CIRCS)
     POST = [qc.post_selection() for qc in CIRCS] if args.post_select else None      # (classical bits: lowering keeps them)
     ACCEPT = POST is not None and (model is not None or args.method is not None)    # no exact conditioned state vector: accept
     if HAVE_QISKIT:                                   # pragma: no cover - Qiskit absent in this image
@@ -132,6 +140,11 @@ def main(argv=None):
         name = "probs_simulation_" if model is None else "probs_simulation_noisy_"
         with open(os.path.join(args.outdir, name + str(args.scale) + ".json"), "w") as f:
             f.write(json.dumps(probs if isinstance(probs, list) else [probs], indent=4))
+    if args.marginals:
+        # the lowered circuit where there is one, conditioned through the model's own classical bits
+        rows = [qc.marginals(simulator, circuit=c) for qc, c in zip(MODELS, CIRCS)]
+        with open(os.path.join(args.outdir, "marginals_simulation_" + str(args.scale) + ".json"), "w") as f:
+            f.write(json.dumps([{"mu": mu.tolist(), "success": float(p)} for mu, p in rows], indent=4))
     return counts
 
 
