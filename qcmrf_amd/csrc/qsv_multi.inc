@@ -71,15 +71,20 @@ static double op_cost(const LocalOp& lo, bool lane_target, const std::vector<int
   }
 }
 
-static bool groupable(const qsv_handle* h, const LocalOp& lo) {
-  if (h->opt_multi_r < 1) return false;
-  if ((lo.type == 0 || lo.type == 1) && (int)lo.list.size() > QSV_MULTI_MAXLIST) return false;
-  return true;
-}
 static size_t table_cplx_of(const LocalOp& lo) {
   if (lo.type == 0) return (size_t)4 << lo.list.size();
   if (lo.type == 1) return (size_t)1 << lo.list.size();
   return 0;
+}
+// complex table entries one pass may stage: 40 KiB of LDS, less the identity table flush_group appends
+#define QSV_MULTI_TABLE_CPLX (2560 - 4)
+static bool groupable(const qsv_handle* h, const LocalOp& lo) {
+  if (h->opt_multi_r < 1) return false;
+  if ((lo.type == 0 || lo.type == 1) && (int)lo.list.size() > QSV_MULTI_MAXLIST) return false;
+  // a table no pass can hold (a mux with 10 selects: 4096 entries): group_add would take it into an empty group all
+  // the same, and the pass would ask for more dynamic LDS than k_multi may have.  It runs as its dedicated kernel.
+  if (table_cplx_of(lo) > QSV_MULTI_TABLE_CPLX) return false;
+  return true;
 }
 
 // lane bits 3..5 in use: static lane targets sitting there plus borrowed ones
@@ -131,7 +136,7 @@ static bool group_fits(const qsv_handle* h, const PendingGroup& g, const LocalOp
     if (!g.dyn_targets.empty() || pl == PL_DYN_NEW) return false;
     if ((int)g.targets.size() + (pl == PL_REG_NEW ? 1 : 0) > std::min(h->opt_multi_r, h->opt_general_r)) return false;
   }
-  if (g.table_cplx + table_cplx_of(lo) > 2560 - 4) return false;  // 40 KiB of LDS tables
+  if (g.table_cplx + table_cplx_of(lo) > QSV_MULTI_TABLE_CPLX) return false;  // 40 KiB of LDS tables
   // keep the pass HBM bound: a general (masked / non-table) pass is cut when its arithmetic outgrows
   // what one read + write of the shard hides; table-only passes of a fused circuit are planned in
   // Python (lane quota) and measured to stay below it
@@ -1018,9 +1023,11 @@ static int flush_group(qsv_handle* h, Shard& s, PendingGroup& g, bool final_pass
   if (h->opt_trace_passes) {
     int hist[11] = {0};
     for (const MultiOp& mo : sorted) ++hist[mo.shape];
-    fprintf(stderr, "[qsv pass] shard %d R %d mode %d init %d ops %zu xframe %d | tab %d/%d x %d mat %d | diag %d/%d phase %d | lane tab %d/%d x %d mat %d\n",
+    fprintf(stderr, "[qsv pass] shard %d R %d mode %d init %d ops %zu xframe %d | tab %d/%d x %d mat %d | diag %d/%d phase %d | lane tab %d/%d x %d mat %d"
+                    " | rounds %d lanes %d/%d/%d tables %d\n",
             (int)(&s - &h->shards[0]), R, mode, (int)init, g.ops.size(), __builtin_popcountll(xmask), hist[GS_TAB_T], hist[GS_TAB_P], hist[GS_X],
-            hist[GS_MAT], hist[GS_DIAG_T], hist[GS_DIAG_A], hist[GS_PHASE], hist[GS_LTAB_T], hist[GS_LTAB_A], hist[GS_LX], hist[GS_LMAT]);
+            hist[GS_MAT], hist[GS_DIAG_T], hist[GS_DIAG_A], hist[GS_PHASE], hist[GS_LTAB_T], hist[GS_LTAB_A], hist[GS_LX], hist[GS_LMAT],
+            nrounds, lp.pos[0], lp.pos[1], lp.pos[2], ntab);
   }
   if (mode == 0 && R > QSV_GENERAL_MAXR) return fail(QSV_E_UNSUPPORTED, "general k_multi pass on %d register bits (limit %d)", R, QSV_GENERAL_MAXR);
   // the init-fused pass (write only) is a different kernel instantiation: accounted on its own

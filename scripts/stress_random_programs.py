@@ -1,5 +1,5 @@
 """GPU box: differential stress of qsv_exec's pass construction -- random programs of table ops
-(multiplexed 2x2 with RX-like or general matrices, diagonals), controlled gates, X and phases on
+(multiplexed 2x2 with RX-like, asymmetric RX-like or general matrices, diagonals), controlled gates, X and phases on
 random bits, with and without a leading init, random pass hints and engine options -- against the
 numpy engine.  Not part of the test suite (minutes); run after touching qsv_multi.inc.
 With sample_shots > 0 every program is also sampled and the words are held to the exact sampling contract
@@ -121,6 +121,19 @@ def run(n_cases=300, seed=7, verbose=True, only=None, override=None, widths=(14,
         rs2 = np.random.RandomState([int(seed) & 0xffffffff, case])
         opts.update({"general_combos": int(rs2.choice([1, 1, 0])), "fold_init_h": int(rs2.choice([1, 1, 0])),
                      "lowctl_mask": int(rs2.choice([1, 1, 0])), "single_shortcut": int(rs2.choice([1, 1, 1, 0]))})
+        # half of the RX-like programs get ASYMMETRIC RX-like tables [[c, is], [-is, -c]] (unitary, c0 != c1 and s0 != s1: a MODE 2
+        # kernel that mixes up the halves of a pair shows), their bare 2x2 gates as muxes without selects so that the pass stays
+        # a table pass, and a leading init on a mask of their own where they had none (drawn from rs2, like the options above)
+        if style == 0 and rs2.rand() < 0.5:
+            def amat():
+                a = float(rs2.uniform(0.3, 1.2)) * float(rs2.choice([-1.0, 1.0]))
+                return np.array([[complex(np.cos(a), 0.0), complex(0.0, np.sin(a))], [complex(0.0, -np.sin(a)), complex(-np.cos(a), 0.0)]])
+            for i, o in enumerate(ops):
+                if o.kind in ("mux", "u"):
+                    ops[i] = ir.op_mux(o.ctrls, o.target, np.array([amat() for _ in range(2 ** len(o.ctrls))]))
+                    ops[i].new_pass = o.new_pass
+            if ops[0].kind != "init":
+                ops.insert(0, ir.op_init(int(rs2.randint(0, 1 << W))))
         if only is not None and (case != only if only >= 0 else case < -only):
             continue                                       # replay mode (CASE, or -CASE: from that case on): the generator state advances, nothing runs
         if override:
