@@ -265,6 +265,31 @@ int qsv_sample_cond_unordered(qsv_handle* h, uint64_t shots, uint64_t seed, cons
 int qsv_marginals_cond(qsv_handle* h, int n_groups, const int* group_k, const int* qubits,
                        uint64_t fix_mask, uint64_t fix_val, double* out, double* mass);
 
+/* The k most probable basis states of the conditioned state in one pass: exact MAP (k = 1) and top-k inference.
+ * Candidates: the global indices x owned by this process with (x & fix_mask) == fix_val; the weight of x is
+ *   p(x) = re*re + im*im, each product and the sum rounded separately, no fused contraction -- deliberately NOT the fma
+ *   the summing kernels (qsv_marginals_cond, qsv_expect_diag) use: numpy's a.real*a.real + a.imag*a.imag on the
+ *   amplitudes read back gives the same bits.
+ * Order: x comes before y iff p(x) > p(y), or p(x) == p(y) and x < y -- strict and total.
+ * Output: the first min(k, number of candidates with p > 0) candidates in that order, out_index[i] and out_p[i];
+ *   *n_found is that number.  A candidate whose p is not > 0 (a 0, an implied zero, a NaN) is never returned; entries of
+ *   out_index / out_p from n_found on are left untouched.
+ * The shards of a process are merged on the host by the same order, an index carries its shard's bits; a fixed shard bit
+ * skips the shards that disagree, as in qsv_marginals_cond; handles of several ranks return this rank's part.
+ * The result is a pure function of the state: selection under a strict total order does not depend on the number of
+ * workgroups (option top_grid) or on the order in which candidates are compared; no floating-point atomics.
+ * Cost: one pass over the compact index space of qsv_sample_cond, 2^(L-f) loads per shard for f fixed bits local to it
+ * (booked under QSV_K_PROB with 16 B each, one launch of that kind per shard); implied zeros are not loaded; nothing is
+ * cached between calls.  A deferred shard is prepared exactly as for qsv_marginals_cond (the tiles holding the sub-cube
+ * listed and stored, one listed_launches, the shard still deferred -- or realised, by the same rule and option
+ * post_select_list); with fix_mask == 0 a deferred shard is realised.
+ * QSV_E_BADARG, checked before the first launch, with a message: a NULL argument, k outside 1..QSV_TOP_MAX_K, fix_val
+ * outside fix_mask, a mask bit at or above n_qubits.  More than 28 fixed bits local to a shard: QSV_E_UNSUPPORTED.
+ * After a refusal the handle is usable. */
+#define QSV_TOP_MAX_K 64
+int qsv_top_cond(qsv_handle* h, int k, uint64_t fix_mask, uint64_t fix_val,
+                 uint64_t* out_index /* k */, double* out_p /* k */, int* n_found);
+
 /* copy amplitudes [start, start+count) of the GLOBAL index space into out (2*count doubles);
  * the range must lie inside shards owned by this process. */
 int qsv_get_amplitudes(qsv_handle* h, uint64_t start, uint64_t count, double* out);
@@ -536,9 +561,9 @@ int qsv_get_stats(qsv_handle* h, qsv_stats* out);
  * ("realises" it; booked under QSV_K_INIT_PROD with the bytes stored).  Entries that realise: qsv_get_amplitudes,
  * qsv_set_amplitudes, qsv_copy_state (source), qsv_probabilities*, qsv_expect_diag, qsv_apply_*, qsv_swap_layout (and
  * its exchanges), qsv_ipc_export, qsv_density_*, a qsv_exec that does not start with an init, and qsv_norm / qsv_sample
- * when they cannot use the tile sums (cache_sums or fused_sums 0), qsv_sample_cond / qsv_marginals_cond when no block
+ * when they cannot use the tile sums (cache_sums or fused_sums 0), qsv_sample_cond / qsv_marginals_cond / qsv_top_cond when no block
  * bit of the tile index is fixed (or by option post_select_list).  Entries that do not: qsv_sample on the tile path,
- * qsv_sample_cond / qsv_marginals_cond when they list the tiles that hold the sub-cube,
+ * qsv_sample_cond / qsv_marginals_cond / qsv_top_cond when they list the tiles that hold the sub-cube,
  * qsv_norm from the cached sums, qsv_tile_sums, qsv_noisy_sample* (they keep their own states), stats, timers, options, qsv_sync.
  * Deferred state ends with realisation or with the next init that writes; a program refused before its init writes
  * leaves the deferred state, recipe included, as it was.
@@ -596,6 +621,8 @@ int qsv_timer_end(qsv_handle* h, double* ms);
  *                                  state is realised; 0 always realised; 1 listed whenever a block bit is fixed and the list fits.  Same words.
  *               marginals_grid [0] diagnostic: qsv_marginals_cond takes at most this many workgroups, 0 = as many as the chip holds;
  *                                  which workgroup walks a chunk changes, no bit of the result does
+ *               top_grid [0]       diagnostic: qsv_top_cond takes at most this many workgroups, 0 = as many as the chip holds;
+ *                                  which workgroup walks a block changes, no bit of the result does
  *   kernels     unroll [4], lowt_shuffle [1], pair_variant [0], kq_mfma [1], blocks_per_cu [65536]
  *               swizzle [1]        one-gate kernels: lane bit 5 of a wave access carries address bit 11 (two 512-byte runs 32 KiB apart);
  *                                  1 from 2^26 amplitudes per shard, 2 from 2^14, 0 never        lane_map_min_l [26]  same for k_multi tiles other than bits 6..10

@@ -32,6 +32,7 @@ OPTION_DEFAULTS = {"blocks_per_cu": 1 << 16, "unroll": 4, "lowt_shuffle": 1, "no
 OP_INIT_ZERO, OP_INIT_UNIFORM, OP_1Q, OP_MCX, OP_DIAG, OP_MCPHASE, OP_MUX, OP_KQ, OP_SWAP, OP_PAULI, OP_KRAUS, OP_MEASURE, OP_KRAUS2, OP_IF, OP_RESET = range(15)
 NOISY_MAX_QUBITS = 13     # qsv_noisy_sample: one trajectory's state lives in the LDS of one workgroup
 NOISY_HBM_MAX_QUBITS = 24 # qsv_noisy_sample_hbm: one trajectory's state lives in a slot of device memory
+TOP_MAX_K = 64            # QSV_TOP_MAX_K: states one qsv_top_cond call returns
 DENSITY_MAX_QUBITS = 17   # qsv_density_*: rho of W qubits is a vector of 2W qubits, 16 * 4^W bytes
 OPF_NEW_PASS = 1
 
@@ -88,6 +89,7 @@ SIGNATURES = {
     "qsv_sample_unordered": (_i, [_vp, _u64, _u64, _ip, _i, _u64p]),
     "qsv_sample_cond_unordered": (_i, [_vp, _u64, _u64, _ip, _i, _u64, _u64, _u64p, _dp]),
     "qsv_marginals_cond": (_i, [_vp, _i, _ip, _ip, _u64, _u64, _dp, _dp]),
+    "qsv_top_cond": (_i, [_vp, _i, _u64, _u64, _u64p, _dp, _ip]),
     "qsv_get_amplitudes": (_i, [_vp, _u64, _u64, _dp]),
     "qsv_set_amplitudes": (_i, [_vp, _u64, _u64, _dp]),
     "qsv_copy_state": (_i, [_vp, _vp]),
@@ -537,6 +539,19 @@ class Engine:
             res.append(out[off:off + (1 << len(g))].copy())
             off += 1 << len(g)
         return res, mass.value
+
+    def top_cond(self, k, fix_mask=0, fix_val=0):
+        """(uint64[n_found], float64[n_found]): the k most probable basis states g with (g & fix_mask) == fix_val and
+        their weights p = re*re + im*im (each operation rounded, as numpy forms it from ``amplitudes()``), by descending p,
+        equal p by ascending index; only states with p > 0, so n_found = min(k, their number).  Not normalised, this
+        process's shards only.  One pass over the matching amplitudes, exact (qsv_top_cond)."""
+        k = int(k)
+        idx = np.zeros(max(1, min(k, TOP_MAX_K)), dtype=np.uint64)          # (a k the entry point does not take is refused there)
+        p = np.zeros(idx.size, dtype=np.float64)
+        n = C.c_int(0)
+        _chk(self._lib.qsv_top_cond(self._h, k, int(fix_mask), int(fix_val), idx.ctypes.data_as(_u64p),
+                                    p.ctypes.data_as(_dp), C.byref(n)))
+        return idx[:n.value].copy(), p[:n.value].copy()
 
     def amplitudes(self, start=0, count=None):
         if count is None:

@@ -344,6 +344,34 @@ class QsvBackend:
             fv |= int(bool(v)) << pl.layout[q]
         return eng.marginals_cond(phys, fm, fv)
 
+    def top_states(self, k, fixed=None):
+        """(logical indices uint64, p) on the state the LAST run left: the k most probable basis states in which every
+        qubit of ``fixed`` ({logical qubit: 0/1}) has the given value, by descending p = |amp|^2, equal p by ascending
+        logical index; only states with p > 0.  Not normalised.  One pass over the matching amplitudes
+        (qsv_top_cond), exact; a deferred state whose fixed bits select tiles stays deferred.  The engine selects in
+        the PHYSICAL index order of the run's layout and the indices are un-permuted here: with states tied exactly at
+        the k-th place, which of them are returned is decided by the physical order (the returned pairs are still
+        sorted by (-p, logical index)); without such a tie the result does not depend on the layout.  One process only,
+        as post_select; virtual shards are fine."""
+        eng, pl = self.last_engine, self.last_plan
+        if eng is None or pl is None:
+            raise RuntimeError("top_states needs a state: run() a circuit on this backend first")
+        comm = self._last_comm
+        if comm is not None and comm.world > 1:
+            raise ValueError("top_states runs in one process; this state is spread over %d ranks" % comm.world)
+        fm = fv = 0
+        for q, v in (fixed or {}).items():
+            fm |= 1 << pl.layout[q]
+            fv |= int(bool(v)) << pl.layout[q]
+        phys, p = eng.top_cond(k, fm, fv)
+        phys = np.asarray(phys, dtype=np.uint64)
+        moved = [(q, b) for q, b in enumerate(pl.layout) if q != b]          # (most of a layout is the identity)
+        logical = phys & np.uint64(sum(1 << b for q, b in enumerate(pl.layout) if q == b))
+        for q, b in moved:
+            logical |= ((phys >> np.uint64(b)) & np.uint64(1)) << np.uint64(q)
+        order = np.lexsort((logical, -np.asarray(p, dtype=np.float64)))
+        return logical[order], np.asarray(p, dtype=np.float64)[order]
+
     def close(self):
         if self._engine is not None:
             self._engine.close()

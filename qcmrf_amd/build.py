@@ -11,7 +11,7 @@ CSRC = os.path.join(HERE, "csrc")
 OUT = os.path.join(CSRC, "libqsv.so")
 SOURCES = ["qsv_kmulti_m0_r5.hip", "qsv_kmulti_m0_r4.hip", "qsv_kmulti_m0_r3.hip", "qsv_kmulti_m0_low.hip", "qsv.hip",
            "qsv_kmulti_m1.hip", "qsv_kmulti_m2.hip", "qsv_noise.hip", "qsv_noise_hbm.hip", "qsv_noise_measure.hip", "qsv_noise_accept.hip", "qsv_noise_kraus2.hip", "qsv_noise_dynamic.hip", "qsv_density.hip", "qsv_branch.hip"]      # slowest first
-DEPENDS = SOURCES + ["qsv_common.h", "qsv_kernels.h", "qsv_kmulti.h", "qsv_kmulti_inst.h", "qsv_gates.inc", "qsv_multi.inc", "qsv_layout.inc", "qsv_measure.inc", "qsv_marginals.inc",
+DEPENDS = SOURCES + ["qsv_common.h", "qsv_kernels.h", "qsv_kmulti.h", "qsv_kmulti_inst.h", "qsv_gates.inc", "qsv_multi.inc", "qsv_layout.inc", "qsv_measure.inc", "qsv_marginals.inc", "qsv_top.inc",
                      "qsv_exec.inc", "qsv_density.inc", "qsv_noise.h", "qsv_noise_ops.h", "qsv_noise_kernel.h", "qsv_noise_hbm.h", "qsv_noise_hbm_kernel.h", "qsv_noise_hbm_shots.inc", "qsv_noise_lds_shots.inc", "qsv_density.h", "qsv_branch.h", "qsv_branch.inc", os.path.join("..", "..", "include", "qsv.h")]
 CFLAGS = ["-O3", "--offload-arch=gfx950", "-std=c++17", "-fPIC", "-munsafe-fp-atomics",
           "-Wno-unused-value", "-Wno-unused-result"]

@@ -92,3 +92,43 @@ def empirical_marginals(cliques, samples):
     if N == 0:
         raise ValueError("no samples")
     return np.concatenate([np.bincount(y, minlength=2 ** len(C)) / float(N) for C, y in zip(cliques, ys)])
+
+
+MAP_MAX_K = 64             # QSV_TOP_MAX_K: the most states one device call returns
+
+
+def _evidence_mask(n, evidence):
+    """(mask, value) over xids for ``evidence`` ({variable: 0/1}); a variable outside 0..n-1 is a ValueError"""
+    m = val = 0
+    for v, b in (evidence or {}).items():
+        v = int(v)
+        if not 0 <= v < n:
+            raise ValueError("evidence variable %d not in 0..%d" % (v, n - 1))
+        m |= 1 << (n - 1 - v)
+        val |= int(bool(b)) << (n - 1 - v)
+    return m, val
+
+
+def states_of(xid, n):
+    """(m, n) int array of the joint states with the given xids: x[i, v] the value of variable v (bit n-1-v of xid)"""
+    xid = np.asarray(xid, dtype=np.uint64).astype(np.int64)
+    return np.stack([(xid >> (n - 1 - v)) & 1 for v in range(n)], axis=1).astype(np.int64).reshape(xid.size, n)
+
+
+def map_states(cliques, theta, k=1, beta=1.0, evidence=None):
+    """(x, p): the k most probable joint states under the Gibbs distribution given ``evidence`` ({variable: 0/1}) -- exact
+    MAP inference (k = 1) and its top-k form, from ``gibbs_pmf``.  ``p`` is renormalised over the states that agree with
+    the evidence, descending; equal p by ascending xid (variable v on bit n-1-v, the convention of
+    ``hamiltonian_diagonal``).  ``x`` is an int array (m, n), x[i, v] the value of variable v; m = min(k, states that
+    agree with the evidence)."""
+    n = num_vertices(cliques)
+    if int(k) < 1:
+        raise ValueError("k = %d, at least 1" % int(k))
+    m, val = _evidence_mask(n, evidence)
+    p, _ = gibbs_pmf(cliques, theta, beta)
+    xid = np.arange(p.size, dtype=np.int64)
+    sel = xid[(xid & m) == val]
+    ps = p[sel]
+    ps = ps / ps.sum()
+    order = np.lexsort((sel, -ps))[:int(k)]
+    return states_of(sel[order], n), ps[order]

@@ -17,6 +17,8 @@ import itertools
 
 import numpy as np
 
+from . import mrf
+
 try:                                             # pragma: no cover - Qiskit absent in this image
     from qiskit import QuantumCircuit
     from qiskit.circuit.library import AND
@@ -172,6 +174,37 @@ class QCMRF(QuantumCircuit):
         if not mass > 0:
             raise ValueError("the post-selected outcome has zero probability")
         return np.concatenate([np.asarray(p, dtype=np.float64) for p in parts]) / mass, mass / norm
+
+    def map_states(self, backend, k=1, evidence=None, circuit=None, **run_options):
+        """The k most probable configurations of the Gibbs state this circuit prepares, given ``evidence`` ({variable:
+        0/1}), from ONE run and one conditioned device pass -- exact MAP inference (k = 1) and its top-k form:
+        ``(x, p, p_condition)`` with ``x`` an int array (m, n), x[i, v] the value of variable v, ``p`` their
+        probabilities given the evidence, descending (equal p by ascending index, variable v on bit n-1-v; see
+        ``QsvBackend.top_states`` for exact ties at the k-th place), and ``p_condition`` the probability that every
+        ancilla and the AND scratch qubit read 0 AND the evidence holds.  Only the amplitudes that match are read, and
+        a state the engine left deferred stays deferred.  m = min(k, matching states with p > 0).  ``circuit``: a
+        lowering of this circuit (``transpile``) to run in its place."""
+        n, W = self._n, self._n + self._num_cliques + 1
+        k = int(k)
+        if not 1 <= k <= mrf.MAP_MAX_K:
+            raise ValueError("k = %d, 1..%d supported" % (k, mrf.MAP_MAX_K))
+        fixed = {q: 0 for q in range(n, W)}
+        for v, b in (evidence or {}).items():
+            if not 0 <= int(v) < n:
+                raise ValueError("evidence variable %d not in 0..%d" % (int(v), n - 1))
+            fixed[n - 1 - int(v)] = int(bool(b))
+        run = self if circuit is None else circuit
+        if self._with_measurements:
+            backend.run(run, shots=0, post_select=self.post_selection(), **run_options)
+        else:
+            backend.run(run, shots=0, **run_options)
+        idx, p_raw = backend.top_states(k, fixed)
+        # the mass of the same condition: one more pass over the sub-cube, the bits marginals() would divide by
+        _, mass = backend.marginals([[]], fixed)
+        norm = backend.last_engine.norm()
+        if not mass > 0:
+            raise ValueError("the post-selected outcome has zero probability")
+        return mrf.states_of(idx & np.uint64((1 << n) - 1), n), p_raw / mass, mass / norm
 
     def post_selection(self):
         """``{classical bit: 0}`` for every clique ancilla: the branch in which the circuit prepares the Gibbs state

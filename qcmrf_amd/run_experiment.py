@@ -49,6 +49,8 @@ import time
 
 import numpy as np
 
+from .mrf import MAP_MAX_K
+
 
 def main(argv=None):
     ap = argparse.ArgumentParser()
@@ -79,7 +81,17 @@ def main(argv=None):
     ap.add_argument("--marginals", action="store_true",
                     help="also write every circuit's clique marginals and success probability (ideal state-vector run, one "
                          "conditioned device pass per circuit) to marginals_simulation_<SCALE>.json")
+    ap.add_argument("--map", type=int, default=None, metavar="K",
+                    help="also write every circuit's K most probable configurations (exact MAP inference for K = 1), their "
+                         "probabilities and the success probability (ideal state-vector run, one conditioned device pass per "
+                         "circuit) to map_simulation_<SCALE>.json")
     args = ap.parse_args(argv)
+    if args.map is not None and (args.method is not None or any(x is not None for x in (args.depolarizing, args.readout, args.t1, args.t2,
+                                                                                        args.gate_time, args.coherent_cx))):
+        ap.error("--map reads the ideal state vector and takes no noise option or --method: the most probable outcomes of a noisy "
+                 "run are the largest entries of the exact distribution that method=\"density_matrix\" returns (Result.get_probabilities())")
+    if args.map is not None and not 1 <= args.map <= MAP_MAX_K:
+        ap.error("--map K: K = %d, 1..%d supported" % (args.map, MAP_MAX_K))
     if args.marginals and (args.method is not None or any(x is not None for x in (args.depolarizing, args.readout, args.t1, args.t2,
                                                                                   args.gate_time, args.coherent_cx))):
         ap.error("--marginals reads the ideal state vector and takes no noise option or --method: the marginals of a noisy run "
@@ -145,6 +157,10 @@ def main(argv=None):
         rows = [qc.marginals(simulator, circuit=c) for qc, c in zip(MODELS, CIRCS)]
         with open(os.path.join(args.outdir, "marginals_simulation_" + str(args.scale) + ".json"), "w") as f:
             f.write(json.dumps([{"mu": mu.tolist(), "success": float(p)} for mu, p in rows], indent=4))
+    if args.map is not None:
+        rows = [qc.map_states(simulator, k=args.map, circuit=c) for qc, c in zip(MODELS, CIRCS)]
+        with open(os.path.join(args.outdir, "map_simulation_" + str(args.scale) + ".json"), "w") as f:
+            f.write(json.dumps([{"x": x.tolist(), "p": p.tolist(), "success": float(ps)} for x, p, ps in rows], indent=4))
     return counts
 
 
