@@ -265,6 +265,32 @@ int qsv_sample_cond_unordered(qsv_handle* h, uint64_t shots, uint64_t seed, cons
 int qsv_marginals_cond(qsv_handle* h, int n_groups, const int* group_k, const int* qubits,
                        uint64_t fix_mask, uint64_t fix_val, double* out, double* mass);
 
+/* The same marginals for n_rows conditions (fix_mask[r], fix_val[r]) on one state -- one conditional query per data row
+ * of a model -- from one launch group and one host wait per shard, not per row.  nbins = sum of 2^group_k.
+ * The contract: row r of out (n_rows x nbins, row-major) and mass[r] (mass may be NULL) are, byte for byte, what
+ * qsv_marginals_cond(h, n_groups, group_k, qubits, fix_mask[r], fix_val[r], ...) writes on the same handle state -- for
+ * every number of workgroups (marginals_grid), every split of the rows over launches (marginals_rows), every order and
+ * composition of the batch (a row repeated, alone, the rows reversed), stored and deferred shards.  Every row keeps its
+ * own compact index space and its own chunking and takes the tree of additions of qsv_marginals.inc; no floating-point
+ * atomics.  A row of zero mass is not an error: its bins and its mass are +0.0.
+ * Cost: per shard on which at least one row is live (a row whose fixed shard bits disagree with a shard is skipped
+ * there) one table upload, one launch booked under QSV_K_PROB with 16 B times the sum of the live rows' 2^(L-f), and
+ * one host wait.  Rows with the same local mask share one descriptor; a row adds 16 bytes.  Where the descriptors exceed
+ * half the arena or the partial sums the kept reduction scratch (2^24 doubles), the rows are processed in slabs of
+ * consecutive rows, each costing the above once; option marginals_rows caps a slab's rows.
+ * A deferred shard is prepared once per call, exactly as qsv_marginals_cond would for the COMMON condition (the bits set
+ * in every row's mask with the same value in every row): its tiles listed (one listed_launches, still deferred) or the
+ * shard realised, by the same rule and option post_select_list; an empty common condition realises.
+ * QSV_E_BADARG before the first launch, the handle usable afterwards: what qsv_marginals_cond refuses about the groups
+ * (same messages), n_rows outside 1..QSV_MARG_MAX_ROWS, NULL fix_mask / fix_val / out, and with a message "row %d: ..."
+ * a fix_val outside its mask or a mask bit at or above n_qubits.  More than 28 fixed bits local to a shard in some row:
+ * QSV_E_UNSUPPORTED, naming the row. */
+#define QSV_MARG_MAX_ROWS 65536
+int qsv_marginals_cond_rows(qsv_handle* h, int n_groups, const int* group_k, const int* qubits,
+                            int n_rows, const uint64_t* fix_mask, const uint64_t* fix_val,
+                            double* out  /* n_rows x nbins, row-major */,
+                            double* mass /* n_rows, may be NULL */);
+
 /* The k most probable basis states of the conditioned state in one pass: exact MAP (k = 1) and top-k inference.
  * Candidates: the global indices x owned by this process with (x & fix_mask) == fix_val; the weight of x is
  *   p(x) = re*re + im*im, each product and the sum rounded separately, no fused contraction -- deliberately NOT the fma
@@ -562,7 +588,7 @@ int qsv_get_stats(qsv_handle* h, qsv_stats* out);
  * qsv_set_amplitudes, qsv_copy_state (source), qsv_probabilities*, qsv_expect_diag, qsv_apply_*, qsv_swap_layout (and
  * its exchanges), qsv_ipc_export, qsv_density_*, a qsv_exec that does not start with an init, and qsv_norm / qsv_sample
  * when they cannot use the tile sums (cache_sums or fused_sums 0), qsv_sample_cond / qsv_marginals_cond / qsv_top_cond when no block
- * bit of the tile index is fixed (or by option post_select_list).  Entries that do not: qsv_sample on the tile path,
+ * bit of the tile index is fixed (or by option post_select_list; qsv_marginals_cond_rows: by its rows' common condition).  Entries that do not: qsv_sample on the tile path,
  * qsv_sample_cond / qsv_marginals_cond / qsv_top_cond when they list the tiles that hold the sub-cube,
  * qsv_norm from the cached sums, qsv_tile_sums, qsv_noisy_sample* (they keep their own states), stats, timers, options, qsv_sync.
  * Deferred state ends with realisation or with the next init that writes; a program refused before its init writes
@@ -621,6 +647,9 @@ int qsv_timer_end(qsv_handle* h, double* ms);
  *                                  state is realised; 0 always realised; 1 listed whenever a block bit is fixed and the list fits.  Same words.
  *               marginals_grid [0] diagnostic: qsv_marginals_cond takes at most this many workgroups, 0 = as many as the chip holds;
  *                                  which workgroup walks a chunk changes, no bit of the result does
+ *               marginals_rows [0] diagnostic: qsv_marginals_cond_rows takes at most this many rows per slab, 0 = as many as the arena and
+ *                                  the reduction scratch hold; the launches per shard change, no bit of the result does.  Refused below 0.
+ *                                  marginals_grid caps the workgroups of the batched kernel too
  *               top_grid [0]       diagnostic: qsv_top_cond takes at most this many workgroups, 0 = as many as the chip holds;
  *                                  which workgroup walks a block changes, no bit of the result does
  *   kernels     unroll [4], lowt_shuffle [1], pair_variant [0], kq_mfma [1], blocks_per_cu [65536]

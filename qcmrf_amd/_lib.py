@@ -32,6 +32,7 @@ OPTION_DEFAULTS = {"blocks_per_cu": 1 << 16, "unroll": 4, "lowt_shuffle": 1, "no
 OP_INIT_ZERO, OP_INIT_UNIFORM, OP_1Q, OP_MCX, OP_DIAG, OP_MCPHASE, OP_MUX, OP_KQ, OP_SWAP, OP_PAULI, OP_KRAUS, OP_MEASURE, OP_KRAUS2, OP_IF, OP_RESET = range(15)
 NOISY_MAX_QUBITS = 13     # qsv_noisy_sample: one trajectory's state lives in the LDS of one workgroup
 NOISY_HBM_MAX_QUBITS = 24 # qsv_noisy_sample_hbm: one trajectory's state lives in a slot of device memory
+MARG_MAX_ROWS = 65536     # QSV_MARG_MAX_ROWS: conditions one qsv_marginals_cond_rows call takes
 TOP_MAX_K = 64            # QSV_TOP_MAX_K: states one qsv_top_cond call returns
 DENSITY_MAX_QUBITS = 17   # qsv_density_*: rho of W qubits is a vector of 2W qubits, 16 * 4^W bytes
 OPF_NEW_PASS = 1
@@ -89,6 +90,7 @@ SIGNATURES = {
     "qsv_sample_unordered": (_i, [_vp, _u64, _u64, _ip, _i, _u64p]),
     "qsv_sample_cond_unordered": (_i, [_vp, _u64, _u64, _ip, _i, _u64, _u64, _u64p, _dp]),
     "qsv_marginals_cond": (_i, [_vp, _i, _ip, _ip, _u64, _u64, _dp, _dp]),
+    "qsv_marginals_cond_rows": (_i, [_vp, _i, _ip, _ip, _i, _u64p, _u64p, _dp, _dp]),
     "qsv_top_cond": (_i, [_vp, _i, _u64, _u64, _u64p, _dp, _ip]),
     "qsv_get_amplitudes": (_i, [_vp, _u64, _u64, _dp]),
     "qsv_set_amplitudes": (_i, [_vp, _u64, _u64, _dp]),
@@ -539,6 +541,27 @@ class Engine:
             res.append(out[off:off + (1 << len(g))].copy())
             off += 1 << len(g)
         return res, mass.value
+
+    def marginals_cond_rows(self, groups, masks, vals):
+        """(out float64 (B, nbins), mass float64 (B,)): ``marginals_cond`` for the B conditions (masks[r], vals[r]) on the
+        same state from one launch group and one host wait per shard; row r holds the groups' bins one after the other
+        and is, byte for byte, what ``marginals_cond(groups, masks[r], vals[r])`` returns (qsv_marginals_cond_rows)."""
+        groups = [[int(q) for q in g] for g in groups]
+        ka, kp = _ia([len(g) for g in groups])
+        qa, qp = _ia([q for g in groups for q in g] or [0])
+        ma = np.array(list(masks) or [0], dtype=np.uint64)
+        va = np.array(list(vals) or [0], dtype=np.uint64)
+        B = len(masks)
+        if len(vals) != B:
+            raise ValueError("%d masks but %d values" % (B, len(vals)))
+        # (a call with more bins or rows than the entry point takes is refused there before anything is written)
+        nbins = max(1, min(4096, sum(1 << len(g) for g in groups)))
+        rows = max(1, min(MARG_MAX_ROWS, B))
+        out = np.zeros((rows, nbins), dtype=np.float64)
+        mass = np.zeros(rows, dtype=np.float64)
+        _chk(self._lib.qsv_marginals_cond_rows(self._h, len(groups), kp, qp, B, ma.ctypes.data_as(_u64p),
+                                               va.ctypes.data_as(_u64p), out.ctypes.data_as(_dp), mass.ctypes.data_as(_dp)))
+        return out, mass
 
     def top_cond(self, k, fix_mask=0, fix_val=0):
         """(uint64[n_found], float64[n_found]): the k most probable basis states g with (g & fix_mask) == fix_val and

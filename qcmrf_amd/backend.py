@@ -372,6 +372,31 @@ class QsvBackend:
         order = np.lexsort((logical, -np.asarray(p, dtype=np.float64)))
         return logical[order], np.asarray(p, dtype=np.float64)[order]
 
+    def marginals_rows(self, groups, fixed_rows):
+        """(out (B, nbins), mass (B,)) on the state the LAST run left: ``marginals(groups, fixed_rows[r])`` for every row
+        of ``fixed_rows`` (a sequence of {logical qubit: 0/1}) from ONE device pass -- one conditional query per data row
+        of a model.  Row r of ``out`` holds the groups' bins one after the other and equals the single call's byte for
+        byte (qsv_marginals_cond_rows); a deferred state stays deferred where the bits all rows fix alike select tiles.
+        One process only, as ``marginals``; virtual shards are fine."""
+        eng, pl = self.last_engine, self.last_plan
+        if eng is None or pl is None:
+            raise RuntimeError("marginals_rows needs a state: run() a circuit on this backend first")
+        comm = self._last_comm
+        if comm is not None and comm.world > 1:
+            raise ValueError("marginals_rows runs in one process; this state is spread over %d ranks" % comm.world)
+        phys = [[pl.layout[q] for q in g] for g in groups]
+        bit = [1 << p for p in pl.layout]
+        masks, vals = [], []
+        for fixed in fixed_rows:
+            fm = fv = 0
+            for q, v in (fixed or {}).items():
+                fm |= bit[q]
+                if v:
+                    fv |= bit[q]
+            masks.append(fm)
+            vals.append(fv)
+        return eng.marginals_cond_rows(phys, masks, vals)
+
     def close(self):
         if self._engine is not None:
             self._engine.close()

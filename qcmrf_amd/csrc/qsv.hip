@@ -234,6 +234,7 @@ struct qsv_handle {
   int exec_ops_left = 1 << 30;            // qsv_exec: ops of the running program not yet consumed (group_fits lets the tail ride along)
   int opt_kq_blocks_per_cu = 0;       // k_kq_mfma grid: workgroups per CU (0: 64)
   int opt_marginals_grid = 0;         // qsv_marginals_cond: workgroups at most (0: as many as the chip holds) -- a diagnostic, no bit of the result depends on it
+  int opt_marginals_rows = 0;         // qsv_marginals_cond_rows: rows per slab at most (0: as many as the arena and the reduction scratch hold) -- a diagnostic, no bit of the result depends on it
   int opt_top_grid = 0;               // qsv_top_cond: workgroups at most (0: as many as the chip holds) -- a diagnostic, no bit of the result depends on it
   int opt_kq_grid = 0;                // matrix-core dense-gate launches (launch_kq_mfma): workgroups at most (0: no cap) -- a diagnostic, the walks of tests/_kq_cases.py
   int opt_kq3_tile = 1;               // dense 3-qubit gates on the vector units (k_kq_tile) instead of I (x) U on a 16 x 16 matrix-core tile
@@ -803,7 +804,7 @@ static int materialize_all(qsv_handle* h) {
 #include "qsv_multi.inc"     // PendingGroup, k_multi pass construction (round schedule, modes), zero tracking
 #include "qsv_layout.inc"    // qsv_apply_kq (VALU + MFMA), qsv_swap_layout: local swap and shard-bit exchange
 #include "qsv_measure.inc"   // qsv_norm / qsv_sample / qsv_probabilities / amplitude copies
-#include "qsv_marginals.inc" // qsv_marginals_cond: many marginals of the conditioned state from one pass, reproducibly
+#include "qsv_marginals.inc" // qsv_marginals_cond / qsv_marginals_cond_rows: many marginals of the conditioned state from one pass, reproducibly
 #include "qsv_top.inc"       // qsv_top_cond: the k most probable states of the conditioned state from one pass (exact MAP / top-k)
 #include "qsv_branch.inc"    // qsv_branch_mass / qsv_branch_split: slots of a wide state (level-wise trajectory walk)
 #include "qsv_exec.inc"      // qsv_exec, stats, timers, options

@@ -829,6 +829,7 @@ extern "C" int qsv_set_option(qsv_handle* h, const char* name, int value) {
   else if (!strcmp(name, "kq_blocks_per_cu")) h->opt_kq_blocks_per_cu = (int)value;
   else if (!strcmp(name, "kq_grid")) { if (value < 0) return fail(QSV_E_BADARG, "kq_grid < 0"); h->opt_kq_grid = value; }
   else if (!strcmp(name, "marginals_grid")) { if (value < 0) return fail(QSV_E_BADARG, "marginals_grid < 0"); h->opt_marginals_grid = value; }
+  else if (!strcmp(name, "marginals_rows")) { if (value < 0) return fail(QSV_E_BADARG, "marginals_rows < 0"); h->opt_marginals_rows = value; }
   else if (!strcmp(name, "top_grid")) { if (value < 0) return fail(QSV_E_BADARG, "top_grid < 0"); h->opt_top_grid = value; }
   else if (!strcmp(name, "blocksum_variant")) h->opt_blocksum_variant = value & 7;
   else if (!strcmp(name, "swizzle")) h->opt_swz = value < 0 ? 0 : (value > 2 ? 2 : value);

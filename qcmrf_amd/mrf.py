@@ -132,3 +132,30 @@ def map_states(cliques, theta, k=1, beta=1.0, evidence=None):
     ps = ps / ps.sum()
     order = np.lexsort((sel, -ps))[:int(k)]
     return states_of(sel[order], n), ps[order]
+
+
+def conditional_marginals(cliques, theta, rows, beta=1.0):
+    """(mu, p_rows) for data rows with missing entries: ``rows`` is an int array (B, n) of 0 / 1 and -1 for an unobserved
+    variable; ``mu[r]`` holds the clique marginals of the Gibbs distribution given row r's observed values, in the order
+    of ``theta`` (an all -1 row gives ``marginals``), and ``p_rows[r]`` is P(observed part of row r).  Exact, summed from
+    ``gibbs_pmf``: the host value of ``QCMRF.conditional_marginals``."""
+    n = num_vertices(cliques)
+    rows = np.asarray(rows)
+    if rows.ndim != 2 or rows.shape[1] != n:
+        raise ValueError("rows have shape %r, the model has %d variables" % (rows.shape, n))
+    if rows.size and not np.isin(rows, (-1, 0, 1)).all():
+        raise ValueError("a row entry is 0, 1 or -1 (unobserved)")
+    rows = rows.astype(np.int64)
+    p, _ = gibbs_pmf(cliques, theta, beta)
+    xid = np.arange(p.size)
+    ys = clique_index(cliques, xid)
+    mu = np.zeros((rows.shape[0], dimension(cliques)))
+    p_rows = np.zeros(rows.shape[0])
+    for r, row in enumerate(rows):
+        w = p.copy()
+        for v in range(n):
+            if row[v] >= 0:
+                w[((xid >> (n - 1 - v)) & 1) != row[v]] = 0.0
+        p_rows[r] = w.sum()
+        mu[r] = np.concatenate([np.bincount(y, weights=w, minlength=2 ** len(C)) for C, y in zip(cliques, ys)]) / p_rows[r]
+    return mu, p_rows

@@ -175,6 +175,62 @@ class QCMRF(QuantumCircuit):
             raise ValueError("the post-selected outcome has zero probability")
         return np.concatenate([np.asarray(p, dtype=np.float64) for p in parts]) / mass, mass / norm
 
+    def conditional_marginals(self, backend, rows, circuit=None, **run_options):
+        """The clique marginals of the Gibbs state given every data row's observed values, from ONE run and ONE batched
+        device pass: ``(mu, p_rows, p_success)``.  ``rows`` is an int array (B, n), rows[r, v] the value of variable v or
+        -1 where it is unobserved; ``mu[r]`` is ``marginals`` of the state conditioned on row r's evidence (length
+        ``dimension``, the order of ``theta``), ``p_rows[r]`` is P(observed part of row r) under the Gibbs distribution
+        and ``p_success`` the probability that every ancilla and the AND scratch qubit read 0.  Every row fixes those
+        qubits to 0 and its observed variables (variable v on qubit n-1-v); one more condition fixes the ancillas
+        alone, its mass is the denominator of ``p_rows``.  With these, beta (mean_r mu[r] - mu) is the gradient of the
+        mean marginal log-likelihood of incomplete data (``learn.fit_incomplete``).  A row of probability zero raises
+        ValueError naming it.  A state the engine left deferred stays deferred.  A row fixes at most 28 qubits of a
+        shard, the ancillas included (the engine refuses a row beyond that, naming it).  ``circuit``: a lowering of this
+        circuit (``transpile``) to run in its place."""
+        n, W = self._n, self._n + self._num_cliques + 1
+        rows = np.asarray(rows)
+        if rows.ndim != 2 or rows.shape[1] != n:
+            raise ValueError("rows have shape %r, the model has %d variables" % (rows.shape, n))
+        if rows.size and not np.isin(rows, (-1, 0, 1)).all():
+            raise ValueError("a row entry is 0, 1 or -1 (unobserved)")
+        run = self if circuit is None else circuit
+        if self._with_measurements:
+            backend.run(run, shots=0, post_select=self.post_selection(), **run_options)
+        else:
+            backend.run(run, shots=0, **run_options)
+        anc = {q: 0 for q in range(n, W)}
+        fixed_rows = []
+        for row in rows:
+            f = dict(anc)
+            f.update({n - 1 - v: int(row[v]) for v in range(n) if row[v] >= 0})
+            fixed_rows.append(f)
+        fixed_rows.append(anc)
+        groups = [[n - 1 - v for v in reversed(C)] for C in self._cliques]
+        out, mass = backend.marginals_rows(groups, fixed_rows)
+        norm = backend.last_engine.norm()
+        if not mass[-1] > 0:
+            raise ValueError("the post-selected outcome has zero probability")
+        for r in range(rows.shape[0]):
+            if not mass[r] > 0:
+                raise ValueError("row %d has zero probability" % r)
+        B = rows.shape[0]
+        return out[:B] / mass[:B, None], mass[:B] / mass[-1], mass[-1] / norm
+
+    def predict_proba(self, backend, rows, variable, circuit=None, **run_options):
+        """P(x_variable = 1 | observed part of row r) for every row of ``rows`` (as in ``conditional_marginals``, which
+        it calls once): read off the marginals of the first clique that contains the variable; a variable the row
+        observes returns its value."""
+        variable = int(variable)
+        hit = [(ci, C) for ci, C in enumerate(self._cliques) if variable in C]
+        if not hit:
+            raise ValueError("variable %d is in no clique" % variable)
+        ci, C = hit[0]
+        mu = self.conditional_marginals(backend, rows, circuit=circuit, **run_options)[0]
+        off = sum(2 ** len(D) for D in self._cliques[:ci])
+        # y counts the clique states with the first variable of C most significant
+        sel = [y for y in range(2 ** len(C)) if (y >> (len(C) - 1 - list(C).index(variable))) & 1]
+        return mu[:, [off + y for y in sel]].sum(axis=1)
+
     def map_states(self, backend, k=1, evidence=None, circuit=None, **run_options):
         """The k most probable configurations of the Gibbs state this circuit prepares, given ``evidence`` ({variable:
         0/1}), from ONE run and one conditioned device pass -- exact MAP inference (k = 1) and its top-k form:
